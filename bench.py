@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- images/s through the vanishing-point hot path (CNN forward -> EM refinement).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload yud|stress]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload yud|stress] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic images whose inputs (sphere
 rasters, line segments) are already resident in HBM: AlexNet-500 forward on the B x 500 x 500
@@ -48,10 +48,6 @@ import sys
 import time
 
 import numpy as np
-
-# one hardware queue per stream (1 CNN + the EM lanes + torch's own): with the default of 4 a fifth stream shares
-# a queue, and a CNN kernel can end up queued behind a 20 ms EM kernel.  Must be set before HIP initialises.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -104,45 +100,28 @@ def parse():
     ap.add_argument("--no-alt", action="store_true", help="skip the extra timed legs (alt_exact_operands, fixture prior, from the lines)")
     ap.add_argument("--no-from-lines", action="store_true", help="skip the from_lines leg (raster -> CNN -> EM per step)")
     ap.add_argument("--cpu-sample", type=int, default=0, help="images timed on the CPU (default 6 yud / 1 stress)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (see dump_outputs)")
     return ap.parse_args()
 
 
 def visible_gpus():
-    """GPUs this process would see, counted WITHOUT touching the HIP runtime (a process that has initialised HIP must
-    not start the ranks): KFD's topology nodes with SIMDs, narrowed by HIP_/ROCR_/CUDA_VISIBLE_DEVICES.  None if the
-    topology cannot be read (then the children validate the count themselves)."""
-    import glob
-    n = 0
-    nodes = glob.glob("/sys/class/kfd/kfd/topology/nodes/*/properties")
-    if not nodes:       # no KFD topology (no GPU driver, or a sandbox): ask a throw-away child process instead
-        import subprocess
-        try:
-            r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count())"],
-                               capture_output=True, text=True, timeout=300)
-            return int(r.stdout.strip().splitlines()[-1])
-        except (OSError, ValueError, IndexError, subprocess.TimeoutExpired):
-            return None
-    for f in nodes:
-        try:
-            props = dict(line.split()[:2] for line in open(f) if len(line.split()) >= 2)
-        except OSError:
-            return None
-        if int(props.get("simd_count", "0")) > 0:
-            # a GPU node; containers restrict GPUs by withholding the render node, so count only what can be opened
-            minor = props.get("drm_render_minor")
-            if minor is None or os.access("/dev/dri/renderD%s" % minor, os.R_OK | os.W_OK):
-                n += 1
-    for var in ("HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):
-        v = os.environ.get(var)
-        if v is not None:
-            n = min(n, len([x for x in v.split(",") if x.strip() != ""]))
-    return n
+    """GPUs this process would see, counted by a throw-away child process: a process that has initialised HIP must not
+    start the ranks, and KFD's topology and the render nodes a container shows can include GPUs its processes may not
+    use.  None if the child fails (then the ranks validate the count themselves)."""
+    import subprocess
+    try:
+        r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count())"],
+                           capture_output=True, text=True, timeout=300)
+        return int(r.stdout.strip().splitlines()[-1])
+    except (OSError, ValueError, IndexError, subprocess.TimeoutExpired):
+        return None
 
 
 def spawn_ranks(args):
     """--gpus N with no launcher environment: run N ranks as CHILD processes (torch.distributed.run, one per
-    GPU) and return their exit code.  This parent never touches the GPU: it counts devices from sysfs (visible_gpus),
-    not through torch / HIP, and every child checks its own device."""
+    GPU) and return their exit code.  This parent never touches the GPU: a throw-away child counts the devices
+    (visible_gpus), and every rank checks its own device."""
     import socket
     import subprocess
     have = visible_gpus()
@@ -472,6 +451,7 @@ def extra_workloads(args, local_rank):
     a.workload, a.steps, a.warmup, a.images = "stress", 3, 1, 0
     a.no_alt = a.no_cpu_baseline = True
     a.em_wgs, a.cnn_precision = -1, 0
+    a.dump_outputs = None                                # (the dump is the headline run's)
     s = run_workload(a, None, 0, local_rank, 1)
     out["stress"] = {k: s[k] for k in ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "config", "stage_ms",
                                        "cnn_layer_ms", "em_stats", "roofline", "cnn_range_check")}
@@ -551,6 +531,46 @@ def get_net(local_rank, rt_cnn):
         _NETS[key] = (cnn.Net(cnn.synthetic_weights(0), cnn.synthetic_mean(0), device=local_rank, runtime=rt_cnn),
                       cnn.synthetic_weights(0), cnn.synthetic_mean(0))
     return _NETS[key]
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, out, resp, offsets):
+    """--dump-outputs: the last timed step's results as <path>/<name>.npy, float32 or float64, so that two builds can be compared
+    output for output.  Per image, what em.em_batch hands a caller: status and flags, and for status 0 num_vp, iterations,
+    vp / sigma / counts / counts_weighted [:num_vp] and vp_assoc of its lines; every other entry is 0 (the library leaves it
+    unset).  cnn_response: the CNN's maps, the EM's prior.  Above DUMP_LIMIT_BYTES in all, a seeded sample of the images is
+    written instead; image_index names the images written."""
+    host = {k: out[k].cpu().numpy() for k in ("vp", "sigma", "counts", "counts_weighted", "num_vp", "vp_assoc", "iterations",
+                                               "status", "flags")}
+    offs = np.asarray(offsets, dtype=np.int64)
+    batch = offs.shape[0] - 1
+    ok = host["status"] == 0
+    m = np.where(ok, host["num_vp"], 0)
+    keep = np.arange(host["vp"].shape[1])[None, :] < m[:, None]
+    per_image = {"cnn_response": resp.reshape(batch, 20, 20).cpu().numpy().astype(np.float32),
+                 "status": host["status"].astype(np.float64),
+                 "flags": (host["flags"].astype(np.int64) & 0xffffffff).astype(np.float64),
+                 "num_vp": m.astype(np.float64),
+                 "iterations": np.where(ok, host["iterations"], 0).astype(np.float64),
+                 "vp": np.where(keep[:, :, None], host["vp"], 0.0)}
+    for k in ("sigma", "counts", "counts_weighted"):
+        per_image[k] = np.where(keep, host[k], 0.0)
+    n_lines = np.diff(offs)
+    assoc = np.where(np.repeat(ok, n_lines), host["vp_assoc"][:offs[-1]], 0).astype(np.float64)
+    row_bytes = sum(a[0].nbytes for a in per_image.values()) + 8 * (n_lines + 1)      # + vp_assoc and image_index
+    budget = DUMP_LIMIT_BYTES - 128 * (len(per_image) + 2)                          # (a 128-byte .npy header per file)
+    order = np.arange(batch)
+    if row_bytes.sum() > budget:
+        order = np.random.RandomState(0).permutation(batch)
+    images = np.sort(order[:np.searchsorted(np.cumsum(row_bytes[order]), budget, side="right")])
+    arrays = {k: v[images] for k, v in per_image.items()}
+    arrays["vp_assoc"] = np.concatenate([assoc[offs[b]:offs[b + 1]] for b in images])
+    arrays["image_index"] = images.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def run_workload(args, dist, rank, local_rank, world):
@@ -705,6 +725,8 @@ def run_workload(args, dist, rank, local_rank, world):
     cnn_finite = bool(torch.isfinite(resp_last).all().item())
     assert cnn_range == 0 and cnn_finite, "CNN left the fp16-pair range (flags %#x) or produced non-finite maps" % cnn_range
     out = {q: (v.clone() if torch.is_tensor(v) else v) for q, v in out.items()}   # the ring's buffers are reused by the legs below
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, resp_last, d["offsets"])
     rank_elapsed = [elapsed]
     if dist is not None:
         tall = torch.zeros(dist.get_world_size(), dtype=torch.float64, device=rt.tdev)

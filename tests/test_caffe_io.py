@@ -57,11 +57,59 @@ def test_prototxt_check(tmp_path):
         caffe_io.check_deploy_prototxt(str(bad))
 
 
-def test_reference_deploy_prototxt_if_present():
-    path = "/root/reference/cnn/deploy.prototxt"          # build container only
-    if not os.path.isfile(path):
-        pytest.skip("reference tree not present (GPU box)")
-    assert caffe_io.check_deploy_prototxt(path)
+_PARAMS = "  param {\n    lr_mult: 1\n    decay_mult: 1\n  }\n  param {\n    lr_mult: 2\n    decay_mult: 0\n  }\n"
+
+
+def _caffe_layout_text(conv2_group=2):
+    """The whole deploy file, as Caffe's model definitions spell it out: bottom / top, `param` blocks nested in the weighted
+    layers, and the ReLU, LRN, Pooling, Dropout and Softmax layers between them."""
+    blocks = ['name: "AlexNet_for_VP_classification"\nforce_backward: true\nlayer {\n  name: "data"\n  type: "Input"\n  top: "data"\n'
+              '  input_param { shape: { dim: 1 dim: 1 dim: 500 dim: 500 } }\n}\n']
+    prev = ["data"]
+
+    def add(name, kind, body="", weighted=False, in_place=False):
+        top = prev[0] if in_place else name
+        blocks.append('layer {\n  name: "%s"\n  type: "%s"\n  bottom: "%s"\n  top: "%s"\n%s%s}\n'
+                      % (name, kind, prev[0], top, _PARAMS if weighted else "", body))
+        prev[0] = top
+
+    def conv(name, n, k, s=1, p=0, g=1):
+        fields = ["num_output: %d" % n] + (["pad: %d" % p] if p else []) + ["kernel_size: %d" % k] + \
+                 (["group: %d" % g] if g != 1 else []) + (["stride: %d" % s] if s != 1 else [])
+        add(name, "Convolution", "  convolution_param {\n%s  }\n" % "".join("    %s\n" % f for f in fields), weighted=True)
+        add("relu" + name[4:], "ReLU", in_place=True)
+
+    lrn = "  lrn_param {\n    local_size: 5\n    alpha: 0.0001\n    beta: 0.75\n  }\n"
+    pool = "  pooling_param {\n    pool: MAX\n    kernel_size: 3\n    stride: 2\n  }\n"
+    conv("conv1", 96, 11, s=4)
+    add("norm1", "LRN", lrn)
+    add("pool1", "Pooling", pool)
+    conv("conv2", 256, 5, p=2, g=conv2_group)
+    add("norm2", "LRN", lrn)
+    add("pool2", "Pooling", pool)
+    conv("conv3", 384, 3, p=1)
+    conv("conv4", 384, 3, p=1, g=2)
+    conv("conv5", 256, 3, p=1, g=2)
+    add("pool5", "Pooling", pool)
+    for i in (6, 7):
+        add("fc%d" % i, "InnerProduct", "  inner_product_param {\n    num_output: 4096\n  }\n", weighted=True)
+        add("relu%d" % i, "ReLU", in_place=True)
+        add("drop%d" % i, "Dropout", "  dropout_param {\n    dropout_ratio: 0.5\n  }\n", in_place=True)
+    add("fc8_20x20", "InnerProduct", "  inner_product_param {\n    num_output: 400\n  }\n", weighted=True)
+    add("prob", "Softmax")
+    return "".join(blocks)
+
+
+def test_deploy_prototxt_in_caffe_layout(tmp_path):
+    """A deploy file laid out as the reference's cnn/deploy.prototxt is: layer blocks with nested messages, and layers
+    without weights between the ones the topology check reads."""
+    good = tmp_path / "deploy.prototxt"
+    good.write_text(_caffe_layout_text())
+    assert caffe_io.check_deploy_prototxt(str(good))
+    bad = tmp_path / "bad.prototxt"
+    bad.write_text(_caffe_layout_text(conv2_group=1))
+    with pytest.raises(ValueError):
+        caffe_io.check_deploy_prototxt(str(bad))
 
 
 def test_reference_result_pickles_load(tmp_path):

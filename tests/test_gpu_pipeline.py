@@ -147,11 +147,12 @@ def test_bench_modes_produce_a_valid_line(mode):
         assert fl["results_equal_unpipelined_pass"] is True  # three stages give one after the other
 
 
-@pytest.mark.parametrize("ranks", [2, 8])
+@pytest.mark.parametrize("ranks", [2, 4])
 def test_sharded_benchmark_ranks_sharing_one_gpu(tmp_path, ranks):
-    """benchmark.py --hlw --synthetic with TWO / EIGHT ranks (torch.distributed.run, as on an 8-GPU node) that share this
+    """benchmark.py --hlw --synthetic with TWO / FOUR ranks (torch.distributed.run, as on an 8-GPU node) that share this
     box's GPU: cost-balanced shards, the real EM on each rank, records gathered (gloo here: RCCL refuses several ranks on
-    one device), AUC on rank 0 -- and the same AUC as the one-process run, a clean exit of every rank."""
+    one device), AUC on rank 0 -- and the same AUC as the one-process run, a clean exit of every rank.  (At most four: the
+    ranks and this process all hold the GPU, and a shared GPU host allows six such processes at a time.)"""
     import os
     import re
     import subprocess
@@ -175,10 +176,10 @@ def test_sharded_benchmark_ranks_sharing_one_gpu(tmp_path, ranks):
     assert auc1 == auc2 and 0.5 < auc1 <= 1.0
 
 
-@pytest.mark.parametrize("ranks", [2, 8])
+@pytest.mark.parametrize("ranks", [2, 4])
 def test_bench_ranks_sharing_one_gpu(ranks):
     """bench.py launched the way the driver launches it for N > 1 (torch.distributed.run, RANK / WORLD_SIZE in the
-    environment), two / eight ranks sharing this box's GPU over gloo: image shards per rank, per-step record gather,
+    environment), two / four ranks (at most four, as above) sharing this box's GPU over gloo: image shards per rank, per-step record gather,
     barrier + max-over-ranks timing, ONE JSON line from rank 0 with n_gpus = ranks_seen = N, no 'workloads' part (that
     is the one-GPU default run's), host threads divided among the ranks."""
     import json
