@@ -168,6 +168,24 @@ int vpk_cnn_calibrate(vpk_handle* h, const uint8_t* rasters, int n);
 int vpk_cnn_get_activation_scales(vpk_handle* h, float scales[6]);
 int vpk_cnn_set_activation_scales(vpk_handle* h, const float scales[6]);
 int vpk_cnn_range_flags(vpk_handle* h, uint32_t* flags_out);
+/* Per-image flags and the exact recompute of flagged images (the range POLICY of the handle).
+ *   vpk_cnn_set_range_policy   0 = RAISE (the default): the above, nothing else changes.  1 = RECOMPUTE_EXACT: after the pair
+ *                          forward of each chunk, the images whose pair forward clamped anything are found on the device and
+ *                          recomputed there with exact operands (the vpk_cnn_set_algorithm(2) forward with the default conv1, the
+ *                          same bits as that forward run on those rasters alone as one batch in their order); their maps replace the
+ *                          pair results in `out` on the handle's stream, before anything behind the forward reads them, with no
+ *                          host wait.  A recomputed image is NOT reported through vpk_cnn_range_flags -- its map is the net's --
+ *                          so that call returns VPK_OK for it.  Any other value: VPK_ERR_ARG.  Modes other than the default
+ *                          arithmetic (vpk_cnn_set_algorithm(0 .. 3), vpk_cnn_set_precision(1)) never clamp and run no pass.
+ *   vpk_cnn_image_range_flags  waits for the stream and copies the per-image bits (as in vpk_cnn_range_flags) of the LAST
+ *                          vpk_cnn_forward (a vpk_pipeline_step's included) into flags_out[0 .. batch); `batch` must equal that
+ *                          call's (VPK_ERR_ARG otherwise).  Under both policies; under RECOMPUTE_EXACT they name the images that
+ *                          were recomputed.  vpk_cnn_forward_tap (debugging) ignores the policy and keeps no per-image bits.
+ *   vpk_cnn_recomputed     waits for the stream, returns in *n_out how many images were recomputed since the previous call
+ *                          and clears the count. */
+int vpk_cnn_set_range_policy(vpk_handle* h, int policy);
+int vpk_cnn_image_range_flags(vpk_handle* h, int batch, uint32_t* flags_out);
+int vpk_cnn_recomputed(vpk_handle* h, int64_t* n_out);
 /* replaces: caffe_forward (evaluation.py:34-38) for a batch: sphere B x 500 x 500 uint8 ->
  * out B x 20 x 20 fp32 (sigout).  max batch per call is unbounded (internally chunked).  `sphere` must be 4-byte
  * aligned (device allocations are). */
@@ -313,7 +331,9 @@ size_t vpk_em_workspace_bytes(const vpk_handle* h, int batch, int n_max, const v
  * enqueued from C++: the host spends tens of microseconds per step.  Buffers as for vpk_cnn_forward / vpk_em_batch;
  * `events`: NULL or four hipEvent_t of the caller (any may be NULL) recorded before / after the CNN on its stream and
  * before / after the EM on its stream.  `cnn` and `em` may be the same handle (one stream: the stages run in turn).
- * The buffers of a step must not be reused before its EM has finished: `reuse_event` expresses that on the device. */
+ * The buffers of a step must not be reused before its EM has finished: `reuse_event` expresses that on the device.
+ * The CNN half is vpk_cnn_forward: under vpk_cnn_set_range_policy(cnn, 1) the exact recompute of flagged images is part of it
+ * and is enqueued before the event that orders the EM behind the CNN, so the EM reads the recomputed maps. */
 typedef struct vpk_step_args {
     const uint8_t* sphere;          /* B x sphere_size x sphere_size */
     int32_t batch, sphere_size;

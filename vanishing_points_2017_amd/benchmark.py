@@ -37,6 +37,8 @@ def build_parser():
     p.add_argument('--force-dist', action='store_true',
                    help='initialise torch.distributed (RCCL unless VPK_DIST_BACKEND says otherwise) even with one rank: the N > 1 '
                         'code path -- process group, barriers, the record gather on the GPU -- on a one-GPU box')
+    p.add_argument('--cnn-range', dest='cnn_range', choices=['raise', 'recompute_exact'], default='raise',
+                   help='CNN range policy: raise on a clamped fp16-pair activation, or recompute those images exactly')
     p.add_argument('--gpus', type=int, default=1,
                    help='GPUs of this node to shard the images over (one process per GPU; results gathered with one '
                         'RCCL all_gather).  Without a launcher environment the ranks are started as child processes.')
@@ -194,7 +196,7 @@ def main(argv=None):
                   % config.cnn_weights_path)
         else:
             evaluation.run_cnn(dataset, mean_file=config.cnn_mean_path, model_def=config.cnn_config_path,
-                               model_weights=config.cnn_weights_path, gpu=device)
+                               model_weights=config.cnn_weights_path, gpu=device, range_policy=args.cnn_range)
     if dist is not None:
         dist.barrier()
     start = 25 if (args.yud or args.ecd) else 0                              # :69

@@ -4,7 +4,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import VpkRangeError
+from ._lib import VPK_ERR_RANGE, VpkRangeError
 from .runtime import get_runtime
 
 # (name, weight shape in Caffe layout, fan-in) per cnn/deploy.prototxt
@@ -13,6 +13,16 @@ LAYER_SHAPES = [
     ("conv4", (384, 192, 3, 3)), ("conv5", (256, 192, 3, 3)), ("fc6", (4096, 57600)),
     ("fc7", (4096, 4096)), ("fc8", (400, 4096)),
 ]
+# vpk_cnn_set_range_policy: what a forward does with images whose fp16-pair activations were clamped (include/vpk.h)
+RANGE_POLICIES = {"raise": 0, "recompute_exact": 1}
+
+
+def range_policy_code(policy):
+    if policy not in RANGE_POLICIES:
+        raise ValueError("range policy must be one of %s, got %r" % (sorted(RANGE_POLICIES), policy))
+    return RANGE_POLICIES[policy]
+
+
 TAP_SHAPES = [(96, 123, 123), (96, 61, 61), (256, 61, 61), (256, 30, 30), (384, 30, 30), (384, 30, 30),
               (256, 30, 30), (256, 15, 15), (4096,), (4096,), (400,)]
 
@@ -59,6 +69,7 @@ class Net(object):
         mean = np.ascontiguousarray(np.asarray(mean, dtype=np.float32).reshape(500, 500))
         arr = (ctypes.c_void_p * 16)(*blobs)
         self.rt.check(self.rt.lib.vpk_cnn_load(self.rt.h, arr, ctypes.c_void_p(mean.ctypes.data)))
+        self._last_batch = None          # batch of the last untapped forward (image_range_flags)
 
     def forward_device(self, sphere, tap=None):
         """sphere: uint8 device tensor (B,500,500) -> float32 device tensor (B,20,20) [, tap tensor]."""
@@ -69,6 +80,7 @@ class Net(object):
             out = t.empty((batch, 20, 20), dtype=t.float32, device=rt.tdev)
             if tap is None:
                 rt.check(rt.lib.vpk_cnn_forward(rt.h, rt.ptr(sphere), batch, rt.ptr(out)))
+                self._last_batch = batch
                 return out
             tp = t.empty((batch,) + TAP_SHAPES[tap], dtype=t.float32, device=rt.tdev)
             rt.check(rt.lib.vpk_cnn_forward_tap(rt.h, rt.ptr(sphere), batch, rt.ptr(out), int(tap), rt.ptr(tp)))
@@ -162,7 +174,7 @@ class Net(object):
         activation stayed inside fp16's range.  Does not raise."""
         w = ctypes.c_uint32(0)
         rc = self.rt.lib.vpk_cnn_range_flags(self.rt.h, ctypes.byref(w))
-        if rc not in (0, -6):
+        if rc not in (0, VPK_ERR_RANGE):
             self.rt.check(rc)
         return int(w.value)
 
@@ -170,9 +182,31 @@ class Net(object):
         """Raise VpkRangeError if a forward since the last check clamped an activation (include/vpk.h: vpk_cnn_range_flags)."""
         w = ctypes.c_uint32(0)
         rc = self.rt.lib.vpk_cnn_range_flags(self.rt.h, ctypes.byref(w))
-        if rc == -6:
-            raise VpkRangeError("libvpk error -6: %s" % self.rt.lib.vpk_last_error(self.rt.h).decode(), int(w.value))
+        if rc == VPK_ERR_RANGE:
+            raise VpkRangeError("libvpk error %d: %s" % (rc, self.rt.lib.vpk_last_error(self.rt.h).decode()), int(w.value))
         self.rt.check(rc)
+
+    def set_range_policy(self, policy):
+        """"raise" (the default): a forward whose fp16-pair activations were clamped raises VpkRangeError.  "recompute_exact":
+        the images that were clamped are recomputed on the device with exact operands (the set_algorithm(2) forward) and their maps
+        replace the pair results; such an image raises nothing (include/vpk.h: vpk_cnn_set_range_policy)."""
+        self.rt.check(self.rt.lib.vpk_cnn_set_range_policy(self.rt.h, range_policy_code(policy)))
+
+    def image_range_flags(self, batch=None):
+        """Waits for the stream; the range bits of each image of the last forward (numpy uint32, one per image): bit li = the
+        consuming layer (1 = conv2 ... 6 = fc7), 0 = nothing clamped.  Under "recompute_exact": the images that were recomputed."""
+        n = self._last_batch if batch is None else int(batch)
+        if n is None:
+            raise ValueError("image_range_flags: no forward yet")
+        flags = np.zeros(n, dtype=np.uint32)
+        self.rt.check(self.rt.lib.vpk_cnn_image_range_flags(self.rt.h, n, flags.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
+        return flags
+
+    def recomputed(self):
+        """Waits for the stream; how many images were recomputed with exact operands since the previous call (and clears it)."""
+        n = ctypes.c_int64(0)
+        self.rt.check(self.rt.lib.vpk_cnn_recomputed(self.rt.h, ctypes.byref(n)))
+        return int(n.value)
 
     def set_profiling(self, on=True):
         self.rt.check(self.rt.lib.vpk_cnn_set_profiling(self.rt.h, int(bool(on))))
@@ -212,9 +246,11 @@ class LazyNet(object):
     the first forward (the reference passes it to caffe_forward, evaluation.py:34-35).  The HIP net is
     (re)built when the mean changes, because `image - mean` is fused into conv1's input load."""
 
-    def __init__(self, weights, device=0, mean=None):
+    def __init__(self, weights, device=0, mean=None, range_policy="raise"):
         self.weights = weights
         self.device = device
+        self.range_policy = range_policy
+        range_policy_code(range_policy)
         self._mean = None
         self._net = None
         if mean is not None:
@@ -224,6 +260,7 @@ class LazyNet(object):
         mean = np.ascontiguousarray(np.asarray(mean_arr, dtype=np.float32).reshape(500, 500))
         if self._net is None or not np.array_equal(mean, self._mean):
             self._net = Net(self.weights, mean, device=self.device)
+            self._net.set_range_policy(self.range_policy)
             self._mean = mean
         return self._net
 

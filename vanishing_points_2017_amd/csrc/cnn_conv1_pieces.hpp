@@ -102,7 +102,8 @@ __global__ __launch_bounds__(C1B_THREADS, 3) void conv1_pieces_kernel(const unsi
                                                                       int OHp, int OWp, int opad, int batch, int group, float oscale,
                                                                       int* __restrict__ item_counter, int total_items,
                                                                       unsigned short* __restrict__ out_planes, float p_ascale,
-                                                                      unsigned* __restrict__ range_word) {
+                                                                      unsigned* __restrict__ range_word, unsigned* __restrict__ img_range,
+                                                                      const int* __restrict__ live) {
     __shared__ __attribute__((aligned(16))) unsigned short Xs[2][C1B_XS];
     // The output patch as [column][channel] (round 6; it was [channel][column]): a lane's four accumulator values are four consecutive
     // channels of one column, the LRN's window runs along the channels and a pooling thread takes four channels of a pixel -- every
@@ -167,6 +168,10 @@ __global__ __launch_bounds__(C1B_THREADS, 3) void conv1_pieces_kernel(const unsi
     const bool pl_on = tid < 24 * C1_QR * C1_QC;
     bool pl_bad = false;
 
+    if (live) {                                                          // recompute pass: the device count's images only
+        batch = __builtin_amdgcn_readfirstlane(*live);
+        total_items = C1B_PATCHES * ((batch + group - 1) / group);
+    }
     int item = blockIdx.x, parity = 0, buf = 0;
     if (item >= total_items) return;
     int pr = (item % C1B_PATCHES) / C1_TC, pc = item % C1_TC;
@@ -348,12 +353,15 @@ __global__ __launch_bounds__(C1B_THREADS, 3) void conv1_pieces_kernel(const unsi
                     if (pw0 + px < C1_POOL) o[px] = __builtin_fmaxf(__builtin_fmaxf(cm[2 * px], cm[2 * px + 1]), cm[2 * px + 2]);
             }
         }
+        if (out_planes) {                                                // (conv2 is the consuming layer; per tile: one image)
+            range_report(pl_bad, range_word, 1u << 1, img_range ? img_range + b : nullptr);
+            pl_bad = false;
+        }
         if (!n_on) break;
         if (n_fresh) parity ^= 1;
         item = n_item; pr = n_pr; pc = n_pc; b = n_b; b1 = n_b1; fresh = n_fresh;
         buf ^= 1;
     }
-    if (out_planes) range_report(pl_bad, range_word, 1u << 1);         // (conv2 is the consuming layer)
 }
 
 

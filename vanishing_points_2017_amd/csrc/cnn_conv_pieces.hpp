@@ -58,6 +58,8 @@ struct PieceDims {
     float o_ascale;                             //   and its activation scale
     unsigned* range_word;                       //   and where an activation beyond fp16's range is reported (split2h_guard), as bit
     unsigned range_bit;                         //   range_bit (the consuming layer's)
+    unsigned* img_range;                        //   and into the image's word of the forward's per-image flags (null: not kept)
+    const int* live;                            // recompute pass (vpk_cnn_set_range_policy): the device count of images, B is its upper bound
     float oscale;                               // 1 / (weight scale x activation scale) of the fp16-pair operands (a power of two); 1 for bf16 pieces
 };
 
@@ -83,8 +85,10 @@ struct PieceDims {
 // per (image, channel group, row): 16 channels x Wp values in, 2 NP x Wp words out.
 template <int NP>
 __global__ __launch_bounds__(256) void to_planes_kernel(const float* __restrict__ in, unsigned short* __restrict__ out, int C, int Hp,
-                                                        int Wp, float ascale, unsigned* __restrict__ range_word, unsigned range_bit) {
+                                                        int Wp, float ascale, unsigned* __restrict__ range_word, unsigned range_bit,
+                                                        unsigned* __restrict__ img_range, const int* __restrict__ live) {
     const int y = blockIdx.x, cg = blockIdx.y, b = blockIdx.z;
+    if (live && b >= *live) return;                              // (recompute pass: slots beyond the device count)
     const float* src = in + (((size_t)b * C + cg * 16) * Hp + y) * Wp;
     u32x4* dst = reinterpret_cast<u32x4*>(out) + (((size_t)b * (C >> 4) + cg) * (2 * NP) * Hp + y) * Wp;
     bool bad = false;
@@ -105,7 +109,7 @@ __global__ __launch_bounds__(256) void to_planes_kernel(const float* __restrict_
             dst[(size_t)(2 * q + h) * Hp * Wp + x] = w4;
         }
     }
-    if (NP == 2) range_report(bad, range_word, range_bit);
+    if (NP == 2) range_report(bad, range_word, range_bit, img_range ? img_range + b : nullptr);
 }
 
 template <int N>
@@ -154,6 +158,10 @@ __global__ __launch_bounds__(CP_THREADS, 2) void conv_pieces_kernel(PieceDims d,
     constexpr int GST = (PR > 8 ? PR * 128 : 1024) + 128;    // bytes between column groups: the rows x 128 bytes, + 128 so that the two or three
                                                              // groups a 16-lane quarter of a ds_read_b128 touches fall on different banks
     static_assert(GST % 256 == 128, "odd multiple of 128 bytes");
+    if (d.live) {                                            // recompute pass: only the tiles of the device count's images
+        d.B = __builtin_amdgcn_readfirstlane(*d.live);
+        total_tiles = d.groups * d.B * d.rtiles * d.ctiles * d.mtiles;
+    }
     constexpr int PLANE = KPP * GST;                         // bytes per plane in LDS: [column group of 8][row (8)][column] 16-byte words
     constexpr int NPL = 2 * NP;                              // planes per channel group: piece x k half
     constexpr int PBUF = NPL * PLANE;                        // bytes per patch buffer
@@ -451,7 +459,7 @@ __global__ __launch_bounds__(CP_THREADS, 2) void conv_pieces_kernel(PieceDims d,
                         *reinterpret_cast<u32x2*>(pbase + (w0 + 2u * wplane)) = u32x2{(unsigned)h1[0] | ((unsigned)h1[1] << 16), (unsigned)h1[2] | ((unsigned)h1[3] << 16)};
                     }
                 }
-                range_report(bad, d.range_word, d.range_bit);
+                range_report(bad, d.range_word, d.range_bit, d.img_range ? d.img_range + e_b : nullptr);
             } else
 #pragma unroll
             for (int j = 0; j < NB; ++j) {

@@ -33,14 +33,20 @@ struct DenseDims {
     int chunks, kparts, cpp;                    // K / 32; split-K parts; chunks per part
     int mtiles, ntiles;
     float wscale, oscale;                       // fp16 pairs (NP = 2): weights x wscale before the split; partials x oscale (powers of two)
+    const int* live = nullptr;                  // recompute pass (vpk_cnn_set_range_policy): the device count of images, N its upper bound
 };
 
 // X f32 [N][K] -> B fragments [column tile][chunk][piece][step][column block][lane][8] (columns >= N: zeros): NP = 3 bf16 triples,
 // NP = 2 fp16 pairs of ascale x (cnn_conv_pieces.hpp)
 template <int NP>
 __global__ __launch_bounds__(256) void dense_split_kernel(const float* __restrict__ x, unsigned short* __restrict__ out, int N, int K,
-                                                          int chunks, float ascale, unsigned* __restrict__ range_word, unsigned range_bit) {
+                                                          int chunks, float ascale, unsigned* __restrict__ range_word, unsigned range_bit,
+                                                          unsigned* __restrict__ img_range, const int* __restrict__ live) {
     const int c = blockIdx.x, nt = blockIdx.y;
+    if (live) {                                  // recompute pass: column tiles of the device count's images; columns beyond it are zeros
+        N = __builtin_amdgcn_readfirstlane(*live);
+        if (nt * DP_BN >= N) return;
+    }
     const int j = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int n = nt * DP_BN + 32 * j + (lane & 31), h = lane >> 5;
     float v[16];
@@ -62,7 +68,15 @@ __global__ __launch_bounds__(256) void dense_split_kernel(const float* __restric
         if (NP == 3) split3(v[e], p[0][e], p[1][e], p[2][e]);
         else split2h_guard(v[e] * ascale, p[0][e], p[1][e], bad);
     }
-    if (NP == 2) range_report(bad, range_word, range_bit);
+    if (NP == 2) {
+        // a wave holds 32 images (columns), each in lanes l and l + 32: ONE ballot; when it is not zero, the handle's word as before and
+        // one atomic per flagged image, from the lower lane of its pair
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(bad);
+        if (m != 0ull) {
+            if (lane == 0) atomicOr(range_word, range_bit);
+            if (img_range && lane < 32 && (((m | (m >> 32)) >> lane) & 1ull)) atomicOr(img_range + n, range_bit);
+        }
+    }
     u32x4* dst = reinterpret_cast<u32x4*>(out + ((size_t)nt * chunks + c) * (DP_STAGE<NP> / 2));
 #pragma unroll
     for (int q = 0; q < NP; ++q)
@@ -244,6 +258,11 @@ __global__ __launch_bounds__(DP_THREADS, 2) void dense_pieces_kernel(DenseDims d
     const unsigned lds0 = lds_addr(dp_lds);
     typedef __attribute__((address_space(3))) const bf16x8 lds_cbf8;
     int parity = 0;
+    if (d.live) {                                        // recompute pass: the column tiles of the device count's images
+        d.N = __builtin_amdgcn_readfirstlane(*d.live);
+        d.ntiles = (d.N + DP_BN - 1) / DP_BN;
+        total_items = d.mtiles * d.ntiles * d.kparts;
+    }
     for (int item = blockIdx.x; item < total_items;) {
         int nx = 0;
         if (tid == 0)

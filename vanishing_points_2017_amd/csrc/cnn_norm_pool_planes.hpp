@@ -22,7 +22,8 @@ template <int TPH>
 __global__ __launch_bounds__(256) void lrn5_pool3s2_planes_kernel(const float* __restrict__ in, float* __restrict__ out_f32,
                                                                   unsigned short* __restrict__ out_planes, int C, int H, int W, int PH,
                                                                   int PW, float alpha, int PHp, int PWp, int opad, int cgroups, float ascale,
-                                                                  unsigned* __restrict__ range_word, unsigned range_bit) {
+                                                                  unsigned* __restrict__ range_word, unsigned range_bit,
+                                                                  unsigned* __restrict__ img_range) {
     // PMAX: floats per normalised plane in LDS.  832 (>= TR x (W + 1) = 13 x 62 at this shape; it was 1024 = the thread slots) makes the
     // double-buffered batch 53 KB, so that THREE workgroups share a CU instead of two (round 6)
     // (four per CU with tiles of four pooled rows, 37 KB: no faster, 0.126 against 0.124 ms)
@@ -124,7 +125,7 @@ __global__ __launch_bounds__(256) void lrn5_pool3s2_planes_kernel(const float* _
         }
         buf ^= 1;
     }
-    if (out_planes) range_report(bad, range_word, range_bit);
+    if (out_planes) range_report(bad, range_word, range_bit, img_range ? img_range + b : nullptr);
 }
 
 }  // namespace

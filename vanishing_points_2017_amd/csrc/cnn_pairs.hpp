@@ -25,8 +25,13 @@ __device__ __forceinline__ void split2h_guard(float x, unsigned short& h0, unsig
     bad |= !(__builtin_fabsf(x) < CP_H_MAX);
     split2h(__builtin_fminf(__builtin_fmaxf(x, -CP_H_MAX), CP_H_MAX), h0, h1);
 }
-__device__ __forceinline__ void range_report(bool bad, unsigned* __restrict__ range_word, unsigned bit) {
-    if (__builtin_amdgcn_ballot_w64(bad) != 0ull && (threadIdx.x & 63) == 0) atomicOr(range_word, bit);
+// img_word: the word of the image the wave's values belong to in the forward's per-image flags (vpk_cnn_image_range_flags), or null.
+// The per-image OR is inside the branch that is only taken when something was clamped: nothing is added to a clean epilogue.
+__device__ __forceinline__ void range_report(bool bad, unsigned* __restrict__ range_word, unsigned bit, unsigned* img_word = nullptr) {
+    if (__builtin_amdgcn_ballot_w64(bad) != 0ull && (threadIdx.x & 63) == 0) {
+        atomicOr(range_word, bit);
+        if (img_word) atomicOr(img_word, bit);
+    }
 }
 
 }  // namespace

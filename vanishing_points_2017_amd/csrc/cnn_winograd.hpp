@@ -77,7 +77,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void conv3x3_winograd_kernel(WinoDim
                                                                          const float* __restrict__ U,
                                                                          const float* __restrict__ bias,
                                                                          float* __restrict__ out, int* __restrict__ tile_counter,
-                                                                         int total_tiles) {
+                                                                         int total_tiles, const int* __restrict__ live) {
     __shared__ __attribute__((aligned(16))) float Us[2][16][WG_KC][WG_OCB];     // 64 KB
     __shared__ __attribute__((aligned(16))) float Vs[2][16][WG_KC][WG_TB];      // 64 KB
     float (*Ms)[16][WG_TB] = reinterpret_cast<float (*)[16][WG_TB]>(&Us[0][0][0][0]);   // epilogue: [p][row][tile] over Us
@@ -85,6 +85,10 @@ __global__ __launch_bounds__(WG_THREADS, 1) void conv3x3_winograd_kernel(WinoDim
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int khalf = lane >> 5, l31 = lane & 31;
     const unsigned us_base = lds_addr(&Us[0][0][0][0]);
+    if (live) {                                         // recompute pass (vpk_cnn_set_range_policy): the device count's images only
+        d.tiles = __builtin_amdgcn_readfirstlane(*live) * WG_TILES_PER_IMAGE;
+        total_tiles = d.groups * d.ocblocks * ((d.tiles + WG_TB - 1) / WG_TB);
+    }
     const int nblocks = (d.tiles + WG_TB - 1) / WG_TB;
     // persistent workgroups over a dynamic tile queue (the first gridDim.x tiles are static): beside another stream's kernel
     // that holds CUs (the EM), a static deal leaves the workgroups of the busy XCDs behind

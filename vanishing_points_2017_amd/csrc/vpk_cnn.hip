@@ -101,7 +101,8 @@ __global__ __launch_bounds__(CONV_THREADS, WPC) void conv_gemm_dma_kernel(ConvDi
                                                                      const float* __restrict__ bias,
                                                                      const unsigned* __restrict__ ktab,
                                                                      float* __restrict__ out, int stride,
-                                                                     int* __restrict__ tile_counter, int total_tiles) {
+                                                                     int* __restrict__ tile_counter, int total_tiles,
+                                                                     const int* __restrict__ live) {
     constexpr int BM = WAVES_M * TM * 32;
     constexpr int BN = WAVES_N * TN * 32;
     static_assert(BN == 128, "the B-tile loader assumes 128 columns");
@@ -123,6 +124,11 @@ __global__ __launch_bounds__(CONV_THREADS, WPC) void conv_gemm_dma_kernel(ConvDi
     // The next index is fetched at the start of a tile and published through LDS, so its latency is hidden.
     __shared__ int s_next[2];
     int parity = 0;
+    if (!C1FUSE && live) {                              // recompute pass (vpk_cnn_set_range_policy): the device count's images only
+        d.B = __builtin_amdgcn_readfirstlane(*live);
+        d.N = d.B * d.OH * d.OW;
+        total_tiles = d.groups * d.ksplit * ((d.N + BN - 1) / BN) * (d.Mp / BM);
+    }
     for (int tile = blockIdx.x; tile < total_tiles;) {
     int nx = 0;
     if (tid == 0)    // ONE lane; the oldest outstanding vector-memory op of wave 0: complete at the first wait_stage
@@ -708,7 +714,9 @@ __global__ void prep_input_kernel(const unsigned char* __restrict__ sphere, cons
 
 // sum the split-K partials, add bias, activation: act 0 = none, 1 = ReLU, 2 = sigmoid
 __global__ void splitk_reduce_kernel(const float* __restrict__ part, const float* __restrict__ bias, int ksplit,
-                                     long long N, int OC, int act, float* __restrict__ out, float* __restrict__ pre) {
+                                     long long N, int OC, int act, float* __restrict__ out, float* __restrict__ pre,
+                                     const int* __restrict__ live) {
+    if (live) N = *live;                                       // recompute pass: the partials of the device count's images
     long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= N * OC) return;
     int m = (int)(idx % OC);
@@ -745,11 +753,12 @@ constexpr int LRN_CCH = 16;   // channels per workgroup (plus a 2-channel halo o
 template <int TPH, int CB>
 __global__ __launch_bounds__(256) void lrn5_pool3s2_stream_kernel(const float* __restrict__ in, float* __restrict__ out, int C,
                                                                   int H, int W, int PH, int PW, float alpha, float beta,
-                                                                  int PHp, int PWp, int opad, int cgroups) {
+                                                                  int PHp, int PWp, int opad, int cgroups, const int* __restrict__ live) {
     constexpr int TR = 2 * TPH + 1, SLOTS = 4, PMAX = 256 * SLOTS;
     __shared__ float plane[2][CB][PMAX];
     const int tiles_h = (PH + TPH - 1) / TPH;
     const int th = blockIdx.x % tiles_h, cgi = (blockIdx.x / tiles_h) % cgroups, b = blockIdx.x / (tiles_h * cgroups);
+    if (live && b >= *live) return;                      // (recompute pass: slots beyond the device count)
     const int cper = C / cgroups, c_lo = cgi * cper, c_hi = c_lo + cper;      // this workgroup's channels [c_lo, c_hi)
     const int ph0 = th * TPH, h0 = 2 * ph0;
     const int HW = H * W, npix = TR * W;                 // npix <= PMAX (checked by the host)
@@ -920,10 +929,12 @@ __global__ __launch_bounds__(256) void lrn5_pool3s2_tiled_kernel(const float* __
 // of neighbouring outputs overlap, and one thread per output reading its nine values from HBM ran at 2.3 TB/s), then
 // every thread takes pooled outputs out of LDS; stores are contiguous.  Maxima: order-free, same values.
 template <int PL>
-__global__ __launch_bounds__(256) void pool5_kernel(const float* __restrict__ in, float* __restrict__ out, long long planes) {
+__global__ __launch_bounds__(256) void pool5_kernel(const float* __restrict__ in, float* __restrict__ out, long long planes,
+                                                    const int* __restrict__ live) {
     constexpr int H = 30, W = 30, P = 15, HW = H * W, PP = P * P;
     __shared__ __attribute__((aligned(16))) float s[PL * HW];
     const long long p0 = (long long)blockIdx.x * PL;
+    if (live && p0 >= (long long)*live * 256) return;    // (recompute pass: the 256 planes of each image beyond the device count)
     const int np = planes - p0 < PL ? (int)(planes - p0) : PL;
     const f32x4* src = reinterpret_cast<const f32x4*>(in + p0 * HW);
     for (int q = threadIdx.x; q < np * HW / 4; q += 256) reinterpret_cast<f32x4*>(s)[q] = src[q];
@@ -999,7 +1010,15 @@ struct vpk_cnn_state {
     unsigned short* xfrag = nullptr;   // fc6's input as bf16 B fragments (dense_split_kernel), grown on demand
     size_t xfrag_bytes = 0;
     unsigned* range_word = nullptr;    // fp16 pairs: bit li set when a scaled INPUT value of layer li reached fp16's range (split2h_guard);
-                                       // sticky until vpk_cnn_range_flags reads and clears it
+                                       // sticky until vpk_cnn_range_flags reads and clears it.  range_word[1]: where the pair pass
+                                       // reports under RECOMPUTE_EXACT (its flagged images are recomputed, so nothing reaches word 0)
+    // range policy (vpk_cnn_set_range_policy): 0 = RAISE, 1 = RECOMPUTE_EXACT
+    int range_policy = 0;
+    unsigned* img_range = nullptr;     // the last vpk_cnn_forward's per-image bits (image b at [b]), grown on demand
+    size_t img_range_bytes = 0;
+    int img_range_batch = 0;           // its batch (0: no forward yet)
+    int* rc_list = nullptr;            // recompute pass: [0] = device count of flagged images of the chunk, [1 ..] their indices in order
+    unsigned long long* rc_total = nullptr;   // images recomputed since vpk_cnn_recomputed last read it
     // optional per-layer timing (HIP events on the handle's stream)
     int split_variant = 0;   // (development) tiling of the split GEMM
     int precision = 0;       // vpk_cnn_set_precision: 0 = native f32 MFMA, 1 = conv2..5 on the bf16 matrix cores (3-piece split)
@@ -1036,6 +1055,9 @@ void vpk_cnn_free(vpk_handle* h) {
     if (h->cnn->act) (void)hipFree(h->cnn->act);
     if (h->cnn->xfrag) (void)hipFree(h->cnn->xfrag);
     if (h->cnn->range_word) (void)hipFree(h->cnn->range_word);
+    if (h->cnn->img_range) (void)hipFree(h->cnn->img_range);
+    if (h->cnn->rc_list) (void)hipFree(h->cnn->rc_list);
+    if (h->cnn->rc_total) (void)hipFree(h->cnn->rc_total);
     if (h->cnn->ev_ready)
         for (auto& set : h->cnn->ev)
             for (auto& e : set) (void)hipEventDestroy(e);
@@ -1074,6 +1096,7 @@ constexpr size_t splitk_partials_per_image() {          // the partials region: 
 // written at allocation time stay valid.  Nothing is reused between layers (17.6 MB per image; 288 GB
 // of HBM3E makes ping-pong buffers unnecessary, and the borders must not be overwritten).
 enum Region { R_IN, R_CONV1, R_POOL1, R_CONV2, R_POOL2, R_CONV3, R_CONV4, R_CONV5, R_POOL5, R_FCA, R_FCB, R_PART, R_SPLIT, R_SPLIT4, R_SPLIT5, R_P6_2, R_P6_3, R_P6_5, R_COUNT };
+constexpr int MAX_CHUNK = 4096;     // images per run_forward at most (32-bit positions inside one launch)
 constexpr size_t CTR_FLOATS = 64;   // tile-queue counters of the 8 GEMM launches, behind the regions
 constexpr size_t GUARD_FLOATS = 64;  // between the last region and the counters: conv_pieces_kernel's patch DMA reads up to 8 words (128
                                      // bytes) past a plane's last row (columns that are never stored); for the last plane of the last
@@ -1121,17 +1144,28 @@ __global__ void unpad_kernel(const float* __restrict__ in, float* __restrict__ o
 
 template <typename KernelT>
 void launch_dma(vpk_handle* h, KernelT kernel, const ConvDims& d, int BM, const float* in, const Layer& l, float* out,
-                int stride, int* counter, int wpc = 3) {
+                int stride, int* counter, int wpc = 3, const int* live = nullptr) {
     long long ntiles = (d.N + 127) / 128;
     long long total = (long long)d.groups * d.ksplit * ntiles * (d.Mp / BM);
     long long blocks = std::min<long long>(total, (long long)wpc * h->num_cu);   // wpc workgroups fit a CU (LDS, registers)
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(CONV_THREADS), 0, h->stream, d, in, l.wp, l.bias, l.ktab,
-                       out, stride, counter, (int)total);
+                       out, stride, counter, (int)total, live);
 }
 
-int run_forward(vpk_handle* h, const uint8_t* sphere, int batch, float* out, int tap, float* tap_out) {
+// Where a forward reports what its fp16-pair writers clamp, and which images it runs (vpk_cnn_set_range_policy).
+struct FwdCtl {
+    unsigned* range_word;       // the sticky word the pair writers OR the consuming layer's bit into
+    unsigned* img_range;        // the same bits per image of this launch (image b at img_range[b]); null: not kept
+    const int* live;            // recompute pass: the device count of images -- `batch` is then only its upper bound; null: batch
+};
+
+int run_forward(vpk_handle* h, const uint8_t* sphere, int batch, float* out, int tap, float* tap_out, const FwdCtl& fc) {
     vpk_cnn_state* S = h->cnn;
     hipStream_t st = h->stream;
+    // the kernels that honour a device count are those of the exact configuration with the default conv1
+    if (fc.live && !(S->precision == 0 && S->algorithm == 2 && S->fuse_conv1 == 3 && tap < 0 && !S->profiling))
+        return vpk_fail(h, VPK_ERR_STATE, "run_forward: a device-counted pass runs algorithm 2 with the default conv1, untapped");
+    const int* live = fc.live;
     if (batch > S->act_batch) {     // grow the arena; all borders (and everything else) start as zeros
         const size_t need = ((size_t)batch * arena_floats_per_image() + GUARD_FLOATS + CTR_FLOATS) * sizeof(float);
         int rc = vpk_reserve(h, (void**)&S->act, &S->act_bytes, need, "hipMalloc(CNN activations)");
@@ -1200,11 +1234,11 @@ int run_forward(vpk_handle* h, const uint8_t* sphere, int batch, float* out, int
             if (S->fuse_conv1 == 4)
                 hipLaunchKernelGGL(conv1_pieces_kernel<2>, dim3((unsigned)std::min(total, h->num_cu)), dim3(C1B_THREADS), 0, st, sphere,
                                    S->L[0].c1half, S->L[0].c1map, R[R_POOL1], 65, 65, 2, batch, group, 1.f / S->L[0].c1scale, ctr + 0, total,
-                                   c2planes, S->L[1].ascale, S->range_word);
+                                   c2planes, S->L[1].ascale, fc.range_word, fc.img_range, live);
             else
                 hipLaunchKernelGGL(conv1_pieces_kernel<3>, dim3((unsigned)std::min(total, h->num_cu)), dim3(C1B_THREADS), 0, st, sphere,
                                    S->L[0].c1frag, S->L[0].c1map, R[R_POOL1], 65, 65, 2, batch, group, 1.f, ctr + 0, total,
-                                   c2planes, S->L[1].ascale, S->range_word);
+                                   c2planes, S->L[1].ascale, fc.range_word, fc.img_range, live);
         } else if (S->fuse_conv1 == 2) {                  // the implicit-GEMM kernel with the fused epilogue (kept for comparison)
             ConvDims df = dims(0);
             df.N = batch * C1_TR * C1_TC * 128;           // one 128-column tile per patch
@@ -1262,7 +1296,7 @@ int run_forward(vpk_handle* h, const uint8_t* sphere, int batch, float* out, int
         wd.tiles = batch * WG_TILES_PER_IMAGE;
         const int total = wd.groups * wd.ocblocks * ((wd.tiles + WG_TB - 1) / WG_TB);
         hipLaunchKernelGGL(conv3x3_winograd_kernel, dim3((unsigned)std::min(total, h->num_cu)), dim3(WG_THREADS), 0, st, wd, src,
-                           S->L[li].wino, S->L[li].bias, dst, ctr + li, total);
+                           S->L[li].wino, S->L[li].bias, dst, ctr + li, total, live);
     };
     const bool wino = S->precision == 0 && S->algorithm >= 1;      // Winograd for the layers that are not on pieces
     const bool pieces = S->precision == 0 && S->algorithm >= 2;     // conv2 (mode 3, measurements: conv3 and conv5 too) on exact bf16 pieces
@@ -1270,16 +1304,16 @@ int run_forward(vpk_handle* h, const uint8_t* sphere, int batch, float* out, int
     const bool halves = S->precision == 0 && S->algorithm == 4;     // conv2..5 on scaled fp16 pairs (three products per step)
     auto to_p6 = [&](const float* src, unsigned short* dst, int C, int Hp, int Wp, int li) {     // li: the layer that reads the planes
         if (halves) hipLaunchKernelGGL(to_planes_kernel<2>, dim3((unsigned)Hp, (unsigned)(C / 16), (unsigned)batch), dim3(256), 0, st, src, dst, C, Hp, Wp,
-                                       S->L[li].ascale, S->range_word, 1u << li);
+                                       S->L[li].ascale, fc.range_word, 1u << li, fc.img_range, live);
         else hipLaunchKernelGGL(to_planes_kernel<3>, dim3((unsigned)Hp, (unsigned)(C / 16), (unsigned)batch), dim3(256), 0, st, src, dst, C, Hp, Wp, 1.f,
-                                S->range_word, 0u);
+                                fc.range_word, 0u, nullptr, live);
     };
     // (planes_next: the next layer's input planes, written by the epilogue instead of the f32 blob -- fp16 pairs only)
     auto conv_pieces = [&](int li, const unsigned short* src6, float* dst, unsigned short* planes_next = nullptr) {
         PieceDims pd = halves ? S->L[li].pdh : S->L[li].pd;
         pd.B = batch;
         if (planes_next) { const PieceDims& nx = S->L[li + 1].pdh; pd.o_cgtot = nx.CGtot; pd.o_Hp = nx.Hp; pd.o_Wp = nx.Wp; pd.o_pad = 1; pd.o_ascale = S->L[li + 1].ascale; }
-        pd.range_word = S->range_word; pd.range_bit = 1u << (li + 1);
+        pd.range_word = fc.range_word; pd.range_bit = 1u << (li + 1); pd.img_range = fc.img_range; pd.live = live;
         if (halves) pd.oscale = 1.f / (S->L[li].hscale * S->L[li].ascale);
         constexpr int nb = 4;                                               // rows of a wave's four 32 x 32 blocks
         const int tile_rows = halves && li == 3 ? 2 * nb : nb;              // (conv4 on pairs: 64 channels x 8 rows per tile)
@@ -1322,10 +1356,10 @@ int run_forward(vpk_handle* h, const uint8_t* sphere, int batch, float* out, int
     if (S->precision == 0 && S->algorithm == 4)
         hipLaunchKernelGGL((lrn5_pool3s2_planes_kernel<6>), dim3((unsigned)(batch * 5 * 8)), dim3(256), 0, st, R[R_CONV2], R[R_POOL2],
                            hand2 ? reinterpret_cast<unsigned short*>(R[R_P6_3]) : nullptr, 256, 61, 61, 30, 30, 1e-4f, 32, 32, 1, 8,
-                           S->L[2].ascale, S->range_word, 1u << 2);
+                           S->L[2].ascale, fc.range_word, 1u << 2, fc.img_range);
     else
     hipLaunchKernelGGL((lrn5_pool3s2_stream_kernel<6, 4>), dim3((unsigned)(batch * 5 * 8)), dim3(256), 0, st, R[R_CONV2], R[R_POOL2],
-                       256, 61, 61, 30, 30, 1e-4f, 0.75f, 32, 32, 1, 8);
+                       256, 61, 61, 30, 30, 1e-4f, 0.75f, 32, 32, 1, 8, live);
     mark();
     mark();
     tapunpad(3, R[R_POOL2], 256, 30, 30, 1);
@@ -1357,7 +1391,7 @@ int run_forward(vpk_handle* h, const uint8_t* sphere, int batch, float* out, int
     mark();
     if ((rc = tapcopy(6, R[R_CONV5], A_CONV5))) return rc;
     hipLaunchKernelGGL((pool5_kernel<8>), dim3((unsigned)(((long long)batch * 256 + 7) / 8)), dim3(256), 0, st, R[R_CONV5], R[R_POOL5],
-                       (long long)batch * 256);
+                       (long long)batch * 256, live);
     mark();
     if ((rc = tapcopy(7, R[R_POOL5], A_POOL5))) return rc;
     // fc6 / fc7 / fc8: split-K partials + deterministic reduction (+ bias, ReLU / sigmoid)
@@ -1374,13 +1408,14 @@ int run_forward(vpk_handle* h, const uint8_t* sphere, int batch, float* out, int
             dd.cpp = dd.chunks / dd.kparts;
             dd.mtiles = (d.OC + DP_BM - 1) / DP_BM; dd.ntiles = (batch + DP_BN - 1) / DP_BN;
             dd.wscale = halves ? S->L[li].hscale : 1.f;
+            dd.live = live;
             dd.oscale = halves ? 1.f / (S->L[li].hscale * S->L[li].ascale) : 1.f;
             const size_t need = (size_t)dd.ntiles * (TOPO[5].IC / DP_CHUNK) * DP_STAGE<3>;
             if ((rc = vpk_reserve(h, (void**)&S->xfrag, &S->xfrag_bytes, need, "hipMalloc(dense input fragments)"))) return rc;
             const int total = dd.mtiles * dd.ntiles * dd.kparts;
             if (halves) {
                 hipLaunchKernelGGL(dense_split_kernel<2>, dim3((unsigned)dd.chunks, (unsigned)dd.ntiles), dim3(256), 0, st, fc_in, S->xfrag, batch,
-                                   d.K, dd.chunks, S->L[li].ascale, S->range_word, 1u << li);
+                                   d.K, dd.chunks, S->L[li].ascale, fc.range_word, 1u << li, fc.img_range, nullptr);
                 if (S->dense_presplit)
                     hipLaunchKernelGGL(dense_pairs_kernel, dim3((unsigned)std::min(total, h->num_cu)), dim3(DP_THREADS), 0, st, dd, S->L[li].wpair,
                                        S->xfrag, R[R_PART], ctr + li, total);
@@ -1389,18 +1424,18 @@ int run_forward(vpk_handle* h, const uint8_t* sphere, int batch, float* out, int
                                    S->xfrag, R[R_PART], ctr + li, total);
             } else {
                 hipLaunchKernelGGL(dense_split_kernel<3>, dim3((unsigned)dd.chunks, (unsigned)dd.ntiles), dim3(256), 0, st, fc_in, S->xfrag, batch,
-                                   d.K, dd.chunks, 1.f, S->range_word, 0u);
+                                   d.K, dd.chunks, 1.f, fc.range_word, 0u, nullptr, live);
                 hipLaunchKernelGGL(dense_pieces_kernel<3>, dim3((unsigned)std::min(total, h->num_cu)), dim3(DP_THREADS), 0, st, dd, S->L[li].wraw,
                                    S->xfrag, R[R_PART], ctr + li, total);
             }
             d.ksplit = dd.kparts;
         } else
-        launch_dma(h, conv_gemm_dma_kernel<2, 2, 2, 2, true>, d, 128, fc_in, S->L[li], R[R_PART], 1, ctr + li);
+        launch_dma(h, conv_gemm_dma_kernel<2, 2, 2, 2, true>, d, 128, fc_in, S->L[li], R[R_PART], 1, ctr + li, 3, live);
         const long long tot = (long long)d.N * d.OC;
         float* dst = li == 7 ? out : fc_out;
         float* pre = (li == 7 && tap == 10) ? tap_out : nullptr;
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3(ew_blocks(tot)), dim3(256), 0, st, R[R_PART], S->L[li].bias, d.ksplit,
-                           d.N, d.OC, li == 7 ? 2 : 1, dst, pre);
+                           d.N, d.OC, li == 7 ? 2 : 1, dst, pre, live);
         mark();
         if (li == 5 && (rc = tapcopy(8, fc_out, A_FC6))) return rc;
         if (li == 6 && (rc = tapcopy(9, fc_out, A_FC7))) return rc;
@@ -1500,7 +1535,7 @@ int blob_maxima(vpk_handle* h, const uint8_t* d_imgs, int n, float mx[CAL_N]) {
     for (int b0 = 0; b0 < n && rc == VPK_OK; b0 += chunk) {
         const int nb = n - b0 < chunk ? n - b0 : chunk;
         for (int i = 0; i < CAL_N && rc == VPK_OK; ++i) {
-            rc = run_forward(h, d_imgs + (size_t)b0 * 500 * 500, nb, d_out, CAL_TAP[i], d_tap);
+            rc = run_forward(h, d_imgs + (size_t)b0 * 500 * 500, nb, d_out, CAL_TAP[i], d_tap, FwdCtl{S->range_word, nullptr, nullptr});
             if (rc == VPK_OK) hipLaunchKernelGGL(absmax_kernel, dim3(256), dim3(256), 0, h->stream, d_tap, (size_t)nb * CAL_SIZE[i], d_max + i);
         }
     }
@@ -1537,6 +1572,85 @@ int calibrate(vpk_handle* h, const uint8_t* rasters, int n) {
         if (!std::isfinite(mx[i]))
             return vpk_fail(h, VPK_ERR_RANGE, "vpk_cnn_calibrate: a blob of the calibration forward is not finite (weights?)");
     for (int i = 0; i < CAL_N; ++i) S->L[CAL_LAYER[i]].ascale = scale_for_maximum(mx[i]);
+    return VPK_OK;
+}
+
+
+// ---- range policy RECOMPUTE_EXACT (vpk_cnn_set_range_policy) ----------------------------------------------------------------------
+// After the pair pass of a chunk, on the handle's stream and with no host wait:
+//   1. range_compact_kernel: the chunk's per-image words -> list[0] = count of flagged images, list[1 ..] their indices in order;
+//   2. range_gather_kernel: their rasters -> slots 0 .. count - 1 of the arena's fp32-input region (R_IN: the exact configuration's conv1
+//      reads rasters itself and never touches it);
+//   3. the forward of vpk_cnn_set_algorithm(2) with the default conv1 over those slots.  The host does not know the count: every kernel
+//      is launched for the whole chunk and reads list[0] (FwdCtl::live) -- the persistent ones size their tile queue by it, the others
+//      exit at once for slots at or beyond it; with nothing flagged every launch is empty.  It is the same computation as that forward
+//      run on the flagged rasters as one batch, so the maps are the same bits;
+//   4. range_scatter_kernel: the maps (in fc6's output region, dead once fc7 has read it) -> their rows of `out`.
+// The pair pass's activations are dead by then: the pass reuses the arena, no extra workspace.
+__global__ __launch_bounds__(1024) void range_compact_kernel(const unsigned* __restrict__ img_range, int nb, int* __restrict__ list,
+                                                             unsigned long long* __restrict__ recomputed) {
+    __shared__ int wsum[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int base = 0;
+    for (int i0 = 0; i0 < nb; i0 += 1024) {
+        const int i = i0 + tid;
+        const bool f = i < nb && img_range[i] != 0u;
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(f);
+        if (lane == 0) wsum[wave] = __popcll(m);
+        __syncthreads();
+        int off = base, all = 0;
+        for (int w = 0; w < 16; ++w) {
+            off += w < wave ? wsum[w] : 0;
+            all += wsum[w];
+        }
+        if (f) list[1 + off + __popcll(m & ((1ull << lane) - 1ull))] = i;
+        base += all;
+        __syncthreads();                                 // (wsum is rewritten by the next round)
+    }
+    if (tid == 0) {
+        list[0] = base;
+        if (base) atomicAdd(recomputed, (unsigned long long)base);
+    }
+}
+
+// slot s < list[0]: the raster of image list[1 + s] (250 000 bytes = 62 500 words: the rasters are 4-byte aligned; 8 workgroups per slot)
+__global__ __launch_bounds__(256) void range_gather_kernel(const uint8_t* __restrict__ sphere, const int* __restrict__ list,
+                                                           uint8_t* __restrict__ slots) {
+    const int s = blockIdx.y;
+    if (s >= list[0]) return;
+    const unsigned* src = reinterpret_cast<const unsigned*>(sphere + (size_t)list[1 + s] * 250000);
+    unsigned* dst = reinterpret_cast<unsigned*>(slots + (size_t)s * 250000);
+    for (int q = blockIdx.x * 256 + threadIdx.x; q < 250000 / 4; q += gridDim.x * 256) dst[q] = src[q];
+}
+
+// slot s < list[0]: its 400-float map -> row list[1 + s] of out
+__global__ __launch_bounds__(128) void range_scatter_kernel(const float* __restrict__ maps, const int* __restrict__ list,
+                                                            float* __restrict__ out) {
+    const int s = blockIdx.x;
+    if (s >= list[0]) return;
+    const float* src = maps + (size_t)s * 400;
+    float* dst = out + (size_t)list[1 + s] * 400;
+    for (int q = threadIdx.x; q < 400; q += 128) dst[q] = src[q];
+}
+
+// the exact recompute of a chunk's flagged images (nb <= MAX_CHUNK; the arena holds nb images: the pair pass ran just before)
+int recompute_flagged(vpk_handle* h, const uint8_t* sphere, int nb, float* out, const unsigned* img_range) {
+    vpk_cnn_state* S = h->cnn;
+    hipStream_t st = h->stream;
+    size_t off_fca = 0;
+    for (int i = 0; i < R_FCA; ++i) off_fca += (size_t)S->act_batch * REGION_FLOATS[i];
+    uint8_t* slots = reinterpret_cast<uint8_t*>(S->act);                  // R_IN (region 0): 4 bytes per raster byte of room
+    float* maps = S->act + off_fca;                                       // R_FCA: 4096 floats per image of room
+    hipLaunchKernelGGL(range_compact_kernel, dim3(1), dim3(1024), 0, st, img_range, nb, S->rc_list, S->rc_total);
+    hipLaunchKernelGGL(range_gather_kernel, dim3(8, (unsigned)nb), dim3(256), 0, st, sphere, S->rc_list, slots);
+    const int keep_alg = S->algorithm, keep_fuse = S->fuse_conv1;
+    const bool keep_prof = S->profiling;
+    S->algorithm = 2; S->fuse_conv1 = 3; S->profiling = false;
+    const int rc = run_forward(h, slots, nb, maps, -1, nullptr, FwdCtl{S->range_word + 1, nullptr, S->rc_list});
+    S->algorithm = keep_alg; S->fuse_conv1 = keep_fuse; S->profiling = keep_prof;
+    if (rc) return rc;
+    hipLaunchKernelGGL(range_scatter_kernel, dim3((unsigned)nb), dim3(128), 0, st, maps, S->rc_list, out);
+    VPK_HIP(h, hipGetLastError());
     return VPK_OK;
 }
 
@@ -1800,6 +1914,9 @@ int vpk_cnn_load(vpk_handle* h, const float* const blobs[16], const float* mean)
     }
     VPK_HIP(h, hipMalloc((void**)&S->range_word, 256));
     VPK_HIP(h, hipMemset(S->range_word, 0, 256));
+    VPK_HIP(h, hipMalloc((void**)&S->rc_list, (1 + MAX_CHUNK) * sizeof(int)));
+    VPK_HIP(h, hipMalloc((void**)&S->rc_total, sizeof(unsigned long long)));
+    VPK_HIP(h, hipMemset(S->rc_total, 0, sizeof(unsigned long long)));
     // the activation scales of the fp16-pair layers: six tapped forwards of the built-in calibration rasters on the f32 direct
     // kernels (calibrate()); their arena (batch 3) is released again so that the first real forward allocates once, for its batch
     const int rc = calibrate(h, nullptr, 0);
@@ -1855,7 +1972,11 @@ int vpk_cnn_range_flags(vpk_handle* h, uint32_t* flags_out) {
     return vpk_fail(h, VPK_ERR_RANGE, msg.c_str());
 }
 
-int vpk_cnn_forward_tap(vpk_handle* h, const uint8_t* sphere, int batch, float* out, int tap, float* tap_out) {
+}  // extern "C"
+
+namespace {
+// policy: vpk_cnn_forward (per-image flags kept, the range policy applied); !policy: vpk_cnn_forward_tap, as before the policy existed
+int forward_chunks(vpk_handle* h, const uint8_t* sphere, int batch, float* out, int tap, float* tap_out, bool policy) {
     if (!h || !sphere || !out || batch < 1) return vpk_fail(h, VPK_ERR_ARG, "vpk_cnn_forward: bad argument");
     if (((size_t)sphere & 3) != 0)      // conv1's loader reads four horizontally adjacent pixels as one 4-byte word
         return vpk_fail(h, VPK_ERR_ARG, "vpk_cnn_forward: the rasters must be 4-byte aligned");
@@ -1864,21 +1985,72 @@ int vpk_cnn_forward_tap(vpk_handle* h, const uint8_t* sphere, int batch, float* 
     // activations for the whole batch stay in HBM; chunk only if they would exceed a third of it
     // (and at 4096 images: positions and dense-layer byte offsets are 32-bit inside one launch)
     const size_t per_img = arena_floats_per_image() * sizeof(float);
-    int chunk = (int)std::min<size_t>(std::min<size_t>((size_t)batch, 4096),
+    int chunk = (int)std::min<size_t>(std::min<size_t>((size_t)batch, MAX_CHUNK),
                                       std::max<size_t>(1, (h->total_mem / 3) / per_img));
     static const size_t tap_size[11] = {A_CONV1, A_POOL1, A_CONV2, A_POOL2, A_CONV3, A_CONV4, A_CONV5, A_POOL5,
                                         A_FC6, A_FC7, A_FC8};
+    vpk_cnn_state* S = h->cnn;
+    if (policy) {
+        int rc = vpk_reserve(h, (void**)&S->img_range, &S->img_range_bytes, (size_t)batch * sizeof(unsigned), "hipMalloc(per-image range flags)");
+        if (rc) return rc;
+        VPK_HIP(h, hipMemsetAsync(S->img_range, 0, (size_t)batch * sizeof(unsigned), h->stream));
+        S->img_range_batch = batch;
+    }
+    // only the fp16-pair configuration can clamp: the recompute pass is not even launched for the others
+    const bool recompute = policy && S->range_policy == 1 && S->precision == 0 && S->algorithm == 4;
     for (int b0 = 0; b0 < batch; b0 += chunk) {
         int nb = std::min(chunk, batch - b0);
         float* tp = (tap_out && tap >= 0 && tap <= 10) ? tap_out + (size_t)b0 * tap_size[tap] : nullptr;
-        int rc = run_forward(h, sphere + (size_t)b0 * 500 * 500, nb, out + (size_t)b0 * 400, tp ? tap : -1, tp);
+        const uint8_t* sp = sphere + (size_t)b0 * 500 * 500;
+        float* op = out + (size_t)b0 * 400;
+        unsigned* img = policy ? S->img_range + b0 : nullptr;
+        int rc = run_forward(h, sp, nb, op, tp ? tap : -1, tp, FwdCtl{recompute ? S->range_word + 1 : S->range_word, img, nullptr});
+        if (!rc && recompute) rc = recompute_flagged(h, sp, nb, op, img);
         if (rc) return rc;
     }
     return VPK_OK;
 }
+}  // namespace
+
+extern "C" {
+
+int vpk_cnn_forward_tap(vpk_handle* h, const uint8_t* sphere, int batch, float* out, int tap, float* tap_out) {
+    return forward_chunks(h, sphere, batch, out, tap, tap_out, false);
+}
 
 int vpk_cnn_forward(vpk_handle* h, const uint8_t* sphere, int batch, float* out) {
-    return vpk_cnn_forward_tap(h, sphere, batch, out, -1, nullptr);
+    return forward_chunks(h, sphere, batch, out, -1, nullptr, true);
+}
+
+int vpk_cnn_set_range_policy(vpk_handle* h, int policy) {
+    if (!h || !h->cnn) return vpk_fail(h, VPK_ERR_STATE, "vpk_cnn_set_range_policy before vpk_cnn_load");
+    if (policy != 0 && policy != 1) return vpk_fail(h, VPK_ERR_ARG, "vpk_cnn_set_range_policy: policy must be 0 (RAISE) or 1 (RECOMPUTE_EXACT)");
+    h->cnn->range_policy = policy;
+    return VPK_OK;
+}
+
+int vpk_cnn_image_range_flags(vpk_handle* h, int batch, uint32_t* flags_out) {
+    if (!h || !flags_out || batch < 1) return vpk_fail(h, VPK_ERR_ARG, "vpk_cnn_image_range_flags: bad argument");
+    if (!h->cnn || !h->cnn->loaded) return vpk_fail(h, VPK_ERR_STATE, "vpk_cnn_image_range_flags before vpk_cnn_load");
+    if (h->cnn->img_range_batch == 0) return vpk_fail(h, VPK_ERR_STATE, "vpk_cnn_image_range_flags before any vpk_cnn_forward");
+    if (batch != h->cnn->img_range_batch)
+        return vpk_fail(h, VPK_ERR_ARG, "vpk_cnn_image_range_flags: batch differs from the last vpk_cnn_forward's");
+    VPK_HIP(h, hipSetDevice(h->device));
+    VPK_HIP(h, hipMemcpyAsync(flags_out, h->cnn->img_range, (size_t)batch * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    VPK_HIP(h, hipStreamSynchronize(h->stream));
+    return VPK_OK;
+}
+
+int vpk_cnn_recomputed(vpk_handle* h, int64_t* n_out) {
+    if (!h || !n_out) return vpk_fail(h, VPK_ERR_ARG, "vpk_cnn_recomputed: null argument");
+    if (!h->cnn || !h->cnn->loaded) return vpk_fail(h, VPK_ERR_STATE, "vpk_cnn_recomputed before vpk_cnn_load");
+    VPK_HIP(h, hipSetDevice(h->device));
+    unsigned long long n = 0;
+    VPK_HIP(h, hipMemcpyAsync(&n, h->cnn->rc_total, sizeof(n), hipMemcpyDeviceToHost, h->stream));
+    VPK_HIP(h, hipMemsetAsync(h->cnn->rc_total, 0, sizeof(n), h->stream));
+    VPK_HIP(h, hipStreamSynchronize(h->stream));
+    *n_out = (int64_t)n;
+    return VPK_OK;
 }
 
 }  // extern "C"

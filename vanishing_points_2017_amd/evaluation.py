@@ -47,9 +47,10 @@ def get_sphere_image(lines, size=250, alpha=0.1, f=1.0):
     return sphere_mapping.sphere_line_plot(lines, size, alpha=alpha, f=f, alternative=False)
 
 
-def init_caffe(model_def, model_weights, gpu_id=0, mean_file=None):
+def init_caffe(model_def, model_weights, gpu_id=0, mean_file=None, range_policy="raise"):
     """evaluation.py:17-22 -> a cnn.Net on GPU gpu_id.  The mean blob is fused into conv1's load, so
-    it is bound here (mean_file) or on the first caffe_forward(net, image, mean_arr) call."""
+    it is bound here (mean_file) or on the first caffe_forward(net, image, mean_arr) call.
+    ``range_policy``: "raise" or "recompute_exact" (cnn.Net.set_range_policy)."""
     if model_def and os.path.isfile(model_def):
         caffe_io.check_deploy_prototxt(model_def)
     layers = caffe_io.read_caffemodel(model_weights)
@@ -60,7 +61,8 @@ def init_caffe(model_def, model_weights, gpu_id=0, mean_file=None):
             raise ValueError("caffemodel %s lacks layer %s" % (model_weights, key))
         w, b = layers[key][0], layers[key][1]
         weights[name] = (w.reshape(dict(cnn.LAYER_SHAPES)[name]), b.reshape(-1))
-    return cnn.LazyNet(weights, device=gpu_id, mean=None if mean_file is None else read_mean_blob(mean_file))
+    return cnn.LazyNet(weights, device=gpu_id, mean=None if mean_file is None else read_mean_blob(mean_file),
+                       range_policy=range_policy)
 
 
 def read_mean_blob(mean_file):
@@ -138,12 +140,16 @@ def detect_lsd_lines(image):
     return frontend.detect_lsd_lines(image)
 
 
-def run_cnn(dataset, model_def, model_weights, mean_file, gpu=0, net=None):
-    """evaluation.py:254-292, batched: every raster of the dataset goes through one forward call."""
+def run_cnn(dataset, model_def, model_weights, mean_file, gpu=0, net=None, range_policy="raise"):
+    """evaluation.py:254-292, batched: every raster of the dataset goes through one forward call.
+    ``range_policy``: "raise" (a clamped fp16-pair activation is VpkRangeError) or "recompute_exact" (such images are
+    recomputed on exact operands; cnn.Net.set_range_policy) -- applied to a given ``net`` too unless it is the default."""
     start = time.time()
     mean_arr = read_mean_blob(mean_file) if net is None else None
     if net is None:
-        net = init_caffe(model_def, model_weights, gpu)
+        net = init_caffe(model_def, model_weights, gpu, range_policy=range_policy)
+    elif range_policy != "raise":
+        net.set_range_policy(range_policy)
     print("CNN init time: ", time.time() - start)
     files = [f[0] if isinstance(f, tuple) else f for f in dataset['pickle_files']]
     data = [_load_pickle(f) for f in files]

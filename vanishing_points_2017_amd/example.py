@@ -22,11 +22,12 @@ def run_folder(args):
     evaluation.create_data_pickles(dataset, update=True, cnn_input_size=500, target_size=640)       # :37
     if all(os.path.isfile(f) for f in (config.cnn_weights_path, config.cnn_mean_path)):
         evaluation.run_cnn(dataset, mean_file=config.cnn_mean_path, model_def=config.cnn_config_path,
-                           model_weights=config.cnn_weights_path, gpu=args.gpu)          # :38
+                           model_weights=config.cnn_weights_path, gpu=args.gpu, range_policy=args.cnn_range)   # :38
     else:
         print("no trained weights at %s: random-init AlexNet-500" % config.cnn_weights_path)
         evaluation.run_cnn(dataset, None, None, None, gpu=args.gpu,
-                           net=cnn.Net(cnn.synthetic_weights(0), cnn.synthetic_mean(0), device=args.gpu))
+                           net=cnn.Net(cnn.synthetic_weights(0), cnn.synthetic_mean(0), device=args.gpu),
+                           range_policy=args.cnn_range)
     evaluation.run_em(dataset)                                                        # :39
     for image_file, data_file in zip(dataset['image_files'], dataset['pickle_files']):
         datum = evaluation._load_pickle(data_file)
@@ -54,6 +55,8 @@ def main(argv=None):
     p.add_argument('--lines', default=800, type=int)
     p.add_argument('--source_folder', default=None, help='folder with images (jpg / png / pgm)')
     p.add_argument('--destination_folder', default='/tmp/vp_example_results')
+    p.add_argument('--cnn-range', dest='cnn_range', choices=['raise', 'recompute_exact'], default='raise',
+                   help='CNN range policy: raise on a clamped fp16-pair activation, or recompute those images exactly')
     args = p.parse_args(argv)
     if args.source_folder:
         return run_folder(args)
@@ -61,6 +64,7 @@ def main(argv=None):
     datum = {'lines': {'lines': sc["l"], 'line_segments': sc["lp"], 'image_shape': sc["image_shape"]},
              'sphere_image': evaluation.get_sphere_image(sc["l"], size=500, alpha=0.1)}
     net = cnn.Net(cnn.synthetic_weights(0), cnn.synthetic_mean(0), device=args.gpu)
+    net.set_range_policy(args.cnn_range)
     datum['cnn_prediction'] = cnn.caffe_forward(net, datum['sphere_image'])
     print("CNN response (random-init weights): min %.3f max %.3f" % (datum['cnn_prediction'].min(),
                                                                      datum['cnn_prediction'].max()))

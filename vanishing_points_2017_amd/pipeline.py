@@ -17,12 +17,18 @@ MAX_VP = 64
 class Step(object):
     """Buffers of one batch in flight on (rt_cnn, rt_em).  ``d``: em.upload_batch() of the batch (resident inputs);
     ``l_in``: the pristine lines (device, sum N x 3).  ``records=True`` also builds sharding-layout records.
-    ``em_prior``: B x 400 response maps (device) the EM uses instead of this step's CNN output (the CNN still runs)."""
+    ``em_prior``: B x 400 response maps (device) the EM uses instead of this step's CNN output (the CNN still runs).
+    ``range_policy``: None (leave the CNN handle's as it is), "raise" or "recompute_exact" -- set on rt_cnn's handle, so it holds
+    for every forward on it (cnn.Net.set_range_policy); the exact recompute of clamped images runs inside the step's CNN forward,
+    before the EM is ordered behind it."""
 
     def __init__(self, rt_cnn, rt_em, d, params, l_in=None, max_vp=MAX_VP, records=False, image_ids=None, timing=True,
-                 em_prior=None):
+                 em_prior=None, range_policy=None):
         torch = rt_em.torch
         self.rt_cnn, self.rt_em = rt_cnn, rt_em
+        if range_policy is not None:
+            from .cnn import range_policy_code
+            rt_cnn.check(rt_cnn.lib.vpk_cnn_set_range_policy(rt_cnn.h, range_policy_code(range_policy)))
         self.offsets = _lib.host_i64(d["offsets"])
         batch = self.offsets.shape[0] - 1
         total = int(self.offsets[-1])
@@ -89,8 +95,8 @@ class Step(object):
         not the net's.  A pipeline calls this once per run, before it trusts the run's results."""
         w = ctypes.c_uint32(0)
         rc = self.rt_cnn.lib.vpk_cnn_range_flags(self.rt_cnn.h, ctypes.byref(w))
-        if rc == -6:
-            raise _lib.VpkRangeError("libvpk error -6: %s" % self.rt_cnn.lib.vpk_last_error(self.rt_cnn.h).decode(), int(w.value))
+        if rc == _lib.VPK_ERR_RANGE:
+            raise _lib.VpkRangeError("libvpk error %d: %s" % (rc, self.rt_cnn.lib.vpk_last_error(self.rt_cnn.h).decode()), int(w.value))
         self.rt_cnn.check(rc)
 
     def stage_ms(self):
