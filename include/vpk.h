@@ -195,6 +195,18 @@ int vpk_cnn_forward(vpk_handle* h, const uint8_t* sphere, int batch, float* out)
  * 10=fc8 pre-sigmoid); tap_out must hold batch * blob_size fp32. */
 int vpk_cnn_forward_tap(vpk_handle* h, const uint8_t* sphere, int batch, float* out, int tap,
                         float* tap_out);
+/* replaces: caffe_forward (evaluation.py:34-38) for float images: image B x 500 x 500 fp32 (DEVICE, 16-byte aligned), the
+ * values Caffe's float32 data blob holds BEFORE the mean is subtracted (any real value; a raster in [0, 1], a blurred or resampled
+ * one) -> out B x 20 x 20 fp32 (sigout).  Everything else is vpk_cnn_forward's / vpk_cnn_forward_tap's: unbounded batch
+ * (internally chunked), asynchronous on the handle's stream, the same range word, per-image bits (vpk_cnn_image_range_flags
+ * names the last forward of either type) and range policy.  Every arithmetic mode accepts it except vpk_cnn_set_fusion(4)
+ * (VPK_ERR_STATE: its fp16 conv1 needs integer pixels).  The default conv1 splits each pixel into three exact bf16 pieces
+ * (six products per weight and pixel instead of three); an integer-valued image in 0 .. 255 gives the same bits as its uint8
+ * raster.  Non-finite pixels are the caller's business, as in Caffe: nothing checks for them.  The activation scales stay
+ * those of uint8 calibration (vpk_cnn_calibrate): images far beyond the calibration set's magnitude are caught by the range
+ * flags and the range policy above, as for rasters. */
+int vpk_cnn_forward_f32(vpk_handle* h, const float* image, int batch, float* out);
+int vpk_cnn_forward_tap_f32(vpk_handle* h, const float* image, int batch, float* out, int tap, float* tap_out);
 
 /* How the net's layers are computed.  The reference runs Caffe in fp32 (deploy.prototxt, evaluation.py:20: cuDNN's pick of
  * algorithm per layer); every setting below keeps f32 operands, f32 accumulation and f32 results -- what changes is which matrix

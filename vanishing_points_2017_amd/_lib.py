@@ -60,6 +60,7 @@ class StepArgs(ctypes.Structure):
 EXPORTS = [
     "vpk_create", "vpk_destroy", "vpk_set_stream", "vpk_get_stream", "vpk_synchronize", "vpk_last_error", "vpk_version",
     "vpk_em_default_params", "vpk_device_info", "vpk_em_set_workgroups", "vpk_em_set_smoother", "vpk_em_set_lds_panel", "vpk_em_set_time_slice", "vpk_em_flush", "vpk_em_set_distribution_out", "vpk_cnn_load", "vpk_cnn_forward", "vpk_cnn_forward_tap",
+    "vpk_cnn_forward_f32", "vpk_cnn_forward_tap_f32",
     "vpk_cnn_set_profiling", "vpk_cnn_set_fusion", "vpk_cnn_set_precision", "vpk_cnn_set_algorithm", "vpk_cnn_last_layer_ms", "vpk_cnn_mean_layer_ms",
     "vpk_cnn_calibrate", "vpk_cnn_get_activation_scales", "vpk_cnn_set_activation_scales", "vpk_cnn_range_flags",
     "vpk_cnn_set_range_policy", "vpk_cnn_image_range_flags", "vpk_cnn_recomputed",
@@ -120,6 +121,8 @@ def load():
     lib.vpk_cnn_load.argtypes = [c_void, ctypes.POINTER(c_void), c_void]
     lib.vpk_cnn_forward.argtypes = [c_void, c_void, ctypes.c_int, c_void]
     lib.vpk_cnn_forward_tap.argtypes = [c_void, c_void, ctypes.c_int, c_void, ctypes.c_int, c_void]
+    lib.vpk_cnn_forward_f32.argtypes = [c_void, c_void, ctypes.c_int, c_void]
+    lib.vpk_cnn_forward_tap_f32.argtypes = [c_void, c_void, ctypes.c_int, c_void, ctypes.c_int, c_void]
     lib.vpk_cnn_set_profiling.argtypes = [c_void, ctypes.c_int]
     lib.vpk_cnn_set_fusion.argtypes = [c_void, ctypes.c_int]
     lib.vpk_cnn_set_precision.argtypes = [c_void, ctypes.c_int]

@@ -23,6 +23,32 @@ def range_policy_code(policy):
     return RANGE_POLICIES[policy]
 
 
+# image dtypes that take the float path (vpk_cnn_forward_f32): Caffe's data blob is float32, and evaluation.py:34-38 writes
+# `image - mean` into it, so a float image is used as its float32 rounding rather than cast to uint8
+FLOAT_DTYPES = ("float16", "float32", "float64")
+
+
+def image_kind(images):
+    """"f32" when ``images`` (numpy array, torch tensor, or anything np.asarray takes) has a float16 / float32 / float64 dtype,
+    "u8" for every other dtype (the uint8 rasters' path and cast).  Float images must be (500, 500) or (B, 500, 500):
+    ValueError otherwise, before any device work."""
+    dtype = getattr(images, "dtype", None)
+    if dtype is None:
+        images = np.asarray(images)
+        dtype = images.dtype
+    if str(dtype).replace("torch.", "") not in FLOAT_DTYPES:
+        return "u8"
+    shape = tuple(images.shape)
+    if len(shape) not in (2, 3) or shape[-2:] != (500, 500):
+        raise ValueError("float images must be (500, 500) or (B, 500, 500), got shape %s" % (shape,))
+    return "f32"
+
+
+def _first_axis(image):
+    """image[None] for a torch tensor, np.asarray(image)[None] otherwise (a single image -> a batch of one)."""
+    return image[None] if hasattr(image, "is_cuda") else np.asarray(image)[None]
+
+
 TAP_SHAPES = [(96, 123, 123), (96, 61, 61), (256, 61, 61), (256, 30, 30), (384, 30, 30), (384, 30, 30),
               (256, 30, 30), (256, 15, 15), (4096,), (4096,), (400,)]
 
@@ -72,18 +98,26 @@ class Net(object):
         self._last_batch = None          # batch of the last untapped forward (image_range_flags)
 
     def forward_device(self, sphere, tap=None):
-        """sphere: uint8 device tensor (B,500,500) -> float32 device tensor (B,20,20) [, tap tensor]."""
+        """sphere: uint8 device tensor (B,500,500) -> float32 device tensor (B,20,20) [, tap tensor].  A float16 / float32 /
+        float64 device tensor (B,500,500) runs the float path (vpk_cnn_forward_f32) on its float32 rounding."""
+        f32 = image_kind(sphere) == "f32"
+        if f32 and len(sphere.shape) != 3:
+            raise ValueError("forward_device: float images must be (B, 500, 500), got shape %s" % (tuple(sphere.shape),))
         rt = self.rt
         t = rt.torch
         batch = int(sphere.shape[0])
         with rt.on_stream():
+            if f32:             # (on the handle's stream: the forward is ordered behind the conversion)
+                sphere = sphere.to(device=rt.tdev, dtype=t.float32).contiguous()
             out = t.empty((batch, 20, 20), dtype=t.float32, device=rt.tdev)
             if tap is None:
-                rt.check(rt.lib.vpk_cnn_forward(rt.h, rt.ptr(sphere), batch, rt.ptr(out)))
+                fwd = rt.lib.vpk_cnn_forward_f32 if f32 else rt.lib.vpk_cnn_forward
+                rt.check(fwd(rt.h, rt.ptr(sphere), batch, rt.ptr(out)))
                 self._last_batch = batch
                 return out
             tp = t.empty((batch,) + TAP_SHAPES[tap], dtype=t.float32, device=rt.tdev)
-            rt.check(rt.lib.vpk_cnn_forward_tap(rt.h, rt.ptr(sphere), batch, rt.ptr(out), int(tap), rt.ptr(tp)))
+            fwd = rt.lib.vpk_cnn_forward_tap_f32 if f32 else rt.lib.vpk_cnn_forward_tap
+            rt.check(fwd(rt.h, rt.ptr(sphere), batch, rt.ptr(out), int(tap), rt.ptr(tp)))
             return out, tp
 
     LAYER_NAMES = ["conv1", "norm1", "pool1", "conv2", "norm2", "pool2", "conv3", "conv4", "conv5", "pool5",
@@ -227,13 +261,22 @@ class Net(object):
         return self.forward(sphere_u8)
 
     def forward_single(self, image, mean_arr=None):
-        return self.forward(np.asarray(image)[None])[0]
+        return self.forward(_first_axis(image))[0]
 
     def forward(self, sphere_u8, tap=None):
+        """(B,500,500) host images -> (B,20,20) float32 maps [, tap].  uint8 rasters (and every non-float dtype, cast to uint8);
+        float16 / float32 / float64 images (numpy, or torch on the host or the device) as Caffe's float32 blob holds them."""
         rt = self.rt
-        sphere_u8 = np.ascontiguousarray(sphere_u8, dtype=np.uint8).reshape(-1, 500, 500)
+        if image_kind(sphere_u8) == "f32":
+            if hasattr(sphere_u8, "is_cuda"):
+                d = sphere_u8.reshape(-1, 500, 500)          # forward_device converts to float32 on the handle's stream
+            else:
+                d = rt.torch.from_numpy(np.ascontiguousarray(sphere_u8, dtype=np.float32).reshape(-1, 500, 500))
+        else:
+            sphere_u8 = np.ascontiguousarray(sphere_u8, dtype=np.uint8).reshape(-1, 500, 500)
+            d = rt.torch.from_numpy(sphere_u8)
         with rt.on_stream():
-            d = rt.torch.from_numpy(sphere_u8).to(rt.tdev)
+            d = d.to(rt.tdev)
         res = self.forward_device(d, tap)
         self.check_range()          # (waits for the stream) a clamped activation is an error here, never a silently wrong map
         if tap is None:
@@ -271,12 +314,13 @@ class LazyNet(object):
         return net.forward(sphere_u8)
 
     def forward_single(self, image, mean_arr=None):
-        return self.forward_batch(np.asarray(image)[None], mean_arr)[0]
+        return self.forward_batch(_first_axis(image), mean_arr)[0]
 
 
 def caffe_forward(net, image, mean_arr=None):
-    """evaluation.py:34-38: one 500x500 uint8 raster -> (20,20) float32.  The mean blob was bound
-    at load time (it is fused into conv1's input load); mean_arr is accepted for signature parity."""
+    """evaluation.py:34-38: one 500x500 image -> (20,20) float32.  uint8 rasters as always; a float16 / float32 / float64
+    image is used as its float32 rounding (Caffe's data blob).  The mean blob was bound at load time (it is fused into
+    conv1's input load); mean_arr is accepted for signature parity."""
     if isinstance(net, LazyNet):
         return net.forward_single(image, mean_arr)
-    return net.forward(np.asarray(image)[None])[0]
+    return net.forward(_first_axis(image))[0]

@@ -21,6 +21,15 @@
 //   * epilogue as in conv1_direct_kernel: ReLU -> LDS patch [channel][column] -> LRN across channels in place -> 3 x 3 / 2
 //     max pool (windows clipped like Caffe's: positions outside the blob hold 0, every real value is >= 0) -> pool1's planes
 //     with conv2's border.  bf16 MFMAs do run beside VALU work (the f32-input ones do not).
+//
+// Float images (vpk_cnn_forward_f32: Caffe's float32 data blob, evaluation.py:34-38, any real value before the mean): Px = float.
+// A pixel is no longer one bf16 number, so the loader splits each f32 pixel into its exact bf16 triple (split3, cnn_split_gemm.hpp:
+// x = x0 + x1 + x2) and keeps three patch planes per buffer; a K step runs the six products whose pieces' orders add up to at most
+// two -- w0 x2, w1 x1, w0 x1, w2 x0, w1 x0, w0 x0 (the ones dropped are below 2^-24 of |w x|, the rule of cnn_split_gemm.hpp) --
+// grouped by pixel piece so that one piece's operands are in registers at a time, as the byte kernel's, and the pieces x2, x1 of
+// all six K steps before x0's.  The mean fold (`cmap`) and
+// everything behind the accumulators are the byte kernel's.  For an integer 0..255 the pieces x1, x2 are zeros, their products
+// add exact zeros to the accumulators, and w2 x0, w1 x0, w0 x0 run in the byte kernel's order: the same bits as the uint8 raster.
 #ifndef VPK_CNN_CONV1_PIECES_HPP_
 #define VPK_CNN_CONV1_PIECES_HPP_
 
@@ -95,8 +104,8 @@ inline void conv1_pieces_cmap(const float* w, const float* bias, const float* me
         }
 }
 
-template <int NP>
-__global__ __launch_bounds__(C1B_THREADS, 3) void conv1_pieces_kernel(const unsigned char* __restrict__ sphere,
+template <int NP, typename Px = unsigned char>
+__global__ __launch_bounds__(C1B_THREADS, 3) void conv1_pieces_kernel(const Px* __restrict__ sphere,
                                                                       const unsigned short* __restrict__ wfrag,
                                                                       const float* __restrict__ cmap, float* __restrict__ out,
                                                                       int OHp, int OWp, int opad, int batch, int group, float oscale,
@@ -104,7 +113,11 @@ __global__ __launch_bounds__(C1B_THREADS, 3) void conv1_pieces_kernel(const unsi
                                                                       unsigned short* __restrict__ out_planes, float p_ascale,
                                                                       unsigned* __restrict__ range_word, unsigned* __restrict__ img_range,
                                                                       const int* __restrict__ live) {
-    __shared__ __attribute__((aligned(16))) unsigned short Xs[2][C1B_XS];
+    constexpr bool F32 = std::is_same<Px, float>::value;               // float images: three pieces per pixel (F32 needs NP == 3)
+    static_assert(!F32 || NP == 3, "float images run on exact bf16 pieces");
+    constexpr int XP = F32 ? 3 : 1;                                     // patch planes per buffer: the pixel's pieces
+    typedef typename std::conditional<F32, f32x4, unsigned>::type Raw;  // a loader thread's four pixels
+    __shared__ __attribute__((aligned(16))) unsigned short Xs[2][XP * C1B_XS];
     // The output patch as [column][channel] (round 6; it was [channel][column]): a lane's four accumulator values are four consecutive
     // channels of one column, the LRN's window runs along the channels and a pooling thread takes four channels of a pixel -- every
     // phase of the epilogue moves 16 bytes per LDS instruction where it moved 4 (wave-level LDS instructions per tile: ~870 -> ~250;
@@ -137,14 +150,25 @@ __global__ __launch_bounds__(C1B_THREADS, 3) void conv1_pieces_kernel(const unsi
         const int crow = c / C1_PC, ccol = c - crow * C1_PC;
         bp[j] = (lds_cu32x2*)&Xs[0][(4 * crow + (q >> 1)) * C1B_LDW + 4 * ccol + 8 * (q & 1)];
     }
-    // ---- patch loader: thread t < 720 brings the four pixels (row t / 20, columns 4 (t % 20) ..) as one 4-byte word ----
+    // ---- patch loader: thread t < 720 brings the four pixels (row t / 20, columns 4 (t % 20) ..) as one 4-byte word (floats: 16 bytes) ----
     const bool p_on = tid < C1B_PROWS * (C1B_PCOLS / 4);
     const int p_row = p_on ? tid / (C1B_PCOLS / 4) : 0, p_q = p_on ? tid - p_row * (C1B_PCOLS / 4) : 0;
     auto patch_offset = [&](int pr, int pc) {                           // byte offset inside an image; overhang is clamped
         const int y = 4 * (C1_PR - 1) * pr + p_row, x = 4 * (C1_PC - 1) * pc + 4 * p_q;   //  (it only meets zero weights and
         return (y < 500 ? y : 499) * 500 + (x < 496 ? x : 496);         //   conv outputs outside the blob, which are zeroed)
     };
-    auto patch_store = [&](unsigned v, int buf) {                        // uint8 -> bf16: exact, the high half of the f32 (fp16: exact too)
+    auto patch_store = [&](Raw v, int buf) {                             // uint8 -> bf16: exact, the high half of the f32 (fp16: exact too)
+        if constexpr (F32) {                                             // f32 -> three bf16 planes (x0, x1, x2 of split3)
+            if (p_on) {
+                unsigned short pc[3][4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) split3(v[e], pc[0][e], pc[1][e], pc[2][e]);
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+                    *reinterpret_cast<u32x2*>(&Xs[buf][k * C1B_XS + p_row * C1B_LDW + 4 * p_q]) =
+                        u32x2{(unsigned)pc[k][0] | ((unsigned)pc[k][1] << 16), (unsigned)pc[k][2] | ((unsigned)pc[k][3] << 16)};
+            }
+        } else
         if (p_on) {
             u32x2 w2;
             if (NP == 3) {
@@ -179,7 +203,7 @@ __global__ __launch_bounds__(C1B_THREADS, 3) void conv1_pieces_kernel(const unsi
     int b1 = b + group < batch ? b + group : batch;
     if (tid == 0) s_next[0] = atomicAdd(item_counter, 1) + (int)gridDim.x;
     int poff = patch_offset(pr, pc);
-    patch_store(*reinterpret_cast<const unsigned*>(sphere + (size_t)b * 250000 + poff), 0);
+    patch_store(*reinterpret_cast<const Raw*>(sphere + (size_t)b * 250000 + poff), 0);
     bool fresh = true;                                                   // first tile of a work item: fetch its constants
     f32x4 cin[4];
     float cap[4];
@@ -187,7 +211,9 @@ __global__ __launch_bounds__(C1B_THREADS, 3) void conv1_pieces_kernel(const unsi
     for (int j = 0; j < 4; ++j) { cin[j] = f32x4{0.f, 0.f, 0.f, 0.f}; cap[j] = 0.f; }
     lds_barrier();
     for (;;) {
-        if (fresh) {
+        // (float images: the constants are fetched again for every tile -- under its K loop -- rather than kept across the LRN,
+        //  whose registers the f32 pixels of the next patch need)
+        if (fresh || F32) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int c = 64 * chalf + 16 * j + c16;
@@ -207,31 +233,64 @@ __global__ __launch_bounds__(C1B_THREADS, 3) void conv1_pieces_kernel(const unsi
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
         u32x2 braw[2][4][2];
-        auto operands = [&](int s) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                lds_cu32x2* src = bp[j] + buf * (C1B_XS / 4) + s * (2 * C1B_LDW / 4);
-                braw[s & 1][j][0] = src[0];
-                braw[s & 1][j][1] = src[1];
-            }
-        };
-        operands(0);
-#pragma unroll
-        for (int s = 0; s < C1B_STEPS; ++s) {
-            if (s + 1 < C1B_STEPS) operands(s + 1);
-            bf16x8 bf[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const u32x4 t4 = {braw[s & 1][j][0][0], braw[s & 1][j][0][1], braw[s & 1][j][1][0], braw[s & 1][j][1][1]};
-                bf[j] = __builtin_bit_cast(bf16x8, t4);
-            }
-#pragma unroll
-            for (int p = NP - 1; p >= 0; --p)
+        if constexpr (F32) {
+            // 18 operand groups g = (pixel piece 2 - g / 6, K step g % 6): the x2 and x1 products of all six steps first, then the
+            // x0 products in the byte kernel's order -- the accumulators hold only the small products' sum when the large products
+            // arrive, so the large ones meet the roundings the byte kernel's meet (grouped by step, twice as many roundings at the
+            // magnitude of sum w x -- x not yet minus the mean -- measured 1.8x the f32 direct kernel's error at pool1); group
+            // g + 1's operands are requested before group g's matrix instructions; weight pieces w_p with p + (pixel piece) <= 2,
+            // smallest first
+            auto operands = [&](int g) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    if constexpr (NP == 3) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[s][p], bf[j], acc[j], 0, 0, 0);
-                    else acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, A[s][p]), __builtin_bit_cast(f16x8, bf[j]), acc[j], 0, 0, 0);
+                    lds_cu32x2* src = bp[j] + buf * (XP * C1B_XS / 4) + (2 - g / C1B_STEPS) * (C1B_XS / 4) + (g % C1B_STEPS) * (2 * C1B_LDW / 4);
+                    braw[g & 1][j][0] = src[0];
+                    braw[g & 1][j][1] = src[1];
                 }
+            };
+            operands(0);
+#pragma unroll
+            for (int g = 0; g < 3 * C1B_STEPS; ++g) {
+                if (g + 1 < 3 * C1B_STEPS) operands(g + 1);
+                const int s = g % C1B_STEPS, xp = 2 - g / C1B_STEPS;
+                bf16x8 bf[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const u32x4 t4 = {braw[g & 1][j][0][0], braw[g & 1][j][0][1], braw[g & 1][j][1][0], braw[g & 1][j][1][1]};
+                    bf[j] = __builtin_bit_cast(bf16x8, t4);
+                }
+#pragma unroll
+                for (int p = 2 - xp; p >= 0; --p)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[s][p], bf[j], acc[j], 0, 0, 0);
+            }
+        } else {
+            auto operands = [&](int s) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    lds_cu32x2* src = bp[j] + buf * (C1B_XS / 4) + s * (2 * C1B_LDW / 4);
+                    braw[s & 1][j][0] = src[0];
+                    braw[s & 1][j][1] = src[1];
+                }
+            };
+            operands(0);
+#pragma unroll
+            for (int s = 0; s < C1B_STEPS; ++s) {
+                if (s + 1 < C1B_STEPS) operands(s + 1);
+                bf16x8 bf[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const u32x4 t4 = {braw[s & 1][j][0][0], braw[s & 1][j][0][1], braw[s & 1][j][1][0], braw[s & 1][j][1][1]};
+                    bf[j] = __builtin_bit_cast(bf16x8, t4);
+                }
+#pragma unroll
+                for (int p = NP - 1; p >= 0; --p)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        if constexpr (NP == 3) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[s][p], bf[j], acc[j], 0, 0, 0);
+                        else acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, A[s][p]), __builtin_bit_cast(f16x8, bf[j]), acc[j], 0, 0, 0);
+                    }
+            }
         }
         lds_barrier();                                                   // (the previous tile's pooling has read Cs)
         // ---- what comes next: the same item's next image, or the next item's first (its index was stored before at
@@ -246,10 +305,10 @@ __global__ __launch_bounds__(C1B_THREADS, 3) void conv1_pieces_kernel(const unsi
             n_fresh = true;
         }
         const bool n_on = n_item < total_items;
-        unsigned pre = 0;
+        Raw pre = {};
         if (n_on) {
             if (n_fresh) poff = patch_offset(n_pr, n_pc);
-            pre = *reinterpret_cast<const unsigned*>(sphere + (size_t)n_b * 250000 + poff);
+            pre = *reinterpret_cast<const Raw*>(sphere + (size_t)n_b * 250000 + poff);
         }
         // ---- + constant, ReLU -> Ct[column][channel + 4]; positions outside the conv blob become 0 ----
 #pragma unroll

@@ -17,6 +17,7 @@
 
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -439,7 +440,9 @@ __device__ long long c1d_dbg[256 * 8 * 8];
 #else
 #define C1D_T(i)
 #endif
-__global__ __launch_bounds__(C1D_THREADS, 2) void conv1_direct_kernel(const unsigned char* __restrict__ sphere,
+// Px = float: the images of vpk_cnn_forward_f32 (Caffe's float32 blob before the mean), four pixels = one 16-byte word
+template <typename Px = unsigned char>
+__global__ __launch_bounds__(C1D_THREADS, 2) void conv1_direct_kernel(const Px* __restrict__ sphere,
                                                                       const float* __restrict__ mean, const float* __restrict__ wp,
                                                                       const float* __restrict__ bias, float* __restrict__ out,
                                                                       int OHp, int OWp, int opad, int* __restrict__ tile_counter,
@@ -488,6 +491,8 @@ __global__ __launch_bounds__(C1D_THREADS, 2) void conv1_direct_kernel(const unsi
     constexpr int QUADS = C1_PH * C1D_PY * C1D_PX;                                 // 684
     constexpr int PRE = (QUADS + C1D_THREADS - 1) / C1D_THREADS;                   // quads per thread (2)
     constexpr int PRE_LAST = QUADS - (PRE - 1) * C1D_THREADS;                      // threads that hold a second one
+    constexpr bool F32 = std::is_same<Px, float>::value;
+    typedef typename std::conditional<F32, f32x4, unsigned>::type Raw;         // a quad of pixels
     int qoff[PRE], pdst[PRE], pyx[PRE];
 #pragma unroll
     for (int u = 0; u < PRE; ++u) {
@@ -498,10 +503,10 @@ __global__ __launch_bounds__(C1D_THREADS, 2) void conv1_direct_kernel(const unsi
         pdst[u] = ((pq * C1_PH) * C1D_PY + py) * C1D_PXL + px;                     // LDS index in phase plane (pq, 0)
         pyx[u] = (pq << 16) | (py << 8) | px;
     }
-    auto patch_load = [&](int tile, f32x4 (&v)[PRE], unsigned (&v8)[PRE]) {
+    auto patch_load = [&](int tile, f32x4 (&v)[PRE], Raw (&v8)[PRE]) {
         const int pc = tile % C1_TC, pr = (tile / C1_TC) % C1_TR, b = tile / (C1_TC * C1_TR);
         const int y0 = (C1_PR - 1) * pr, x0 = (C1_PC - 1) * pc;
-        const unsigned char* img = sphere + (size_t)b * 500 * 500;
+        const Px* img = sphere + (size_t)b * 500 * 500;
         if (pr < C1_TR - 1 && pc < C1_TC - 1) {        // the patch lies inside the planes: scalar base + per-thread offset
             const int origin = (C1_PH * y0) * 500 + C1_PH * x0;
 #pragma unroll
@@ -509,7 +514,7 @@ __global__ __launch_bounds__(C1D_THREADS, 2) void conv1_direct_kernel(const unsi
                 const bool on = u < PRE - 1 || tid < PRE_LAST;
                 const int o = on ? origin + qoff[u] : origin;
                 v[u] = *reinterpret_cast<const f32x4*>(mean + o);
-                v8[u] = *reinterpret_cast<const unsigned*>(img + o);
+                v8[u] = *reinterpret_cast<const Raw*>(img + o);
             }
         } else {
 #pragma unroll
@@ -520,24 +525,26 @@ __global__ __launch_bounds__(C1D_THREADS, 2) void conv1_direct_kernel(const unsi
                 const bool on = u < PRE - 1 || tid < PRE_LAST;
                 const int o = on ? (C1_PH * yc + pq) * 500 + C1_PH * xc : 0;
                 v[u] = *reinterpret_cast<const f32x4*>(mean + o);
-                v8[u] = *reinterpret_cast<const unsigned*>(img + o);
+                v8[u] = *reinterpret_cast<const Raw*>(img + o);
             }
         }
     };
-    auto patch_store = [&](const f32x4 (&v)[PRE], const unsigned (&v8)[PRE]) {
+    auto patch_store = [&](const f32x4 (&v)[PRE], const Raw (&v8)[PRE]) {
 #pragma unroll
         for (int u = 0; u < PRE; ++u)
             if (u < PRE - 1 || tid < PRE_LAST) {
 #pragma unroll
-                for (int q = 0; q < C1_PH; ++q)
-                    Xs[pdst[u] + q * (C1D_PY * C1D_PXL)] = (float)((v8[u] >> (8 * q)) & 255u) - v[u][q];
+                for (int q = 0; q < C1_PH; ++q) {
+                    if constexpr (F32) Xs[pdst[u] + q * (C1D_PY * C1D_PXL)] = v8[u][q] - v[u][q];
+                    else Xs[pdst[u] + q * (C1D_PY * C1D_PXL)] = (float)((v8[u] >> (8 * q)) & 255u) - v[u][q];
+                }
             }
     };
     // dynamic tile queue (CUs held by other streams' kernels make static shares uneven); the index of the tile after
     // next is fetched one tile ahead, so the atomic's round trip is never waited for
     int tile = blockIdx.x;
     f32x4 pre[PRE];
-    unsigned pre8[PRE];
+    Raw pre8[PRE];
     if (tile < total_tiles) { patch_load(tile, pre, pre8); patch_store(pre, pre8); }
     if (tid == 0) s_next[0] = atomicAdd(tile_counter, 1) + (int)gridDim.x;
     __syncthreads();
@@ -694,7 +701,7 @@ extern "C" int vpk_dbg_c1d(long long* out) { return (int)hipMemcpyFromSymbol(out
 #endif
 
 // conv1 input for the unfused / tapped paths (the default conv1_direct_kernel converts in its patch loader):
-// float(uint8 raster) - mean (evaluation.py:35), written as the 16 stride-4 phase planes
+// float(uint8 raster) - mean (evaluation.py:35), written as the 16 stride-4 phase planes (Px = float: float image - mean)
 //   P[py][px][Y][X] = x[4Y + py][4X + px]   (125 x 125 each)
 // so that conv1 (11 x 11, stride 4) is a stride-1 gather for the DMA kernel: tap (kh, kw) of output (oh, ow)
 // is P[kh % 4][kw % 4][oh + kh / 4][ow + kw / 4], and the 64 lanes of a gather (consecutive ow) read 256
@@ -702,7 +709,8 @@ extern "C" int vpk_dbg_c1d(long long* out) { return (int)hipMemcpyFromSymbol(out
 // 2.76 -> 2.57 ms at B = 512, unchanged at B = 102.  With its MFMAs and stores removed conv1 still takes
 // 0.36 of its 0.58 ms: with only 8 K-stages per tile it is bound by the issue rate of the 4-byte gather DMAs
 // (about one per 40-60 cycles per CU), which a wider (16-byte, row-tiled) loader would relieve.
-__global__ void prep_input_kernel(const unsigned char* __restrict__ sphere, const float* __restrict__ mean,
+template <typename Px>
+__global__ void prep_input_kernel(const Px* __restrict__ sphere, const float* __restrict__ mean,
                                   float* __restrict__ out, int plane) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;       // pixel within the image
     if (p >= plane) return;
@@ -1159,13 +1167,25 @@ struct FwdCtl {
     const int* live;            // recompute pass: the device count of images -- `batch` is then only its upper bound; null: batch
 };
 
-int run_forward(vpk_handle* h, const uint8_t* sphere, int batch, float* out, int tap, float* tap_out, const FwdCtl& fc) {
+// The images of a forward: uint8 rasters (vpk_cnn_forward) or float images before the mean (vpk_cnn_forward_f32), B x 500 x 500
+struct Images {
+    const void* p;
+    bool f32;
+    const uint8_t* u8() const { return static_cast<const uint8_t*>(p); }
+    const float* f() const { return static_cast<const float*>(p); }
+    Images at(size_t b) const { return Images{f32 ? (const void*)(f() + b * 250000) : (const void*)(u8() + b * 250000), f32}; }
+};
+
+int run_forward(vpk_handle* h, Images img, int batch, float* out, int tap, float* tap_out, const FwdCtl& fc) {
     vpk_cnn_state* S = h->cnn;
     hipStream_t st = h->stream;
     // the kernels that honour a device count are those of the exact configuration with the default conv1
     if (fc.live && !(S->precision == 0 && S->algorithm == 2 && S->fuse_conv1 == 3 && tap < 0 && !S->profiling))
         return vpk_fail(h, VPK_ERR_STATE, "run_forward: a device-counted pass runs algorithm 2 with the default conv1, untapped");
     const int* live = fc.live;
+    // (the scaled fp16-pair conv1 relies on a pixel being an exact fp16 number: uint8 rasters only)
+    if (img.f32 && S->fuse_conv1 == 4 && !(tap == 0 || !S->fuse_conv1))
+        return vpk_fail(h, VPK_ERR_STATE, "vpk_cnn_forward_f32: vpk_cnn_set_fusion(4) takes uint8 rasters only");
     if (batch > S->act_batch) {     // grow the arena; all borders (and everything else) start as zeros
         const size_t need = ((size_t)batch * arena_floats_per_image() + GUARD_FLOATS + CTR_FLOATS) * sizeof(float);
         int rc = vpk_reserve(h, (void**)&S->act, &S->act_bytes, need, "hipMalloc(CNN activations)");
@@ -1211,9 +1231,14 @@ int run_forward(vpk_handle* h, const uint8_t* sphere, int batch, float* out, int
     const bool conv1_hands_planes = S->precision == 0 && S->algorithm == 4 && S->fuse_conv1 >= 3 && tap != 0 && tap != 1;
     // conv1 + relu1: uint8 raster - mean -> fp32 (pre-pass), then the DMA kernel
     const bool direct = !(tap == 0 || !S->fuse_conv1) && S->fuse_conv1 != 2;   // conv1_direct_kernel reads the rasters itself
-    if (!direct)
-        hipLaunchKernelGGL(prep_input_kernel, dim3((500 * 500 + 255) / 256, batch), dim3(256), 0, st, sphere, S->mean, R[R_IN],
-                           500 * 500);
+    if (!direct) {
+        if (img.f32)
+            hipLaunchKernelGGL(prep_input_kernel<float>, dim3((500 * 500 + 255) / 256, batch), dim3(256), 0, st, img.f(), S->mean, R[R_IN],
+                               500 * 500);
+        else
+            hipLaunchKernelGGL(prep_input_kernel<unsigned char>, dim3((500 * 500 + 255) / 256, batch), dim3(256), 0, st, img.u8(), S->mean,
+                               R[R_IN], 500 * 500);
+    }
     if (tap == 0 || !S->fuse_conv1) {
         launch_dma(h, conv_gemm_dma_kernel<1, 4, 3, 1, false>, dims(0), 96, R[R_IN], S->L[0], R[R_CONV1], 1, ctr + 0);   // stride 1 over the phase planes
         mark();
@@ -1232,11 +1257,15 @@ int run_forward(vpk_handle* h, const uint8_t* sphere, int batch, float* out, int
             // fp16 pairs downstream and pool1 not tapped: the pooling stage writes conv2's piece planes itself (no f32 pool1 blob)
             unsigned short* c2planes = conv1_hands_planes ? reinterpret_cast<unsigned short*>(R[R_P6_2]) : nullptr;
             if (S->fuse_conv1 == 4)
-                hipLaunchKernelGGL(conv1_pieces_kernel<2>, dim3((unsigned)std::min(total, h->num_cu)), dim3(C1B_THREADS), 0, st, sphere,
+                hipLaunchKernelGGL(conv1_pieces_kernel<2>, dim3((unsigned)std::min(total, h->num_cu)), dim3(C1B_THREADS), 0, st, img.u8(),
                                    S->L[0].c1half, S->L[0].c1map, R[R_POOL1], 65, 65, 2, batch, group, 1.f / S->L[0].c1scale, ctr + 0, total,
                                    c2planes, S->L[1].ascale, fc.range_word, fc.img_range, live);
+            else if (img.f32)                             // float images: three pieces per pixel, six products per K step
+                hipLaunchKernelGGL((conv1_pieces_kernel<3, float>), dim3((unsigned)std::min(total, h->num_cu)), dim3(C1B_THREADS), 0, st,
+                                   img.f(), S->L[0].c1frag, S->L[0].c1map, R[R_POOL1], 65, 65, 2, batch, group, 1.f, ctr + 0, total,
+                                   c2planes, S->L[1].ascale, fc.range_word, fc.img_range, live);
             else
-                hipLaunchKernelGGL(conv1_pieces_kernel<3>, dim3((unsigned)std::min(total, h->num_cu)), dim3(C1B_THREADS), 0, st, sphere,
+                hipLaunchKernelGGL(conv1_pieces_kernel<3>, dim3((unsigned)std::min(total, h->num_cu)), dim3(C1B_THREADS), 0, st, img.u8(),
                                    S->L[0].c1frag, S->L[0].c1map, R[R_POOL1], 65, 65, 2, batch, group, 1.f, ctr + 0, total,
                                    c2planes, S->L[1].ascale, fc.range_word, fc.img_range, live);
         } else if (S->fuse_conv1 == 2) {                  // the implicit-GEMM kernel with the fused epilogue (kept for comparison)
@@ -1246,8 +1275,12 @@ int run_forward(vpk_handle* h, const uint8_t* sphere, int batch, float* out, int
             launch_dma(h, conv_gemm_dma_kernel<1, 4, 3, 1, false, true>, df, 96, R[R_IN], S->L[0], R[R_POOL1], 1, ctr + 0);
         } else {
             const int total = batch * C1_TR * C1_TC;
-            hipLaunchKernelGGL(conv1_direct_kernel, dim3((unsigned)std::min(total, h->num_cu)), dim3(C1D_THREADS), 0, st, sphere,
-                               S->mean, S->L[0].wp, S->L[0].bias, R[R_POOL1], 65, 65, 2, ctr + 0, total);
+            if (img.f32)
+                hipLaunchKernelGGL(conv1_direct_kernel<float>, dim3((unsigned)std::min(total, h->num_cu)), dim3(C1D_THREADS), 0, st, img.f(),
+                                   S->mean, S->L[0].wp, S->L[0].bias, R[R_POOL1], 65, 65, 2, ctr + 0, total);
+            else
+                hipLaunchKernelGGL(conv1_direct_kernel<unsigned char>, dim3((unsigned)std::min(total, h->num_cu)), dim3(C1D_THREADS), 0, st,
+                                   img.u8(), S->mean, S->L[0].wp, S->L[0].bias, R[R_POOL1], 65, 65, 2, ctr + 0, total);
         }
         mark();
         mark();
@@ -1535,7 +1568,7 @@ int blob_maxima(vpk_handle* h, const uint8_t* d_imgs, int n, float mx[CAL_N]) {
     for (int b0 = 0; b0 < n && rc == VPK_OK; b0 += chunk) {
         const int nb = n - b0 < chunk ? n - b0 : chunk;
         for (int i = 0; i < CAL_N && rc == VPK_OK; ++i) {
-            rc = run_forward(h, d_imgs + (size_t)b0 * 500 * 500, nb, d_out, CAL_TAP[i], d_tap, FwdCtl{S->range_word, nullptr, nullptr});
+            rc = run_forward(h, Images{d_imgs + (size_t)b0 * 500 * 500, false}, nb, d_out, CAL_TAP[i], d_tap, FwdCtl{S->range_word, nullptr, nullptr});
             if (rc == VPK_OK) hipLaunchKernelGGL(absmax_kernel, dim3(256), dim3(256), 0, h->stream, d_tap, (size_t)nb * CAL_SIZE[i], d_max + i);
         }
     }
@@ -1613,14 +1646,17 @@ __global__ __launch_bounds__(1024) void range_compact_kernel(const unsigned* __r
     }
 }
 
-// slot s < list[0]: the raster of image list[1 + s] (250 000 bytes = 62 500 words: the rasters are 4-byte aligned; 8 workgroups per slot)
-__global__ __launch_bounds__(256) void range_gather_kernel(const uint8_t* __restrict__ sphere, const int* __restrict__ list,
-                                                           uint8_t* __restrict__ slots) {
+// slot s < list[0]: the raster of image list[1 + s] (250 000 bytes = 62 500 words: the rasters are 4-byte aligned; 8 workgroups per slot;
+// Px = float: the float image, 250 000 words -- the size of an image's R_IN)
+template <typename Px>
+__global__ __launch_bounds__(256) void range_gather_kernel(const Px* __restrict__ sphere, const int* __restrict__ list,
+                                                           Px* __restrict__ slots) {
+    constexpr int WORDS = 250000 * (int)sizeof(Px) / 4;
     const int s = blockIdx.y;
     if (s >= list[0]) return;
     const unsigned* src = reinterpret_cast<const unsigned*>(sphere + (size_t)list[1 + s] * 250000);
     unsigned* dst = reinterpret_cast<unsigned*>(slots + (size_t)s * 250000);
-    for (int q = blockIdx.x * 256 + threadIdx.x; q < 250000 / 4; q += gridDim.x * 256) dst[q] = src[q];
+    for (int q = blockIdx.x * 256 + threadIdx.x; q < WORDS; q += gridDim.x * 256) dst[q] = src[q];
 }
 
 // slot s < list[0]: its 400-float map -> row list[1 + s] of out
@@ -1634,19 +1670,22 @@ __global__ __launch_bounds__(128) void range_scatter_kernel(const float* __restr
 }
 
 // the exact recompute of a chunk's flagged images (nb <= MAX_CHUNK; the arena holds nb images: the pair pass ran just before)
-int recompute_flagged(vpk_handle* h, const uint8_t* sphere, int nb, float* out, const unsigned* img_range) {
+int recompute_flagged(vpk_handle* h, Images img, int nb, float* out, const unsigned* img_range) {
     vpk_cnn_state* S = h->cnn;
     hipStream_t st = h->stream;
     size_t off_fca = 0;
     for (int i = 0; i < R_FCA; ++i) off_fca += (size_t)S->act_batch * REGION_FLOATS[i];
-    uint8_t* slots = reinterpret_cast<uint8_t*>(S->act);                  // R_IN (region 0): 4 bytes per raster byte of room
+    void* slots = S->act;                                                 // R_IN (region 0): 4 bytes per raster byte (one float image) of room
     float* maps = S->act + off_fca;                                       // R_FCA: 4096 floats per image of room
     hipLaunchKernelGGL(range_compact_kernel, dim3(1), dim3(1024), 0, st, img_range, nb, S->rc_list, S->rc_total);
-    hipLaunchKernelGGL(range_gather_kernel, dim3(8, (unsigned)nb), dim3(256), 0, st, sphere, S->rc_list, slots);
+    if (img.f32)
+        hipLaunchKernelGGL(range_gather_kernel<float>, dim3(8, (unsigned)nb), dim3(256), 0, st, img.f(), S->rc_list, static_cast<float*>(slots));
+    else
+        hipLaunchKernelGGL(range_gather_kernel<uint8_t>, dim3(8, (unsigned)nb), dim3(256), 0, st, img.u8(), S->rc_list, static_cast<uint8_t*>(slots));
     const int keep_alg = S->algorithm, keep_fuse = S->fuse_conv1;
     const bool keep_prof = S->profiling;
     S->algorithm = 2; S->fuse_conv1 = 3; S->profiling = false;
-    const int rc = run_forward(h, slots, nb, maps, -1, nullptr, FwdCtl{S->range_word + 1, nullptr, S->rc_list});
+    const int rc = run_forward(h, Images{slots, img.f32}, nb, maps, -1, nullptr, FwdCtl{S->range_word + 1, nullptr, S->rc_list});
     S->algorithm = keep_alg; S->fuse_conv1 = keep_fuse; S->profiling = keep_prof;
     if (rc) return rc;
     hipLaunchKernelGGL(range_scatter_kernel, dim3((unsigned)nb), dim3(128), 0, st, maps, S->rc_list, out);
@@ -1976,10 +2015,12 @@ int vpk_cnn_range_flags(vpk_handle* h, uint32_t* flags_out) {
 
 namespace {
 // policy: vpk_cnn_forward (per-image flags kept, the range policy applied); !policy: vpk_cnn_forward_tap, as before the policy existed
-int forward_chunks(vpk_handle* h, const uint8_t* sphere, int batch, float* out, int tap, float* tap_out, bool policy) {
-    if (!h || !sphere || !out || batch < 1) return vpk_fail(h, VPK_ERR_ARG, "vpk_cnn_forward: bad argument");
-    if (((size_t)sphere & 3) != 0)      // conv1's loader reads four horizontally adjacent pixels as one 4-byte word
+int forward_chunks(vpk_handle* h, Images sphere, int batch, float* out, int tap, float* tap_out, bool policy) {
+    if (!h || !sphere.p || !out || batch < 1) return vpk_fail(h, VPK_ERR_ARG, "vpk_cnn_forward: bad argument");
+    if (!sphere.f32 && ((size_t)sphere.p & 3) != 0)      // conv1's loader reads four horizontally adjacent pixels as one 4-byte word
         return vpk_fail(h, VPK_ERR_ARG, "vpk_cnn_forward: the rasters must be 4-byte aligned");
+    if (sphere.f32 && ((size_t)sphere.p & 15) != 0)      // ... as one 16-byte word
+        return vpk_fail(h, VPK_ERR_ARG, "vpk_cnn_forward_f32: the images must be 16-byte aligned");
     if (!h->cnn || !h->cnn->loaded) return vpk_fail(h, VPK_ERR_STATE, "vpk_cnn_forward before vpk_cnn_load");
     VPK_HIP(h, hipSetDevice(h->device));
     // activations for the whole batch stay in HBM; chunk only if they would exceed a third of it
@@ -2001,7 +2042,7 @@ int forward_chunks(vpk_handle* h, const uint8_t* sphere, int batch, float* out, 
     for (int b0 = 0; b0 < batch; b0 += chunk) {
         int nb = std::min(chunk, batch - b0);
         float* tp = (tap_out && tap >= 0 && tap <= 10) ? tap_out + (size_t)b0 * tap_size[tap] : nullptr;
-        const uint8_t* sp = sphere + (size_t)b0 * 500 * 500;
+        const Images sp = sphere.at((size_t)b0);
         float* op = out + (size_t)b0 * 400;
         unsigned* img = policy ? S->img_range + b0 : nullptr;
         int rc = run_forward(h, sp, nb, op, tp ? tap : -1, tp, FwdCtl{recompute ? S->range_word + 1 : S->range_word, img, nullptr});
@@ -2015,11 +2056,19 @@ int forward_chunks(vpk_handle* h, const uint8_t* sphere, int batch, float* out, 
 extern "C" {
 
 int vpk_cnn_forward_tap(vpk_handle* h, const uint8_t* sphere, int batch, float* out, int tap, float* tap_out) {
-    return forward_chunks(h, sphere, batch, out, tap, tap_out, false);
+    return forward_chunks(h, Images{sphere, false}, batch, out, tap, tap_out, false);
 }
 
 int vpk_cnn_forward(vpk_handle* h, const uint8_t* sphere, int batch, float* out) {
-    return forward_chunks(h, sphere, batch, out, -1, nullptr, true);
+    return forward_chunks(h, Images{sphere, false}, batch, out, -1, nullptr, true);
+}
+
+int vpk_cnn_forward_tap_f32(vpk_handle* h, const float* image, int batch, float* out, int tap, float* tap_out) {
+    return forward_chunks(h, Images{image, true}, batch, out, tap, tap_out, false);
+}
+
+int vpk_cnn_forward_f32(vpk_handle* h, const float* image, int batch, float* out) {
+    return forward_chunks(h, Images{image, true}, batch, out, -1, nullptr, true);
 }
 
 int vpk_cnn_set_range_policy(vpk_handle* h, int policy) {

@@ -71,7 +71,8 @@ def read_mean_blob(mean_file):
 
 
 def caffe_forward(net, image, mean_arr):
-    """evaluation.py:34-38: uint8 500x500 raster -> (20, 20) float32 sigout."""
+    """evaluation.py:34-38: 500x500 image -> (20, 20) float32 sigout.  A uint8 raster, or a float16 / float32 / float64
+    image used as Caffe's float32 data blob holds it (cnn.image_kind)."""
     return net.forward_single(image, mean_arr)
 
 
@@ -143,7 +144,9 @@ def detect_lsd_lines(image):
 def run_cnn(dataset, model_def, model_weights, mean_file, gpu=0, net=None, range_policy="raise"):
     """evaluation.py:254-292, batched: every raster of the dataset goes through one forward call.
     ``range_policy``: "raise" (a clamped fp16-pair activation is VpkRangeError) or "recompute_exact" (such images are
-    recomputed on exact operands; cnn.Net.set_range_policy) -- applied to a given ``net`` too unless it is the default."""
+    recomputed on exact operands; cnn.Net.set_range_policy) -- applied to a given ``net`` too unless it is the default.
+    Float ``sphere_image``s take the float path; in a mixed dataset np.stack makes the uint8 rasters float too, and an
+    integer-valued float image gives the same bits as its uint8 raster."""
     start = time.time()
     mean_arr = read_mean_blob(mean_file) if net is None else None
     if net is None:
