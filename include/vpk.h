@@ -283,7 +283,7 @@ int vpk_sphere_raster_set_alternative(vpk_handle* h, int on);
  * simplified curve keeps 30-100 of its 10 000 samples).  `batch` must be that call's batch (VPK_ERR_ARG otherwise). */
 int vpk_sphere_raster_flags(vpk_handle* h, int batch, uint32_t* flags_out);
 
-/* ---- front end: line segment detection (HOST code, host pointers) -------------------------------------------- */
+/* ---- front end: line segment detection (vpk_lsd_detect: HOST code, host pointers) -------------------------------- */
 /* replaces: lsdpython.lsd.detect_line_segments(image) as called by detect_lsd_lines (evaluation.py:227-251; the
  * detector itself is an un-vendored submodule of the reference, .gitmodules:1-3 -- parity unpinned, see
  * csrc/vpk_lsd.cpp).  image [host]: height x width fp64 grey levels 0..255, row-major; scale: Gaussian sub-sampling
@@ -291,6 +291,24 @@ int vpk_sphere_raster_flags(vpk_handle* h, int batch, uint32_t* flags_out);
  * -log10(NFA)) in pixel coordinates of the input image; *n_out = number of segments found (if it exceeds
  * max_segments only the first max_segments were written: call again with a larger buffer).  No GPU involved. */
 int vpk_lsd_detect(const double* image, int width, int height, double scale, double* out, int max_segments, int* n_out);
+/* The same detector for a batch of images on the GPU (csrc/vpk_lsd_gpu.hip).  Per image exactly what vpk_lsd_detect
+ * does: the same rows in the same order, the same argument rules (width, height >= 8 and scale > 0, else VPK_ERR_ARG)
+ * and the same overflow rule; coordinates and -log10(NFA) may differ from the host's in the last bits only, where the
+ * device's atan2 / sin / cos / exp / log differ from the host libm's.
+ *   dims         [host] B x 2 int32: width, height of each image
+ *   pix_offsets  [host] B+1 int64 prefix sums of width * height (offsets of the images in `images`)
+ *   images       concatenated row-major fp64 grey levels 0..255
+ *   out          B x max_segments x 7 fp64: image b's rows start at b * max_segments
+ *   n_out        B int32: image b's segment count (may exceed max_segments: only the first max_segments rows are written)
+ * Asynchronous on the handle's stream; batch = 0 does nothing.  The workspace is kept on the handle and grows on demand;
+ * a batch whose workspace would pass the handle's limit runs in chunks inside the call.  Rows do not depend on the rest
+ * of the batch or on the chunking.  An image with a side beyond 2^20 pixels or more than 2^30 sub-sampled pixels:
+ * VPK_ERR_LIMIT. */
+int vpk_lsd_detect_batch(vpk_handle* h, int batch, const int32_t* dims, const int64_t* pix_offsets, const double* images,
+                         double scale, double* out, int max_segments, int32_t* n_out);
+/* Workspace limit of vpk_lsd_detect_batch in bytes (0 = the default, 4 GiB; about 43 bytes per sub-sampled pixel, so
+ * 8.5 MB for a 640 x 480 image at scale 0.8).  An image larger than the limit runs alone. */
+int vpk_lsd_set_workspace_limit(vpk_handle* h, size_t bytes);
 
 /* ---- EM refinement (vp_localisation.py:168-450) ------------------------------------------------ */
 /* replaces: run_em / run_em_single -> expectation_maximisation (evaluation.py:295-354) for a

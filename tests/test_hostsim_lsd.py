@@ -1,0 +1,94 @@
+"""The GPU line segment detector's PRODUCT arithmetic (csrc/lsd_device.hpp: Gaussian samples with host-made weights,
+gradient, seed bins, region growing, rectangles, refinement, NFA) compiled for the host by tests/hostsim/sim_lsd.cpp and
+run serially with a one-lane wave -- bit for bit the rows of the host detector vpk_lsd_detect (csrc/vpk_lsd.cpp).  The
+kernels' own orchestration (grid-wide passes, the LDS counting sort, the wave-split loops) is what tests/test_gpu_lsd.py
+covers.  Also: the argument checks of lsd.detect_line_segments_batch that need no GPU."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from test_frontend import _render
+from vanishing_points_2017_amd import _lib, lsd
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+SIM_SRC = os.path.join(HERE, "hostsim", "sim_lsd.cpp")
+
+pytestmark = pytest.mark.skipif(not os.path.exists(_lib.SO_PATH), reason="libvpk.so not built")
+
+
+@pytest.fixture(scope="module")
+def sim(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("sim_lsd") / "libvpk_hostsim_lsd.so")
+    # -fno-builtin: g++ merges sin(a) and cos(a) into glibc's sincos, which differs from sin / cos in the last bit of some
+    # arguments; the product's host detector (clang) calls sin and cos
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-builtin", "-fPIC", "-shared", SIM_SRC,
+                           "-o", so])
+    lib = ctypes.CDLL(so)
+    lib.sim_lsd.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_int,
+                            ctypes.POINTER(ctypes.c_int)]
+
+    def run(image, scale):
+        img = np.ascontiguousarray(image, dtype=np.float64)
+        h, w = img.shape
+        cap = 8192
+        out = np.zeros((cap, 7))
+        n = ctypes.c_int(0)
+        assert lib.sim_lsd(img.ctypes.data_as(ctypes.c_void_p), w, h, scale, out.ctypes.data_as(ctypes.c_void_p), cap,
+                           ctypes.byref(n)) == 0
+        assert n.value <= cap
+        return out[:n.value].copy()
+    return run
+
+
+def _strokes(seed, n, h, w, noise):
+    rs = np.random.RandomState(seed)
+    segs = [tuple(rs.uniform(0, [w, h, w, h])) for _ in range(n)]
+    return _render(segs, h, w) + rs.normal(0, noise, (h, w))
+
+
+def _cases():
+    rs = np.random.RandomState(7)
+    true = [(40, 50, 300, 70), (60, 200, 280, 120), (150, 20, 170, 230), (20, 230, 120, 140), (200, 30, 310, 220)]
+    yield "strokes_noise", _render(true, 256, 336) + np.random.RandomState(4).normal(0, 1.5, (256, 336))
+    yield "strokes150_640x480", _strokes(1, 150, 480, 640, 2.0)
+    yield "noise_200", rs.uniform(0, 255, (200, 200))
+    yield "constant", np.full((120, 90), 117.0)
+    yield "min_8x8", rs.uniform(0, 255, (8, 8))
+    yield "odd_9x13", _render([(1, 1, 8, 12)], 13, 9)
+    yield "odd_641x479", _strokes(2, 40, 479, 641, 1.0)
+
+
+CASES = list(_cases())
+
+
+@pytest.mark.parametrize("scale", [0.8, 1.0, 0.5])
+@pytest.mark.parametrize("name", [c[0] for c in CASES])
+def test_device_source_on_the_host_equals_the_host_detector(sim, name, scale):
+    image = dict(CASES)[name]
+    want = lsd.detect_line_segments(image, scale=scale)
+    got = sim(image, scale)
+    assert got.shape == want.shape
+    assert got.tobytes() == want.tobytes(), "rows differ: %s" % np.argwhere(got != want)[:5]
+    if name == "constant":
+        assert want.shape[0] == 0
+    if name.startswith("strokes"):
+        assert want.shape[0] > 20
+
+
+def test_batch_rejects_a_non_2d_image_before_device_work(monkeypatch):
+    def no_handle(device=0):
+        raise AssertionError("device work before the shape check")
+    monkeypatch.setattr(_lib, "get_handle", no_handle)
+    with pytest.raises(ValueError):
+        lsd.detect_line_segments_batch([np.zeros((20, 20)), np.zeros((20, 20, 3))])
+
+
+def test_batch_without_a_gpu_raises_vpk_error(monkeypatch):
+    import torch
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    monkeypatch.setattr(_lib, "_handles", {})
+    with pytest.raises(_lib.VpkError):
+        lsd.detect_line_segments_batch([np.zeros((20, 20))])

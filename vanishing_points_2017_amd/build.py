@@ -25,6 +25,7 @@ UNITS = {
     "vpk_horizon.hip": ["-ffp-contract=off"],
     "vpk_pipeline.hip": [],
     "vpk_lsd.cpp": ["-ffp-contract=off"],      # host code: the front end's line segment detector
+    "vpk_lsd_gpu.hip": ["-ffp-contract=off"],  # the same detector batched on the GPU: the host's roundings (lsd_device.hpp)
 }
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-Wno-unused-result"]

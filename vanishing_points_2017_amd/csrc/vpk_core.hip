@@ -83,6 +83,10 @@ int vpk_destroy(vpk_handle* h) {
     }
     if (h->small_ws) (void)hipFree(h->small_ws);
     if (h->raster_hdr) (void)hipFree(h->raster_hdr);
+    if (h->lsd_ws) (void)hipFree(h->lsd_ws);
+    if (h->lsd_hdr) (void)hipFree(h->lsd_hdr);
+    if (h->lsd_host) (void)hipHostFree(h->lsd_host);
+    if (h->lsd_ev) (void)hipEventDestroy(h->lsd_ev);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return VPK_OK;

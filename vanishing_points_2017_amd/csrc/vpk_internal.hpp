@@ -70,6 +70,17 @@ struct vpk_handle {
     vpk::EmLayout em_sess_layout = {};
     hipEvent_t step_event = nullptr; // vpk_pipeline_step: orders the EM stream behind the CNN stream
     vpk_cnn_state* cnn = nullptr;
+    // vpk_lsd_detect_batch (vpk_lsd_gpu.hip): workspace (grown on demand), header (descriptors + Gaussian weights) and its
+    // pinned staging, reused once the event of the previous call's upload has fired
+    size_t lsd_ws_limit = 0;         // vpk_lsd_set_workspace_limit (0 = the default, 4 GiB)
+    void* lsd_ws = nullptr;
+    size_t lsd_ws_bytes = 0;
+    void* lsd_hdr = nullptr;
+    size_t lsd_hdr_bytes = 0;
+    void* lsd_host = nullptr;
+    size_t lsd_host_bytes = 0;
+    hipEvent_t lsd_ev = nullptr;
+    bool lsd_ev_valid = false;
 };
 
 int vpk_fail(vpk_handle* h, int code, const char* what);

@@ -107,18 +107,25 @@ def get_data_list(source_folder, destination_folder, name, cnn_model_root, cnn_m
     return dataset
 
 
-def create_data_pickles(dataset, update=False, cnn_input_size=250, target_size=None, line_detector=None):
+def create_data_pickles(dataset, update=False, cnn_input_size=250, target_size=None, line_detector=None, lsd_device=None):
     """evaluation.py:121-186.  ``line_detector`` (image_file, target_size) -> (image_rgb, segments N x 4 in the
     reference's normalised coordinates) defaults to this package's front end (frontend.line_detector: the
     reference's `lsdpython` submodule is empty and ImageMagick is an external program, so both are stand-ins --
-    frontend.py says what is pinned and what is not); the pickles are the reference's, rasterised on the GPU."""
-    if line_detector is None:       # this package's own front end (frontend.py: Pillow + the LSD of csrc/vpk_lsd.cpp)
+    frontend.py says what is pinned and what is not); the pickles are the reference's, rasterised on the GPU.
+    ``lsd_device``: detect the segments of every image that needs a pickle in one batch on that GPU
+    (frontend.line_detector_batch) instead of one host call per image; same schema."""
+    if lsd_device is not None and line_detector is not None:
+        raise ValueError("create_data_pickles: give line_detector or lsd_device, not both")
+    todo = [(f, d) for f, d in zip(dataset["image_files"], dataset["pickle_files"]) if update or not os.path.isfile(d)]
+    if lsd_device is not None:
         from . import frontend
-        line_detector = frontend.line_detector
-    for image_file, data_file in zip(dataset["image_files"], dataset["pickle_files"]):
-        if os.path.isfile(data_file) and not update:
-            continue
-        image_rgb, segs = line_detector(image_file, target_size)
+        detected = frontend.line_detector_batch([f for f, _ in todo], target_size, device=lsd_device)
+    else:
+        if line_detector is None:   # this package's own front end (frontend.py: Pillow + the LSD of csrc/vpk_lsd.cpp)
+            from . import frontend
+            line_detector = frontend.line_detector
+        detected = (line_detector(f, target_size) for f, _ in todo)
+    for (image_file, data_file), (image_rgb, segs) in zip(todo, detected):
         segs = np.ascontiguousarray(segs, dtype=np.float64)
         p1 = np.concatenate([segs[:, 0:2], np.ones((segs.shape[0], 1))], 1)
         p2 = np.concatenate([segs[:, 2:4], np.ones((segs.shape[0], 1))], 1)

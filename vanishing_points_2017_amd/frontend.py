@@ -95,3 +95,23 @@ def line_detector(image_file, target_size=None):
     if target_size is not None:
         image_rgb = resize_to_fit(image_rgb, target_size)
     return image_rgb, detect_lsd_lines(rgb2gray(image_rgb))['segments']
+
+
+def _detector_input(grey):
+    """The image detect_lsd_lines hands to its detector."""
+    image = np.asarray(grey).astype('float64')
+    return image * 255 if np.max(image) <= 1 else image
+
+
+def line_detector_batch(image_files, target_size=None, device=0):
+    """line_detector for many files with ONE GPU detector call (lsd.detect_line_segments_batch): reading, resizing and
+    grey conversion stay on the host.  -> the list of (image_rgb, segments) pairs line_detector would return."""
+    rgbs = []
+    for f in image_files:
+        image_rgb = imread(f)
+        if target_size is not None:
+            image_rgb = resize_to_fit(image_rgb, target_size)
+        rgbs.append(image_rgb)
+    greys = [rgb2gray(im) for im in rgbs]
+    raw = lsd.detect_line_segments_batch([_detector_input(g) for g in greys], device=device)
+    return [(im, detect_lsd_lines(g, detector=lambda image, r=r: r)['segments']) for im, g, r in zip(rgbs, greys, raw)]
