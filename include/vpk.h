@@ -294,7 +294,10 @@ int vpk_lsd_detect(const double* image, int width, int height, double scale, dou
 /* The same detector for a batch of images on the GPU (csrc/vpk_lsd_gpu.hip).  Per image exactly what vpk_lsd_detect
  * does: the same rows in the same order, the same argument rules (width, height >= 8 and scale > 0, else VPK_ERR_ARG)
  * and the same overflow rule; coordinates and -log10(NFA) may differ from the host's in the last bits only, where the
- * device's atan2 / sin / cos / exp / log differ from the host libm's.
+ * device's atan2 / sin / cos / exp / log differ from the host libm's.  Everything else -- the
+ * grid-wide passes, the seed order, the wave-split region stage, the chunking -- is pinned bit for bit: under the
+ * portable math policy (vpk_lsd_set_math) the rows equal the host build of the same source byte for byte
+ * (tests/test_gpu_lsd_exact.py).
  *   dims         [host] B x 2 int32: width, height of each image
  *   pix_offsets  [host] B+1 int64 prefix sums of width * height (offsets of the images in `images`)
  *   images       concatenated row-major fp64 grey levels 0..255
@@ -309,6 +312,11 @@ int vpk_lsd_detect_batch(vpk_handle* h, int batch, const int32_t* dims, const in
 /* Workspace limit of vpk_lsd_detect_batch in bytes (0 = the default, 4 GiB; about 43 bytes per sub-sampled pixel, so
  * 8.5 MB for a 640 x 480 image at scale 0.8).  An image larger than the limit runs alone. */
 int vpk_lsd_set_workspace_limit(vpk_handle* h, size_t bytes);
+/* TEST HOOK: the elementary functions vpk_lsd_detect_batch's gradient and region kernels call on this handle.
+ * mode 0 (default) = the device libm, the product's; 1 = the portable functions of csrc/lsd_portable_math.hpp, which
+ * give the host build's bits on the device, so the batch's rows can be compared with the host build byte for byte.
+ * Any other mode: VPK_ERR_ARG.  Not used by any product path. */
+int vpk_lsd_set_math(vpk_handle* h, int mode);
 
 /* ---- EM refinement (vp_localisation.py:168-450) ------------------------------------------------ */
 /* replaces: run_em / run_em_single -> expectation_maximisation (evaluation.py:295-354) for a

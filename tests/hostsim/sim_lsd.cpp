@@ -2,6 +2,8 @@
 // the Gaussian samples, the gradient, the seed bins and the region stage are the product's code, run with glibc's libm and
 // a one-lane wave; only the orchestration around them -- five kernels over a batch on the GPU, the LDS counting sort of
 // lsd_order -- is a serial loop here.  tests/test_hostsim_lsd.py checks it bit for bit against vpk_lsd_detect.
+// sim_lsd_portable is the same with the portable math policy (lsd_portable_math.hpp): the rows the GPU must reproduce
+// byte for byte under vpk_lsd_set_math(h, 1) (tests/test_gpu_lsd_exact.py).
 // It is not a product path: nothing in the package builds, loads or links it.
 #include "../../vanishing_points_2017_amd/csrc/lsd_device.hpp"
 
@@ -19,9 +21,8 @@ struct HostWave {
     double min_d(double v) const { return v; }
 };
 
-}  // namespace
-
-extern "C" int sim_lsd(const double* image, int width, int height, double scale, double* out, int max_segments, int* n_out) {
+template <class M>
+int run(const double* image, int width, int height, double scale, double* out, int max_segments, int* n_out) {
     if (!image || width < 8 || height < 8 || !n_out || max_segments < 0 || (max_segments > 0 && !out) || !(scale > 0.0))
         return -1;
     const Params q = make_params(scale);
@@ -47,7 +48,7 @@ extern "C" int sim_lsd(const double* image, int width, int height, double scale,
     for (int y = 0; y < ys; ++y)
         for (int x = 0; x < xs; ++x) {
             double a;
-            const double g = gradient(img, xs, ys, x, y, q.rho, &a);
+            const double g = gradient<M>(img, xs, ys, x, y, q.rho, &a);
             angles[(size_t)y * xs + x] = a;
             modgrad[(size_t)y * xs + x] = g;
             if (a != NOTDEF && g > max_grad) max_grad = g;
@@ -66,7 +67,18 @@ extern "C" int sim_lsd(const double* image, int width, int height, double scale,
     std::vector<Pt> reg((size_t)xs * ys);
     const HostWave w;
     const double logNT = log_nt(xs, ys);
-    const Region<HostWave> r{w, angles.data(), modgrad.data(), used.data(), reg.data(), xs, ys, logNT};
+    const Region<HostWave, M> r{w, angles.data(), modgrad.data(), used.data(), reg.data(), xs, ys, logNT};
     *n_out = r.detect(order.data(), (int)order.size(), q, min_reg_size(logNT, q.p), out, max_segments);
     return 0;
+}
+
+}  // namespace
+
+extern "C" int sim_lsd(const double* image, int width, int height, double scale, double* out, int max_segments, int* n_out) {
+    return run<Libm>(image, width, height, scale, out, max_segments, n_out);
+}
+
+extern "C" int sim_lsd_portable(const double* image, int width, int height, double scale, double* out, int max_segments,
+                                int* n_out) {
+    return run<Portable>(image, width, height, scale, out, max_segments, n_out);
 }

@@ -7,7 +7,9 @@
 // What the GPU computes differently from the host is only the device libm (ocml): atan2 / sin / cos in the gradient and
 // the region's running angle, exp / log / log10 / pow / sinh in the NFA.  Everything else -- the Gaussian weights (made
 // on the host by gaussian_weights below), sqrt, division, floor / ceil, the integer pixel counts of the NFA, min / max --
-// is exact and identical.  The fp64 sums of the region stage keep the host's order: one wave runs the region stage of
+// is exact and identical.  The elementary functions of the per-pixel and region-stage code go through a math policy M:
+// Libm (the product's, above) or Portable (lsd_portable_math.hpp, test-only), under which device and host give the
+// same bits and the kernels' orchestration is pinned exactly (tests/test_gpu_lsd_exact.py).  The fp64 sums of the region stage keep the host's order: one wave runs the region stage of
 // one image with every lane executing the same sequential code; only order-free work (the per-column pixel counts of
 // rect_nfa and the min / max of region2rect) is split across the lanes.
 #ifndef VPK_LSD_DEVICE_HPP_
@@ -16,6 +18,8 @@
 #include <float.h>
 #include <math.h>
 #include <stdint.h>
+
+#include "lsd_portable_math.hpp"
 
 #ifdef __HIPCC__
 #define LSD_HD __host__ __device__
@@ -37,6 +41,28 @@ constexpr double SIGMA_SCALE = 0.6, QUANT = 2.0, ANG_TH = 22.5, LOG_EPS = 0.0, D
 struct Pt { int x, y; };
 struct Rect {
     double x1, y1, x2, y2, width, x, y, theta, dx, dy, prec, p;
+};
+
+// math policies of the device-side code (the host-only helpers below call glibc directly)
+struct Libm {                                  // the product: ocml on the device, the C library on the host
+    LSD_HD static double atan2(double y, double x) { return ::atan2(y, x); }
+    LSD_HD static double sin(double x) { return ::sin(x); }
+    LSD_HD static double cos(double x) { return ::cos(x); }
+    LSD_HD static double exp(double x) { return ::exp(x); }
+    LSD_HD static double log(double x) { return ::log(x); }
+    LSD_HD static double log10(double x) { return ::log10(x); }
+    LSD_HD static double pow(double x, double y) { return ::pow(x, y); }
+    LSD_HD static double sinh(double x) { return ::sinh(x); }
+};
+struct Portable {                              // test-only: the same bits on both sides
+    LSD_HD static double atan2(double y, double x) { return vpk_pmath::atan2(y, x); }
+    LSD_HD static double sin(double x) { return vpk_pmath::sin(x); }
+    LSD_HD static double cos(double x) { return vpk_pmath::cos(x); }
+    LSD_HD static double exp(double x) { return vpk_pmath::exp(x); }
+    LSD_HD static double log(double x) { return vpk_pmath::log(x); }
+    LSD_HD static double log10(double x) { return vpk_pmath::log10(x); }
+    LSD_HD static double pow(double x, double y) { return vpk_pmath::pow(x, y); }
+    LSD_HD static double sinh(double x) { return vpk_pmath::sinh(x); }
 };
 
 // per-call constants, all made on the host (vpk_lsd.cpp computes them the same way)
@@ -108,6 +134,7 @@ LSD_HD inline double sample(const double* src, int len, long long stride, int c,
 
 // ---- 2. gradient, level-line angle, magnitude of pixel (x, y) of an xs x ys image ---------------------------------------
 // returns the magnitude (0 on the last row / column); *angle = NOTDEF when it is at most rho
+template <class M = Libm>
 LSD_HD inline double gradient(const double* img, int xs, int ys, int x, int y, double rho, double* angle) {
     if (x >= xs - 1 || y >= ys - 1) {
         *angle = NOTDEF;
@@ -118,7 +145,7 @@ LSD_HD inline double gradient(const double* img, int xs, int ys, int x, int y, d
     const double com2 = img[adr + 1] - img[adr + xs];
     const double gx = com1 + com2, gy = com1 - com2;
     const double norm = sqrt((gx * gx + gy * gy) / 4.0);
-    *angle = norm <= rho ? NOTDEF : atan2(gx, -gy);              // level-line angle
+    *angle = norm <= rho ? NOTDEF : M::atan2(gx, -gy);              // level-line angle
     return norm;
 }
 
@@ -163,30 +190,35 @@ LSD_HD inline double angle_diff_signed(double a, double b) {
 LSD_HD inline double angle_diff(double a, double b) { return fabs(angle_diff_signed(a, b)); }
 
 // ---- 7. NFA ---------------------------------------------------------------------------------------------------------
+template <class M>
 LSD_HD inline double log_gamma_lanczos(double x) {
     const double q[7] = {75122.6331530, 80916.6278952, 36308.2951477, 8687.24529705, 1168.92649479, 83.8676043424,
                          2.50662827511};
-    double a = (x + 0.5) * log(x + 5.5) - (x + 5.5);
+    double a = (x + 0.5) * M::log(x + 5.5) - (x + 5.5);
     double b = 0.0;
     for (int n = 0; n < 7; ++n) {
-        a -= log(x + (double)n);
-        b += q[n] * pow(x, (double)n);
+        a -= M::log(x + (double)n);
+        b += q[n] * M::pow(x, (double)n);
     }
-    return a + log(b);
+    return a + M::log(b);
 }
+template <class M>
 LSD_HD inline double log_gamma_windschitl(double x) {
-    return 0.918938533204673 + (x - 0.5) * log(x) - x + 0.5 * x * log(x * sinh(1 / x) + 1 / (810.0 * pow(x, 6.0)));
+    return 0.918938533204673 + (x - 0.5) * M::log(x) - x +
+           0.5 * x * M::log(x * M::sinh(1 / x) + 1 / (810.0 * M::pow(x, 6.0)));
 }
-LSD_HD inline double log_gamma(double x) { return x > 15.0 ? log_gamma_windschitl(x) : log_gamma_lanczos(x); }
+template <class M>
+LSD_HD inline double log_gamma(double x) { return x > 15.0 ? log_gamma_windschitl<M>(x) : log_gamma_lanczos<M>(x); }
 
+template <class M = Libm>
 LSD_HD inline double nfa(int n, int k, double p, double logNT) {
     const double tolerance = 0.1;
     if (n == 0 || k == 0) return -logNT;
-    if (n == k) return -logNT - (double)n * log10(p);
+    if (n == k) return -logNT - (double)n * M::log10(p);
     const double p_term = p / (1.0 - p);
-    const double log1term = log_gamma((double)n + 1.0) - log_gamma((double)k + 1.0) - log_gamma((double)(n - k) + 1.0) +
-                            (double)k * log(p) + (double)(n - k) * log(1.0 - p);
-    double term = exp(log1term);
+    const double log1term = log_gamma<M>((double)n + 1.0) - log_gamma<M>((double)k + 1.0) -
+                            log_gamma<M>((double)(n - k) + 1.0) + (double)k * M::log(p) + (double)(n - k) * M::log(1.0 - p);
+    double term = M::exp(log1term);
     if (double_equal(term, 0.0)) {
         if ((double)k > (double)n * p) return -log1term / LN10_L - logNT;
         return -logNT;
@@ -198,11 +230,11 @@ LSD_HD inline double nfa(int n, int k, double p, double logNT) {
         term *= mult_term;
         bin_tail += term;
         if (bin_term < 1.0) {
-            const double err = term * ((1.0 - pow(mult_term, (double)(n - i + 1))) / (1.0 - mult_term) - 1.0);
-            if (err < tolerance * fabs(-log10(bin_tail) - logNT) * bin_tail) break;
+            const double err = term * ((1.0 - M::pow(mult_term, (double)(n - i + 1))) / (1.0 - mult_term) - 1.0);
+            if (err < tolerance * fabs(-M::log10(bin_tail) - logNT) * bin_tail) break;
         }
     }
-    return -log10(bin_tail) - logNT;
+    return -M::log10(bin_tail) - logNT;
 }
 
 LSD_HD inline double inter_low(double x, double x1, double y1, double x2, double y2) {
@@ -218,8 +250,8 @@ LSD_HD inline double inter_hi(double x, double x1, double y1, double x2, double 
 
 // One image's region stage.  W is the wave the stage runs on: lane() / size() and the reductions sum_int(int),
 // max_d(double), min_d(double) over its lanes (a one-lane wave on the host).  Every lane runs the same sequential code
-// with the same values; loops split over lanes are marked.
-template <class W>
+// with the same values; loops split over lanes are marked.  M: the math policy.
+template <class W, class M = Libm>
 struct Region {
     const W& w;
     const double* angles;
@@ -265,7 +297,7 @@ struct Region {
                 if (isaligned_a(angle(x, y), r.theta, r.prec)) ++alg;
             }
         }
-        return nfa(w.sum_int(pts), w.sum_int(alg), r.p, logNT);
+        return nfa<M>(w.sum_int(pts), w.sum_int(alg), r.p, logNT);
     }
 
     // 4. region growing
@@ -273,7 +305,7 @@ struct Region {
         reg_size = 1;
         reg[0] = Pt{x, y};
         reg_angle = angle(x, y);
-        double sumdx = cos(reg_angle), sumdy = sin(reg_angle);
+        double sumdx = M::cos(reg_angle), sumdy = M::sin(reg_angle);
         use(x, y) = 1;
         for (int i = 0; i < reg_size; ++i) {
             const Pt c = reg[i];
@@ -285,9 +317,9 @@ struct Region {
                         use(xx, yy) = 1;
                         reg[reg_size] = Pt{xx, yy};
                         ++reg_size;
-                        sumdx += cos(a);
-                        sumdy += sin(a);
-                        reg_angle = atan2(sumdy, sumdx);
+                        sumdx += M::cos(a);
+                        sumdy += M::sin(a);
+                        reg_angle = M::atan2(sumdy, sumdx);
                     }
         }
     }
@@ -303,7 +335,7 @@ struct Region {
             Ixy -= ((double)c.x - x) * ((double)c.y - y) * wt;
         }
         const double lambda = 0.5 * (Ixx + Iyy - sqrt((Ixx - Iyy) * (Ixx - Iyy) + 4.0 * Ixy * Ixy));
-        double theta = fabs(Ixx) > fabs(Iyy) ? atan2(lambda - Ixx, Ixy) : atan2(Ixy, lambda - Iyy);
+        double theta = fabs(Ixx) > fabs(Iyy) ? M::atan2(lambda - Ixx, Ixy) : M::atan2(Ixy, lambda - Iyy);
         if (angle_diff(theta, reg_angle) > prec) theta += PI_L;
         return theta;
     }
@@ -320,7 +352,7 @@ struct Region {
         x /= sum;
         y /= sum;
         const double theta = get_theta(reg_size, x, y, reg_angle, prec);
-        const double dx = cos(theta), dy = sin(theta);
+        const double dx = M::cos(theta), dy = M::sin(theta);
         double l_min = 0.0, l_max = 0.0, w_min = 0.0, w_max = 0.0;
         for (int i = w.lane(); i < reg_size; i += w.size()) {              // [split]: min / max are exact
             const Pt c = reg[i];

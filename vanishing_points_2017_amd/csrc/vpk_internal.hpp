@@ -73,6 +73,7 @@ struct vpk_handle {
     // vpk_lsd_detect_batch (vpk_lsd_gpu.hip): workspace (grown on demand), header (descriptors + Gaussian weights) and its
     // pinned staging, reused once the event of the previous call's upload has fired
     size_t lsd_ws_limit = 0;         // vpk_lsd_set_workspace_limit (0 = the default, 4 GiB)
+    int lsd_math = 0;                // vpk_lsd_set_math (test hook): 0 = device libm, 1 = portable math
     void* lsd_ws = nullptr;
     size_t lsd_ws_bytes = 0;
     void* lsd_hdr = nullptr;

@@ -11,6 +11,8 @@
 // The workspace lives on the handle and grows on demand; images are grouped into chunks whose workspace stays under the
 // handle's limit (vpk_lsd_set_workspace_limit).  Each image reads and writes only its own slice, so its rows do not depend
 // on what else is in the batch or on how the batch was chunked.
+// lsd_gradient and lsd_region exist for both math policies of lsd_device.hpp: Libm (the product) and Portable (test-only,
+// vpk_lsd_set_math), under which the rows equal the host build's bit for bit.
 #include "vpk_internal.hpp"
 
 #include <string.h>
@@ -72,6 +74,7 @@ __global__ void __launch_bounds__(PASS_THREADS) lsd_sample_y(const ImgDesc* __re
     }
 }
 
+template <class M>
 __global__ void __launch_bounds__(PASS_THREADS) lsd_gradient(const ImgDesc* __restrict__ desc, const double* __restrict__ images,
                                                              Params q, unsigned char* ws, Meta* meta) {
     const ImgDesc d = desc[blockIdx.y];
@@ -84,7 +87,7 @@ __global__ void __launch_bounds__(PASS_THREADS) lsd_gradient(const ImgDesc* __re
     for (long long i = (long long)blockIdx.x * PASS_THREADS + threadIdx.x; i < total; i += (long long)gridDim.x * PASS_THREADS) {
         const int y = (int)(i / d.xs), x = (int)(i % d.xs);
         double a;
-        const double g = gradient(img, d.xs, d.ys, x, y, q.rho, &a);
+        const double g = gradient<M>(img, d.xs, d.ys, x, y, q.rho, &a);
         ang[i] = a;
         grad[i] = g;
         used[i] = 0;
@@ -197,11 +200,12 @@ struct DevWave {
     }
 };
 
+template <class M>
 __global__ void __launch_bounds__(64) lsd_region(const ImgDesc* __restrict__ desc, Params q, unsigned char* ws, const Meta* meta,
                                                  double* out, int max_segments, int* n_out) {
     const ImgDesc d = desc[blockIdx.x];
     DevWave w;
-    Region<DevWave> r{w, at<double>(ws, d.ang), at<double>(ws, d.grad), at<unsigned char>(ws, d.used), at<Pt>(ws, d.reg),
+    Region<DevWave, M> r{w, at<double>(ws, d.ang), at<double>(ws, d.grad), at<unsigned char>(ws, d.used), at<Pt>(ws, d.reg),
                       d.xs, d.ys, d.logNT};
     const int n = r.detect(at<int>(ws, d.order), meta[blockIdx.x].n_seeds, q, d.min_reg,
                            out + (long long)d.b * max_segments * 7, max_segments);
@@ -215,6 +219,13 @@ extern "C" {
 int vpk_lsd_set_workspace_limit(vpk_handle* h, size_t bytes) {
     if (!h) return VPK_ERR_ARG;
     h->lsd_ws_limit = bytes;
+    return VPK_OK;
+}
+
+int vpk_lsd_set_math(vpk_handle* h, int mode) {
+    if (!h) return VPK_ERR_ARG;
+    if (mode != 0 && mode != 1) return vpk_fail(h, VPK_ERR_ARG, "vpk_lsd_set_math: mode must be 0 or 1");
+    h->lsd_math = mode;
     return VPK_OK;
 }
 
@@ -335,11 +346,19 @@ int vpk_lsd_detect_batch(vpk_handle* h, int batch, const int32_t* dims, const in
                                q, ws);
             hipLaunchKernelGGL(lsd_sample_y, dim3(blocks(max_px), n), dim3(PASS_THREADS), 0, h->stream, ddesc + s, wts, q, ws);
         }
-        hipLaunchKernelGGL(lsd_gradient, dim3(blocks(max_px), n), dim3(PASS_THREADS), 0, h->stream, ddesc + s, images, q, ws,
-                           meta);
+        if (h->lsd_math == 1)
+            hipLaunchKernelGGL(lsd_gradient<Portable>, dim3(blocks(max_px), n), dim3(PASS_THREADS), 0, h->stream, ddesc + s,
+                               images, q, ws, meta);
+        else
+            hipLaunchKernelGGL(lsd_gradient<Libm>, dim3(blocks(max_px), n), dim3(PASS_THREADS), 0, h->stream, ddesc + s,
+                               images, q, ws, meta);
         hipLaunchKernelGGL(lsd_order, dim3(n), dim3(ORDER_THREADS), 0, h->stream, ddesc + s, ws, meta);
-        hipLaunchKernelGGL(lsd_region, dim3(n), dim3(64), 0, h->stream, ddesc + s, q, ws, (const Meta*)meta, out, max_segments,
-                           (int*)n_out);
+        if (h->lsd_math == 1)
+            hipLaunchKernelGGL(lsd_region<Portable>, dim3(n), dim3(64), 0, h->stream, ddesc + s, q, ws, (const Meta*)meta, out,
+                               max_segments, (int*)n_out);
+        else
+            hipLaunchKernelGGL(lsd_region<Libm>, dim3(n), dim3(64), 0, h->stream, ddesc + s, q, ws, (const Meta*)meta, out,
+                               max_segments, (int*)n_out);
         VPK_HIP(h, hipGetLastError());
     }
     return VPK_OK;
