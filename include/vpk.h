@@ -318,6 +318,42 @@ int vpk_lsd_set_workspace_limit(vpk_handle* h, size_t bytes);
  * Any other mode: VPK_ERR_ARG.  Not used by any product path. */
 int vpk_lsd_set_math(vpk_handle* h, int mode);
 
+/* ---- front end: decoded images -> grey levels, detector rows -> lines (csrc/vpk_frontend.hip) --------------------- */
+/* replaces: the host half of the reference's front end around the detector for a batch of decoded images --
+ * `convert -resize SxS` (evaluation.py:141-143; this package's stand-in is Pillow's Image.resize(LANCZOS),
+ * frontend.resize_to_fit) and rgb2gray (evaluation.py:148-150) -- with the grey levels detect_lsd_lines hands to the
+ * detector (evaluation.py:227-236).  Per image: a separable Lanczos fit-resize in Pillow's fixed-point arithmetic (weights
+ * made on the host with the C library's sin, integer passes on the device, the horizontal pass first and clipped to uint8; a
+ * pass whose size is unchanged is skipped) -- byte for byte Pillow's uint8 result -- then
+ *   grey = (((r / 255) * 0.2125 + (g / 255) * 0.7154) + (b / 255) * 0.0721) * 255   (3 channels, left to right, no FMA)
+ *   grey = (g / 255) * 255                                                          (1 channel)
+ * (frontend.rgb2gray rounds the same sum in the order of its BLAS dot: a few ulp apart; csrc/image_device.hpp).
+ *   dims         [host] B x 5 int32: in_w, in_h, channels (1 or 3), out_w, out_h
+ *   in_offsets   [host] B+1 int64 prefix sums of in_w * in_h * channels (byte offsets of the images in `images`)
+ *   images       concatenated row-major interleaved uint8 pixels
+ *   out_offsets  [host] B+1 int64 prefix sums of out_w * out_h (pixel offsets of the images in `grey_out`)
+ *   resized_out  NULL or the resized uint8 images, one after the other (image b at the sum of out_w * out_h * channels
+ *                of the images before it)
+ *   grey_out     fp64 grey levels 0..255: exactly the `images` / `pix_offsets` vpk_lsd_detect_batch takes, with dims
+ *                (out_w, out_h)
+ * Channels other than 1 or 3, a side < 1 or offsets that disagree with dims: VPK_ERR_ARG; a side beyond 2^20:
+ * VPK_ERR_LIMIT.  Asynchronous on the handle's stream; batch = 0 does nothing. */
+int vpk_image_prepare_batch(vpk_handle* h, int batch, const int32_t* dims, const int64_t* in_offsets, const uint8_t* images,
+                            const int64_t* out_offsets, uint8_t* resized_out, double* grey_out);
+/* replaces: the arithmetic after the detector in detect_lsd_lines (evaluation.py:237-251: centre, divide by half of the
+ * long side, y up) and the homogeneous lines of create_data_pickles (evaluation.py:161-168: np.cross((x1, y1, 1),
+ * (x2, y2, 1))) -- the same fp64 operations, each rounded on its own, so the results equal numpy's byte for byte.
+ *   dims          [host] B x 2 int32: width, height of the image each detector row belongs to (vpk_lsd_detect_batch's dims)
+ *   rows          B x max_segments x 7 fp64: vpk_lsd_detect_batch's `out`
+ *   line_offsets  [host] B+1 int64 prefix sums of the images' segment counts (vpk_lsd_detect_batch's n_out); a count
+ *                 above max_segments: VPK_ERR_ARG -- those rows were not written: detect again with a larger buffer
+ *   lp_out        sum(N) x 4 fp64 (x1, y1, x2, y2) normalised segments, vpk_em_batch's `lp`
+ *   l_out         sum(N) x 3 fp64 homogeneous lines, vpk_sphere_raster's / vpk_em_batch's `l`
+ *   nfa_out       sum(N) fp64 -log10(NFA)
+ * Each output may be NULL (not written).  Asynchronous on the handle's stream; batch = 0 does nothing. */
+int vpk_lsd_rows_to_lines(vpk_handle* h, int batch, const int32_t* dims, const double* rows, int max_segments,
+                          const int64_t* line_offsets, double* lp_out, double* l_out, double* nfa_out);
+
 /* ---- EM refinement (vp_localisation.py:168-450) ------------------------------------------------ */
 /* replaces: run_em / run_em_single -> expectation_maximisation (evaluation.py:295-354) for a
  * batch of images.  One workgroup runs the whole EM of one image; images are independent.

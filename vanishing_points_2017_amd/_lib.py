@@ -67,6 +67,7 @@ EXPORTS = [
     "vpk_sphere_raster", "vpk_sphere_raster_flags", "vpk_sphere_raster_set_alternative", "vpk_em_batch", "vpk_em_workspace_bytes", "vpk_pairwise", "vpk_init_vps",
     "vpk_estep", "vpk_weight_matrix", "vpk_mstep", "vpk_line_counts", "vpk_cluster2", "vpk_horizon_batch", "vpk_lsd_detect",
     "vpk_lsd_detect_batch", "vpk_lsd_set_workspace_limit", "vpk_lsd_set_math",
+    "vpk_image_prepare_batch", "vpk_lsd_rows_to_lines",
     "vpk_pipeline_step", "vpk_build_records", "vpk_record_width", "vpk_math_probe",
 ]
 
@@ -147,6 +148,8 @@ def load():
                                          c_void]
     lib.vpk_lsd_set_workspace_limit.argtypes = [c_void, ctypes.c_size_t]
     lib.vpk_lsd_set_math.argtypes = [c_void, ctypes.c_int]
+    lib.vpk_image_prepare_batch.argtypes = [c_void, ctypes.c_int, c_void, c_void, c_void, c_void, c_void, c_void]
+    lib.vpk_lsd_rows_to_lines.argtypes = [c_void, ctypes.c_int, c_void, c_void, ctypes.c_int, c_void, c_void, c_void, c_void]
     _lib = lib
     return lib
 

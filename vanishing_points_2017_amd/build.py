@@ -26,6 +26,7 @@ UNITS = {
     "vpk_pipeline.hip": [],
     "vpk_lsd.cpp": ["-ffp-contract=off"],      # host code: the front end's line segment detector
     "vpk_lsd_gpu.hip": ["-ffp-contract=off"],  # the same detector batched on the GPU: the host's roundings (lsd_device.hpp)
+    "vpk_frontend.hip": ["-ffp-contract=off"], # images -> grey levels, rows -> lines: numpy's roundings (image_device.hpp)
 }
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-Wno-unused-result"]

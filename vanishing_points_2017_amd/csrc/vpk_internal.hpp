@@ -12,6 +12,16 @@
 
 struct vpk_cnn_state;   // vpk_cnn.hip
 
+// a device header uploaded through pinned staging: the staging is reused once the event of the previous upload has fired
+struct vpk_staged {
+    void* host = nullptr;
+    size_t host_bytes = 0;
+    void* dev = nullptr;
+    size_t dev_bytes = 0;
+    hipEvent_t ev = nullptr;
+    bool ev_valid = false;
+};
+
 struct vpk_handle {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -82,6 +92,11 @@ struct vpk_handle {
     size_t lsd_host_bytes = 0;
     hipEvent_t lsd_ev = nullptr;
     bool lsd_ev_valid = false;
+    // vpk_image_prepare_batch / vpk_lsd_rows_to_lines (vpk_frontend.hip): headers (descriptors + Lanczos weights) and the
+    // horizontal pass's uint8 intermediate (grown on demand)
+    vpk_staged fe_prep, fe_rows;
+    void* fe_ws = nullptr;
+    size_t fe_ws_bytes = 0;
 };
 
 int vpk_fail(vpk_handle* h, int code, const char* what);

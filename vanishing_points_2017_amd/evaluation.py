@@ -107,16 +107,34 @@ def get_data_list(source_folder, destination_folder, name, cnn_model_root, cnn_m
     return dataset
 
 
-def create_data_pickles(dataset, update=False, cnn_input_size=250, target_size=None, line_detector=None, lsd_device=None):
+def create_data_pickles(dataset, update=False, cnn_input_size=250, target_size=None, line_detector=None, lsd_device=None,
+                        frontend_device=None):
     """evaluation.py:121-186.  ``line_detector`` (image_file, target_size) -> (image_rgb, segments N x 4 in the
     reference's normalised coordinates) defaults to this package's front end (frontend.line_detector: the
     reference's `lsdpython` submodule is empty and ImageMagick is an external program, so both are stand-ins --
     frontend.py says what is pinned and what is not); the pickles are the reference's, rasterised on the GPU.
     ``lsd_device``: detect the segments of every image that needs a pickle in one batch on that GPU
-    (frontend.line_detector_batch) instead of one host call per image; same schema."""
-    if lsd_device is not None and line_detector is not None:
-        raise ValueError("create_data_pickles: give line_detector or lsd_device, not both")
+    (frontend.line_detector_batch) instead of one host call per image; same schema.
+    ``frontend_device``: everything after decoding -- resize, grey levels, detector, lines and sphere raster -- in one
+    batch on that GPU (frontend.lines_batch_device); same schema."""
+    if sum(x is not None for x in (line_detector, lsd_device, frontend_device)) > 1:
+        raise ValueError("create_data_pickles: give at most one of line_detector, lsd_device and frontend_device")
     todo = [(f, d) for f, d in zip(dataset["image_files"], dataset["pickle_files"]) if update or not os.path.isfile(d)]
+    if frontend_device is not None and cnn_input_size is None:
+        raise ValueError("create_data_pickles: frontend_device needs cnn_input_size (the size of the sphere raster)")
+    if frontend_device is not None:
+        from . import frontend
+        if not todo:
+            return
+        r = frontend.lines_batch_device([frontend.imread(f) for f, _ in todo], target_size, device=frontend_device,
+                                        cnn_input_size=cnn_input_size, keep_resized=True)
+        lp, l, sphere, offs = r["lp"].cpu().numpy(), r["l"].cpu().numpy(), r["sphere"].cpu().numpy(), r["offsets"]
+        for k, ((image_file, data_file), image_rgb) in enumerate(zip(todo, r["images"])):
+            lo, hi = int(offs[k]), int(offs[k + 1])
+            datum = {"dataset": dataset["name"], "image_file": image_file, "image_shape": image_rgb.shape[:2],
+                     "image": image_rgb, "line_segments": lp[lo:hi].copy(), "lines": l[lo:hi].copy()}    # :161-168
+            _dump_pickle({'lines': datum, 'sphere_image': sphere[k].copy()}, data_file)                 # :175
+        return
     if lsd_device is not None:
         from . import frontend
         detected = frontend.line_detector_batch([f for f, _ in todo], target_size, device=lsd_device)

@@ -20,7 +20,8 @@ def run_folder(args):
                                        distance_measure='angle', use_weights=True, do_split=True, do_merge=True,
                                        update=True)                                   # example.py:30-34
     evaluation.create_data_pickles(dataset, update=True, cnn_input_size=500, target_size=640,       # :37
-                                   lsd_device=args.gpu if args.lsd == 'gpu' else None)
+                                   lsd_device=args.gpu if args.lsd == 'gpu' else None,
+                                   frontend_device=args.gpu if args.lsd == 'gpu-frontend' else None)
     if all(os.path.isfile(f) for f in (config.cnn_weights_path, config.cnn_mean_path)):
         evaluation.run_cnn(dataset, mean_file=config.cnn_mean_path, model_def=config.cnn_config_path,
                            model_weights=config.cnn_weights_path, gpu=args.gpu, range_policy=args.cnn_range)   # :38
@@ -58,8 +59,9 @@ def main(argv=None):
     p.add_argument('--destination_folder', default='/tmp/vp_example_results')
     p.add_argument('--cnn-range', dest='cnn_range', choices=['raise', 'recompute_exact'], default='raise',
                    help='CNN range policy: raise on a clamped fp16-pair activation, or recompute those images exactly')
-    p.add_argument('--lsd', choices=['host', 'gpu'], default='host',
-                   help='line segment detector of --source_folder: per image on the host, or all images in one GPU batch')
+    p.add_argument('--lsd', choices=['host', 'gpu', 'gpu-frontend'], default='host',
+                   help='line segment detector of --source_folder: per image on the host, all images in one GPU batch, '
+                        'or the whole front end after decoding (resize, grey, detector, lines, raster) on the GPU')
     args = p.parse_args(argv)
     if args.source_folder:
         return run_folder(args)
