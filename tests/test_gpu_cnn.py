@@ -464,3 +464,42 @@ def test_range_guard_reports_a_clamped_activation_and_never_lets_a_nan_out(layer
         net.set_activation_scales(good)
     assert np.array_equal(net.forward(sphere), first)
     assert net.range_flags() == 0
+
+
+def test_a_failed_load_leaves_the_model_unloaded_and_the_handle_usable():
+    """vpk_cnn_load with weights that make its calibration fail: a blob of the calibration forwards is not finite -> VPK_ERR_RANGE,
+    and the model stays unloaded (vpk_cnn_forward refuses with "before vpk_cnn_load").  A valid load on the same handle then
+    computes the bits a fresh handle computes.
+    The poison is +inf among conv3's weights.  A NaN does not fail a load, in conv1 or anywhere else (measured: conv1 NaN, conv1 +inf
+    and conv3 NaN all load): every calibrated blob lies behind a ReLU written as a compare or v_med3, which turns NaN into 0, and
+    conv1's +inf becomes NaN in its LRN.  conv3's blob is tapped right behind its ReLU, where +inf times a positive pool2 value stays."""
+    import ctypes
+    from vanishing_points_2017_amd import cnn, runtime, sphere_mapping, synth
+    from vanishing_points_2017_amd._lib import VPK_ERR_RANGE, VpkError
+    w = cnn.synthetic_weights(0)
+    mean = cnn.synthetic_mean(0)
+    sphere = sphere_mapping.raster_batch([synth.make_scene(7100 + i, 120 + 30 * i, 3)["l"] for i in range(2)])
+    rt = runtime.Runtime(0)                       # handles of this test's own: nothing else has loaded a model on them
+    poisoned = dict(w)
+    w3 = w["conv3"][0].copy()
+    w3[5, 7, 1, 1] = np.inf
+    poisoned["conv3"] = (w3, w["conv3"][1])
+    with pytest.raises(VpkError) as ei:
+        cnn.Net(poisoned, mean, runtime=rt)
+    assert "libvpk error %d" % VPK_ERR_RANGE in str(ei.value) and "not finite" in str(ei.value)
+    d = rt.torch.from_numpy(sphere).to(rt.tdev)
+    out = rt.torch.empty((2, 20, 20), dtype=rt.torch.float32, device=rt.tdev)
+    rc = rt.lib.vpk_cnn_forward(rt.h, rt.ptr(d), 2, rt.ptr(out))
+    assert rc == -4 and b"before vpk_cnn_load" in rt.lib.vpk_last_error(rt.h)        # VPK_ERR_STATE
+    scales = (ctypes.c_float * 6)()
+    assert rt.lib.vpk_cnn_get_activation_scales(rt.h, scales) == -4
+    assert rt.lib.vpk_cnn_set_algorithm(rt.h, 2) == -4
+    net = cnn.Net(w, mean, runtime=rt)            # the same handle, loaded properly
+    fresh = cnn.Net(w, mean, runtime=runtime.Runtime(0))
+    assert np.array_equal(net.activation_scales(), fresh.activation_scales())
+    for alg in (4, 2):
+        net.set_algorithm(alg)
+        fresh.set_algorithm(alg)
+        got, want = net.forward(sphere), fresh.forward(sphere)
+        assert np.isfinite(want).all()
+        assert np.array_equal(got, want), alg

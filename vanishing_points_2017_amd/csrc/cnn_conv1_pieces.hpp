@@ -1,5 +1,5 @@
 // cnn_conv1_pieces.hpp -- conv1 + relu1 + norm1 + pool1 (cnn/deploy.prototxt:9-55) on the bf16 matrix cores with EXACT
-// operands.  Included by vpk_cnn.hip (after cnn_split_gemm.hpp: bf16x8, lds_barrier, C1_* / C1D_LD constants).
+// operands.  Included by vpk_cnn.hip (after cnn_split_gemm.hpp: bf16x8; cnn_conv1_direct.hpp: lds_barrier, C1D_LD; cnn_gemm_f32.hpp: C1_* constants).
 //
 // conv1's input is an 8-bit raster (evaluation.py:34-38: float(image) - mean, no scaling).  An integer 0..255 IS a bf16
 // number (8 significant bits), every f32 weight is exactly the sum of three bf16 pieces (cnn_split_gemm.hpp), a product of
@@ -47,12 +47,44 @@ typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) const u32x2 lds_cu32x2;
 
+// max |w| -> the power of two that puts it in [2^13, 2^14): the scale of a layer's fp16-pair weights (1 for all-zero weights)
+inline float weight_scale_pow2(const float* w, size_t n) {
+    float wmax = 0.f;
+    for (size_t i = 0; i < n; ++i) wmax = std::max(wmax, std::fabs(w[i]));
+    int ex = 0;
+    if (wmax > 0.f) (void)std::frexp(wmax, &ex);               // wmax = f 2^ex, f in [0.5, 1)
+    return std::ldexp(1.f, wmax > 0.f ? 14 - ex : 0);
+}
+
+// The NP pieces of one weight as the device would split it: NP = 3 the bf16 triple of split3() (cnn_split_gemm.hpp), NP = 2 the
+// fp16 pair of split2h() (cnn_pairs.hpp; the caller has scaled the weight).  Piece q goes to p[q * stride].
+template <int NP>
+inline void weight_pieces(float w, unsigned short* p, size_t stride) {
+    if constexpr (NP == 2) {
+        const _Float16 h0 = (_Float16)w;
+        const _Float16 h1 = (_Float16)(w - (float)h0);
+        memcpy(p, &h0, 2);
+        memcpy(p + stride, &h1, 2);
+    } else {
+        auto rne = [](float x) { unsigned b; memcpy(&b, &x, 4); return (b + 0x7fffu + ((b >> 16) & 1u)) & 0xffff0000u; };
+        const unsigned b0 = rne(w);
+        float f0; memcpy(&f0, &b0, 4);
+        const float r1 = w - f0;
+        const unsigned b1 = rne(r1);
+        float f1; memcpy(&f1, &b1, 4);
+        const float r2 = r1 - f1;
+        unsigned b2; memcpy(&b2, &r2, 4);
+        p[0] = (unsigned short)(b0 >> 16);
+        p[stride] = (unsigned short)(b1 >> 16);
+        p[2 * stride] = (unsigned short)(b2 >> 16);
+    }
+}
+
 // [m tile 6][K step 6][piece 3][lane 64][8] bf16: the A operand of v_mfma_f32_16x16x32_bf16 for output channels
 // 16 mt + lane % 16, k = 8 (lane / 16) + e -> kernel row 2 s + (lane / 32), tap 8 ((lane / 16) % 2) + e (zero beyond 10)
 // np = 2: scaled fp16 pairs instead (cnn_conv_pieces.hpp; the raster's integers are exact fp16 numbers too): x scale, two pieces
 inline void conv1_pieces_weights(const float* w, std::vector<unsigned short>& out, int np = 3, float scale = 1.f) {
     out.assign((size_t)6 * C1B_STEPS * np * 64 * 8, 0);
-    auto rne = [](float x) { unsigned b; memcpy(&b, &x, 4); return (b + 0x7fffu + ((b >> 16) & 1u)) & 0xffff0000u; };
     for (int mt = 0; mt < 6; ++mt)
         for (int s = 0; s < C1B_STEPS; ++s)
             for (int ln = 0; ln < 64; ++ln)
@@ -60,27 +92,32 @@ inline void conv1_pieces_weights(const float* w, std::vector<unsigned short>& ou
                     const int q = ln >> 4, kh = 2 * s + (q >> 1), kw = 8 * (q & 1) + e, oc = 16 * mt + (ln & 15);
                     if (kh > 10 || kw > 10) continue;
                     const float x = w[(size_t)oc * 121 + kh * 11 + kw];
-                    if (np == 2) {
-                        const float xs = x * scale;
-                        const _Float16 h0 = (_Float16)xs;
-                        const _Float16 h1 = (_Float16)(xs - (float)h0);
-                        const size_t at2 = ((((size_t)mt * C1B_STEPS + s) * 2) * 64 + ln) * 8 + e;
-                        memcpy(&out[at2], &h0, 2);
-                        memcpy(&out[at2 + 512], &h1, 2);
-                        continue;
-                    }
-                    const unsigned b0 = rne(x);                    // the three pieces of split3() (cnn_split_gemm.hpp)
-                    float f0; memcpy(&f0, &b0, 4);
-                    const float r1 = x - f0;
-                    const unsigned b1 = rne(r1);
-                    float f1; memcpy(&f1, &b1, 4);
-                    const float r2 = r1 - f1;
-                    unsigned b2; memcpy(&b2, &r2, 4);
-                    const size_t at = ((((size_t)mt * C1B_STEPS + s) * 3) * 64 + ln) * 8 + e;
-                    out[at] = (unsigned short)(b0 >> 16);
-                    out[at + 512] = (unsigned short)(b1 >> 16);
-                    out[at + 1024] = (unsigned short)(b2 >> 16);
+                    unsigned short* at = &out[((((size_t)mt * C1B_STEPS + s) * np) * 64 + ln) * 8 + e];
+                    if (np == 2) weight_pieces<2>(x * scale, at, 512);
+                    else weight_pieces<3>(x, at, 512);
                 }
+}
+
+// conv2..5 (Caffe's [G * OC][IC][KH][KH]) as NP pieces per weight in the A-fragment order of the 32 x 32 x 16 matrix instructions, as
+// conv_gemm_split_kernel and conv_pieces_kernel stream them: [group][K step][32-row block of `mblocks`][piece][lane 64][8], K step =
+// (16-channel group, tap), lane = row of the block + 32 x (k half), e = channel within the half; rows beyond OC are zeros.
+// NP = 2: the weights are multiplied by `scale` (weight_scale_pow2) first.
+template <int NP>
+inline void pack_conv_fragments(const float* w, int G, int OC, int IC, int KH, int mblocks, float scale, std::vector<unsigned short>& out) {
+    const int ntaps = KH * KH, ksteps = ntaps * (IC / 16);
+    out.assign((size_t)G * ksteps * mblocks * NP * 512, 0);
+    for (int g = 0; g < G; ++g)
+        for (int s = 0; s < ksteps; ++s)
+            for (int mb = 0; mb < mblocks; ++mb)
+                for (int ln = 0; ln < 64; ++ln)
+                    for (int e = 0; e < 8; ++e) {
+                        const int m = mb * 32 + (ln & 31);
+                        const int tap = s % ntaps, c = (s / ntaps) * 16 + 8 * (ln >> 5) + e;
+                        float x = 0.f;
+                        if (m < OC) x = w[((size_t)(g * OC + m) * IC + c) * ntaps + tap];
+                        if constexpr (NP == 2) x *= scale;
+                        weight_pieces<NP>(x, &out[((((size_t)g * ksteps + s) * mblocks + mb) * NP) * 512 + (size_t)ln * 8 + e], 512);
+                    }
 }
 
 // cmap[oh][ow][oc] = bias[oc] - sum_k w[oc][k] mean[4 oh + kh][4 ow + kw], in float64, rounded once

@@ -69,7 +69,7 @@ struct PieceDims {
 // bf16 triples, for a product that is within 8 x 2^-24 of exact in the worst case and 2^-24 in the median
 // (tests/test_split_precision_math.py) where an f32 FMA chain rounds every partial sum to 2^-24 of ITS magnitude.  fp16's exponent range is what needs care, and powers of two take care of it (exactly):
 //   * weights: x 2^k per layer, the largest in [2^13, 2^14): every weight down to 2^-17 of the largest keeps a normal second piece;
-//   * activations: x a power of two per CONSUMING layer, fixed at load by a calibration forward (vpk_cnn.hip: calibrate): the layer's
+//   * activations: x a power of two per CONSUMING layer, fixed at load by a calibration forward (cnn_calibrate.hpp: calibrate): the layer's
 //     input blob for a synthetic raster, computed by the f32 direct kernels, is brought to a maximum in [64, 128).  The pair misses
 //     the scaled value x by at most max(2^-23 |x|, 2^-25) (tests/test_split_precision_math.py): full precision from 2^-8 to 2^+9 of
 //     the calibration maximum; below, the second piece is a denormal -- the matrix cores multiply fp16 denormals, measured with

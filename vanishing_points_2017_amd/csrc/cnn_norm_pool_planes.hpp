@@ -3,7 +3,7 @@
 // in piece planes (cnn_conv_pieces.hpp) -- or the f32 planes when a caller taps pool2.  Included by vpk_cnn.hip after
 // cnn_conv_pieces.hpp (split2h).
 //
-// Same walk as lrn5_pool3s2_stream_kernel (vpk_cnn.hip): a workgroup owns TPH pooled rows x the whole width of one image -- in an
+// Same walk as lrn5_pool3s2_stream_kernel (cnn_norm_pool.hpp): a workgroup owns TPH pooled rows x the whole width of one image -- in an
 // unpadded NCHW plane one contiguous run of (2 TPH + 1) W floats per channel -- and a range of channels; a thread keeps the 5-deep
 // raw window of its (up to four) pixels in registers, every raw value is read once, fully coalesced; the normalised planes of a
 // batch of channels go to LDS (double buffered, one barrier per batch).  What differs (round 5):

@@ -1,5 +1,5 @@
 // cnn_winograd.hpp -- conv3 / conv4 / conv5 of cnn/deploy.prototxt (:104-174: 3 x 3, stride 1, pad 1, 30 x 30 planes) by
-// Winograd's minimal filtering F(2 x 2, 3 x 3) on the f32 matrix cores.  Included by vpk_cnn.hip (uses its DMA helpers).
+// Winograd's minimal filtering F(2 x 2, 3 x 3) on the f32 matrix cores.  Included by vpk_cnn.hip (uses cnn_gemm_f32.hpp's DMA helpers).
 //
 // A 2 x 2 block of outputs of one channel is  Y = A^T [ (G g G^T) (.) (B^T d B) ] A  with d the 4 x 4 input patch, g the 3 x 3
 // filter and (.) the element-wise product summed over the input channels: 16 multiplications per input channel instead
