@@ -211,7 +211,8 @@ int vpk_cnn_forward_tap_f32(vpk_handle* h, const float* image, int batch, float*
 /* How the net's layers are computed.  The reference runs Caffe in fp32 (deploy.prototxt, evaluation.py:20: cuDNN's pick of
  * algorithm per layer); every setting below keeps f32 operands, f32 accumulation and f32 results -- what changes is which matrix
  * instruction multiplies, in how many pieces the operands reach it, and where the sums are rounded.  Each setting's error against the SAME net evaluated in float64 is
- * measured by tests/test_gpu_cnn.py; the defaults are, at every tap, no further from it than the f32-input direct kernels.
+ * measured by tests/test_gpu_cnn.py and tests/test_gpu_cnn_modes.py; the defaults are, at every tap, no further from it than the
+ * f32-input direct kernels.
  *
  * conv1 + relu1 + norm1 + pool1 (deploy.prototxt:9-55):
  *   3 (default)  ONE kernel on the bf16 matrix cores with EXACT operands: the uint8 raster is one bf16 piece, each weight the sum
@@ -219,6 +220,9 @@ int vpk_cnn_forward_tap_f32(vpk_handle* h, const float* image, int batch, float*
  *                product, none of them rounded (csrc/cnn_conv1_pieces.hpp).  The 96 x 123 x 123 conv1 blob is never written.
  *   4            the same kernel with the weights as scaled fp16 PAIRS (two products: the raster's integers are exact fp16 numbers too);
  *                no faster -- the kernel is bound by its LDS epilogue, not by the matrix pipe (0.366 against 0.375 ms) -- and not the default
+ *                (22 of the weights' 24 bits: at pool1 it meets the factor-1 rule against mode 1 -- 2.4e-7 against 5.9e-7 of the blob's
+ *                scale --, and so does the output under vpk_cnn_set_algorithm(4); the output under algorithm 0 is NOT held to
+ *                factor 1, only to 2e-5: the f32 chains behind it dominate, measured 1.03 x mode 1's; tests/test_gpu_cnn_modes.py)
  *   1            ONE kernel on the f32-input matrix instructions (v_mfma_f32_16x16x4_f32: an f32 FMA chain over the 121 taps)
  *   2            the implicit-GEMM kernel with the fused LRN / pooling epilogue
  *   0            separate conv1 and LRN / pooling kernels (also used whenever tap 0 is requested) */
@@ -226,7 +230,11 @@ int vpk_cnn_set_fusion(vpk_handle* h, int mode);
 /* Arithmetic of conv2..conv5 (deploy.prototxt:56-174) when vpk_cnn_set_algorithm is 0:
  *   0 (default)  f32-input matrix instructions (v_mfma_f32_32x32x2_f32): bit-for-bit an f32 FMA chain per output
  *   1            every f32 operand as the exact sum of three bf16 pieces, six bf16 matrix products per f32 product
- *                (everything above 2^-24 of the product), f32 accumulation, implicit GEMM (csrc/cnn_split_gemm.hpp) */
+ *                (everything above 2^-24 of the product), f32 accumulation, implicit GEMM (csrc/cnn_split_gemm.hpp); per layer
+ *                the faster of its two tilings (conv2 / conv3: two 4-wave workgroups per CU, conv5: one 8-wave workgroup)
+ *   2, 3         (development) as 1, but force one tiling of the split GEMM for every layer: 2 = one 8-wave workgroup per CU,
+ *                3 = two 4-wave workgroups per CU (conv4 has one tiling only).  The same arithmetic as 1.
+ * Any other value: VPK_ERR_ARG. */
 int vpk_cnn_set_precision(vpk_handle* h, int mode);
 /* Algorithm of conv2..conv5 and fc6 (precision 0):
  *   4  (default) DIRECT convolutions (and fc6's weight stream) on the fp16 matrix cores, every f32 operand as a SCALED PAIR of fp16

@@ -658,7 +658,7 @@ int vpk_cnn_set_algorithm(vpk_handle* h, int mode) {
 
 int vpk_cnn_set_precision(vpk_handle* h, int mode) {
     if (!h || !h->cnn) return vpk_fail(h, VPK_ERR_STATE, "vpk_cnn_set_precision before vpk_cnn_load");
-    if (mode < 0 || mode > 3) return vpk_fail(h, VPK_ERR_ARG, "vpk_cnn_set_precision: mode must be 0 or 1");
+    if (mode < 0 || mode > 3) return vpk_fail(h, VPK_ERR_ARG, "vpk_cnn_set_precision: mode must be 0 .. 3");
     cnn_config_set_precision(h->cnn->cfg, mode);       // 2, 3: force one tiling for every layer (development)
     return VPK_OK;
 }
