@@ -23,7 +23,13 @@ A one-ulp input change stands for what any other implementation of exp / acos / 
 (tests/test_gpu_math.py measures the device's: up to 1-2 ulp, a few per cent of the arguments).  The test
 (tests/test_gpu_full_configs.py) exempts an image from the full bar only if its certificate says `unstable`.
 
+With --keywords NAME the runs use the keywords of that row of make_keyword_goldens.SETTINGS (a supplied init_vp included) and
+the certificates go to tests/golden/instability_keywords.npz, which has the same fields plus `setting` (the row's label): the
+cases of tests/golden/full_config_keywords.npz on which the reference's answer moves under those keywords.  --jobs J runs the
+perturbed copies in J worker processes (a 99-iteration run of a 662-line image takes minutes).
+
 Usage:  python oracle/make_instability_certificates.py [--trials T] [--all T2] [--from gpurun_out/parity_failures.json] [cfg:idx ...]
+        (and, in front of the images: [--keywords NAME] [--jobs J])
 """
 import json
 import os
@@ -43,23 +49,42 @@ from make_golden import reference_raster  # noqa: E402
 from ref_instability import perturbations  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden", "instability.npz")
+OUT_KEYWORDS = os.path.join(ROOT, "tests", "golden", "instability_keywords.npz")
 FIELDS = ("config", "index", "trials", "trials_all", "iterations", "max_vp_move", "max_assoc_flips", "iterations_stable", "num_vp_stable",
           "unstable")
 
 
-def certify(mods, cfg, idx, trials, trials_all=0):
+def _reference_run(args):
+    """One run of the reference (in a worker process under --jobs): (cfg, idx, setting label or None, lp)."""
     import joblib
-    vpl = mods["vp_localisation"]
+    cfg, idx, setting, lp = args
+    warnings.filterwarnings("ignore")
+    mods = load_reference()
     sc = next(synth.config_scenes(cfg, count=1, start=idx))
+    kw = {}
+    if setting is not None:
+        from make_keyword_goldens import SETTINGS, em_kwargs
+        kw = em_kwargs(dict(SETTINGS)[setting], cfg, idx)
     sphere = reference_raster(mods["sphere_mapping"], sc["l"])
+    with joblib.parallel_backend("multiprocessing"):
+        r = mods["vp_localisation"].expectation_maximisation(sc["l"].copy(), lp.copy(), sc["cnn_response"].copy(),
+                                                              sphere_image=sphere, **kw)
+    return {k: r[k] for k in ("iterations", "vp", "vp_assoc")}
 
-    def run(lp):
-        with joblib.parallel_backend("multiprocessing"):
-            return vpl.expectation_maximisation(sc["l"].copy(), lp.copy(), sc["cnn_response"].copy(), sphere_image=sphere)
-    base = run(sc["lp"])
+
+def certify(cfg, idx, trials, trials_all=0, setting=None, jobs=1):
+    from concurrent.futures import ProcessPoolExecutor
+    sc = next(synth.config_scenes(cfg, count=1, start=idx))
+    moved = list(perturbations(sc["lp"], trials, seed=idx, trials_all=trials_all))
+    todo = [(cfg, idx, setting, sc["lp"])] + [(cfg, idx, setting, q) for _, _, q in moved]
+    if jobs > 1:
+        with ProcessPoolExecutor(max_workers=jobs) as pool:
+            runs = list(pool.map(_reference_run, todo))
+    else:
+        runs = [_reference_run(t) for t in todo]
+    base = runs[0]
     move, flips, it_ok, nv_ok = 0.0, 0, True, True
-    for i, j, q in perturbations(sc["lp"], trials, seed=idx, trials_all=trials_all):
-        r = run(q)
+    for (i, j, _), r in zip(moved, runs[1:]):
         it_ok &= r["iterations"] == base["iterations"]
         same = r["vp"].shape == base["vp"].shape
         nv_ok &= same
@@ -76,31 +101,38 @@ def certify(mods, cfg, idx, trials, trials_all=0):
 
 def main(argv):
     warnings.filterwarnings("ignore")
-    trials, trials_all, todo = 6, 0, []
+    trials, trials_all, todo, setting, jobs = 6, 0, [], None, 1
     while argv:
         a = argv.pop(0)
         if a == "--trials":
             trials = int(argv.pop(0))
         elif a == "--all":
             trials_all = int(argv.pop(0))
+        elif a == "--keywords":
+            setting = argv.pop(0)
+        elif a == "--jobs":
+            jobs = int(argv.pop(0))
         elif a == "--from":
             for cfg, lst in json.load(open(argv.pop(0))).items():
                 todo += [(int(cfg), int(i)) for i in lst]
         else:
             cfg, idx = a.split(":")
             todo.append((int(cfg), int(idx)))
+    out, fields = (OUT, FIELDS) if setting is None else (OUT_KEYWORDS, FIELDS + ("setting",))
     have = {}
-    if os.path.isfile(OUT):
-        g = np.load(OUT)
+    if os.path.isfile(out):
+        g = np.load(out)
         for k in range(len(g["config"])):
-            have[(int(g["config"][k]), int(g["index"][k]))] = {f: (g[f][k].item() if f in g.files else 0) for f in FIELDS}
-    mods = load_reference()
+            key = (str(g["setting"][k]) if setting is not None else None, int(g["config"][k]), int(g["index"][k]))
+            have[key] = {f: (g[f][k].item() if f in g.files else 0) for f in fields}
     for cfg, idx in todo:
-        c = certify(mods, cfg, idx, trials, trials_all)
-        have[(cfg, idx)] = c
-        print("config %d image %d: %s" % (cfg, idx, c), flush=True)
-        keys = sorted(have)
-        np.savez_compressed(OUT, **{f: np.array([have[k][f] for k in keys]) for f in FIELDS})
+        c = certify(cfg, idx, trials, trials_all, setting, jobs)
+        if setting is not None:
+            c["setting"] = setting
+        have[(setting, cfg, idx)] = c
+        print("config %d image %d%s: %s" % (cfg, idx, "" if setting is None else " under " + setting, c), flush=True)
+        keys = sorted(have, key=lambda k: (k[0] or "", k[1], k[2]))
+        np.savez_compressed(out, **{f: np.array([have[k][f] for k in keys]) for f in fields})
 
 
 if __name__ == "__main__":

@@ -19,6 +19,7 @@ everything its certificate shows to be stable and bounds the rest by what the re
 import numpy as np
 import pytest
 
+from golden_util import check_parity
 from vanishing_points_2017_amd import parity, synth
 
 pytestmark = pytest.mark.gpu
@@ -44,30 +45,8 @@ def _run(cfg):
 def _check(cfg):
     ref, scenes, res = _run(cfg)
     cert = parity.instability_certificates()
-    bad = []
-    for i, r in zip(ref.index, res):
-        g = ref.get(i)
-        c = parity.compare_one(r, g)
-        assert r["flags"] & 4 == 0
-        if parity.passes(c):
-            continue
-        k = cert.get((cfg, int(i)))
-        if k is None or not k["unstable"]:
-            bad.append((int(i), c))
-            continue
-        # the reference itself moves on this image under a one-ulp input change: assert what it keeps fixed, bound the rest
-        assert c["status"], (cfg, int(i), c)
-        if k["iterations_stable"]:
-            assert c["iterations"], (cfg, int(i), c)
-        if k["num_vp_stable"]:
-            assert c["num_vp"], (cfg, int(i), c)
-            assert 0 <= c["assoc_diff"] <= max(4, 3 * k["max_assoc_flips"]), (cfg, int(i), c, k)
-        if c["num_vp"] and g["vp"].size:
-            # same VP count: every VP must lie within a few times the reference's own movement of SOME reference VP, up to
-            # sign (the certificates' max_vp_move of ~2 are sign flips / reorderings between the reference's own runs)
-            d = np.minimum(np.abs(r["vp"][:, None, :] - g["vp"][None, :, :]).max(-1),
-                           np.abs(r["vp"][:, None, :] + g["vp"][None, :, :]).max(-1)).min(1)
-            assert d.max() <= max(parity.VP_TOL, 3.0 * k["max_vp_move"]), (cfg, int(i), float(d.max()), k)
+    _, _, bad = check_parity(((cfg, int(i)), r, ref.get(i), cert.get((cfg, int(i)))) for i, r in zip(ref.index, res))
+    bad = [(label[1], c) for label, c in bad]
     assert not bad, "config %d: %d of %d images miss the parity bar without an instability certificate: %s" % (
         cfg, len(bad), len(ref), bad[:5])
     return ref, res

@@ -19,6 +19,11 @@ def golden_path(config_id):
     return os.path.join(ROOT, "tests", "golden", "full_c%d.npz" % config_id)
 
 
+def keyword_golden_path():
+    """The reference's results over the keyword surface of expectation_maximisation (full_config_keywords.npz)."""
+    return os.path.join(ROOT, "tests", "golden", "full_config_keywords.npz")
+
+
 def input_sha(scene):
     """First 8 bytes of sha1(l | lp | cnn_response) -- ties a stored result to the inputs the reference was given.  The
     raster is not an input: the reference makes it from the lines (evaluation.py:175), see raster_sha."""
@@ -82,6 +87,60 @@ class ReferenceResults(object):
                 "input_sha": g["input_sha"][k], "raster_sha": g["raster_sha"][k] if "raster_sha" in g else None,
                 "ref_seconds": float(g["ref_seconds"][k]),
                 "events": {e: int(g["ev_" + e][k]) for e in ("split", "merge", "abort", "final_merge")}}
+
+
+class KeywordResults(ReferenceResults):
+    """Per-case views into full_config_keywords.npz (written by make_keyword_goldens.py, test infrastructure): the layout of
+    full_c<config>.npz with one row per (keyword setting, scene) case.  get(row) takes the ROW number; `config` / `index`
+    name the row's scene, `setting` its row of the keyword table (`kw_names` x `kw_table`, defaults filled in)."""
+
+    def __init__(self, path=None):
+        ReferenceResults.__init__(self, 0, path or keyword_golden_path())
+        self._pos = {k: k for k in range(len(self.index))}
+        self.config, self.setting = self.g["config"], self.g["setting"]
+        self.setting_names = [str(s) for s in self.g["setting_names"]]
+
+    def rows(self, setting):
+        """Row numbers of one setting (name or table row)."""
+        s = self.setting_names.index(setting) if isinstance(setting, str) else int(setting)
+        return [k for k in range(len(self.index)) if int(self.setting[k]) == s]
+
+    def scene(self, row):
+        """The generator scene of a row: lines and a response map, no raster."""
+        from . import synth
+        return next(synth.config_scenes(int(self.config[row]), count=1, start=int(self.index[row])))
+
+    def kwargs(self, setting, row=None):
+        """The keywords of one setting that differ from the reference's defaults, typed as the reference's; with `row`, a
+        supplied init_vp too (the table's "init_vp" column m > 0: synth.stress_init_vps(seed, m))."""
+        import ast
+        from . import synth
+        s = self.setting_names.index(setting) if isinstance(setting, str) else int(setting)
+        default = {str(n): ast.literal_eval(str(d)) for n, d in zip(self.g["sig_names"], self.g["sig_defaults"])
+                   if str(d) != "<required>"}
+        kw = {}
+        for name, val in zip(self.g["kw_names"], self.g["kw_table"][s]):
+            name = str(name)
+            if name == "init_vp":
+                if val > 0 and row is not None:
+                    kw["init_vp"] = synth.stress_init_vps(1000 * int(self.config[row]) + int(self.index[row]), int(val))
+            elif val != default[name]:
+                kw[name] = bool(val) if isinstance(default[name], bool) else (
+                    int(val) if isinstance(default[name], int) and float(val).is_integer() else float(val))
+        return kw
+
+
+def keyword_instability_certificates(path=None):
+    """{(setting name, config, image): certificate} from tests/golden/instability_keywords.npz: instability_certificates'
+    fields for runs of the REFERENCE under one setting of the keyword table (make_instability_certificates.py --keywords)."""
+    path = path or os.path.join(ROOT, "tests", "golden", "instability_keywords.npz")
+    if not os.path.isfile(path):
+        return {}
+    g = np.load(path, allow_pickle=False)
+    return {(str(g["setting"][k]), int(g["config"][k]), int(g["index"][k])): {
+        "trials": int(g["trials"][k]), "max_vp_move": float(g["max_vp_move"][k]),
+        "max_assoc_flips": int(g["max_assoc_flips"][k]), "iterations_stable": bool(g["iterations_stable"][k]),
+        "num_vp_stable": bool(g["num_vp_stable"][k]), "unstable": bool(g["unstable"][k])} for k in range(len(g["config"]))}
 
 
 def compare_one(res, ref):
