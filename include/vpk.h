@@ -443,7 +443,18 @@ typedef struct vpk_step_args {
 int vpk_pipeline_step(vpk_handle* cnn, vpk_handle* em, const vpk_step_args* a);
 /* Fixed-size result records, one row of vpk_record_width() doubles per image: [image id, status, m, (x, y, z) x 20,
  * line count x 20, NaN] with the m <= 20 best-supported VPs in descending order of their counts (calc_horizon.py:34-36:
- * what the horizon selection reads); the records every rank contributes to the final all_gather. */
+ * what the horizon selection reads); the records every rank contributes to the final all_gather.
+ * What a consumer may rely on: row b is [image_ids[b], status[b], m, ...] whatever the status; num_vp[b] is clamped to
+ * [0, max_vp] first and m = min(num_vp, 20); VP k and count k belong together; counts descend, and VPs with EQUAL counts
+ * keep their ascending index order (sharding.device_records is the same, bit for bit); everything behind the m-th VP and
+ * the m-th count is 0, the last column NaN.
+ * What it may NOT rely on: that order among equal counts is not calc_horizon.py:34-36's, which is np.argsort(counts)[::-1]
+ * (NumPy's unstable sort, reversed; sharding.pack_records follows it).  Both keep the same VPs with the same counts when
+ * m = num_vp; where a run of equal counts straddles the 20th place they may keep different members of the run.  A horizon
+ * selected from a record can therefore differ from the one selected from the EM result -- always when every triplet
+ * scores 0, since the first three of the order then win.  No path of this library does that: benchmark.py and bench.py
+ * select horizons from the EM results of each rank (calculate_horizon_batch) and the gathered records only carry the
+ * result; sharding.py never selects one. */
 int vpk_record_width(void);
 int vpk_build_records(vpk_handle* h, int batch, int max_vp, const int64_t* image_ids, const double* vp,
                       const double* counts, const int32_t* num_vp, const int32_t* status, double* records);

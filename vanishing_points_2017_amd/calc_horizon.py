@@ -29,7 +29,14 @@ def _end_points(hlin):
 
 
 def calculate_horizon_and_ortho_vp(em_result, maxbest=10, theta_vmin=np.pi / 10., theta_z=np.pi / 4.):
-    """Returns (hP1, hP2, zVP, hVP1, hVP2, best_combo) exactly like the reference."""
+    """Returns (hP1, hP2, zVP, hVP1, hVP2, best_combo) exactly like the reference (tests/test_horizon_cases.py: 200 cases
+    over maxbest, theta_vmin and theta_z, ties and degenerate values, np.array_equal).  Where the reference raises:
+    * every score NaN (e.g. three VPs at infinity): no triplet ever wins, hlin stays None and np.cross raises ValueError --
+      here too.  vpk_horizon_batch returns the first triplet of the order with its NaN end points instead.
+    * fewer than two scored VPs (M or maxbest below 2): the reference divides an integer hlin in place (calc_horizon.py:220-223),
+      which today's NumPy refuses (UFuncTypeError).  This port divides out of place and returns what that code says: the
+      horizon y = 0 (hP1 = (-1, 0, 1), hP2 = (1, 0, 1)), zVP = (0, 1, 0), best_combo = (0, 0) and the first VP twice -- or
+      (-1, 0, 0), (1, 0, 0) without any -- as the horizon VPs.  vpk_horizon_batch returns the same."""
     vps = em_result['vp'].copy()
     counts = em_result['counts']
     num_best = int(np.minimum(maxbest, vps.shape[0]))

@@ -123,6 +123,25 @@ def cluster2(ldist, device=0):
     return labels.cpu().numpy(), int(flags.cpu()[0])
 
 
+def build_records(image_ids, vp, counts, num_vp, status, max_vp, device=0):
+    """vpk_build_records (include/vpk.h): the fixed-size result records of a batch, (B, vpk_record_width()) float64.
+    image_ids B int64, vp B x max_vp x 3, counts B x max_vp, num_vp and status B int32."""
+    rt = get_runtime(device)
+    t = rt.torch
+    batch = int(np.asarray(image_ids).shape[0])
+    vp, counts = np.asarray(vp, dtype=np.float64), np.asarray(counts, dtype=np.float64)
+    if vp.shape != (batch, max_vp, 3) or counts.shape != (batch, max_vp) or len(num_vp) != batch or len(status) != batch:
+        raise ValueError("build_records: vp must be B x max_vp x 3, counts B x max_vp, num_vp and status B")
+    with rt.on_stream():
+        d_id, d_vp, d_cnt = _up(rt, image_ids, np.int64), _up(rt, vp, np.float64), _up(rt, counts, np.float64)
+        d_num, d_st = _up(rt, num_vp, np.int32), _up(rt, status, np.int32)
+        rec = t.empty((batch, int(rt.lib.vpk_record_width())), dtype=t.float64, device=rt.tdev)
+        rt.check(rt.lib.vpk_build_records(rt.h, batch, int(max_vp), rt.ptr(d_id), rt.ptr(d_vp), rt.ptr(d_cnt), rt.ptr(d_num),
+                                          rt.ptr(d_st), rt.ptr(rec)))
+    rt.synchronize()
+    return rec.cpu().numpy()
+
+
 MATH_FUNCTIONS = ("exp", "acos", "asin", "atan", "sqrt", "sin", "cos", "log")
 
 

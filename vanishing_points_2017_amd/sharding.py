@@ -61,10 +61,13 @@ def device_records(torch, image_ids, out):
     key = torch.where(valid, counts, torch.full_like(counts, -1.0))
     width = min(REC_VPS, max_vp)
     order = torch.argsort(key, dim=1, descending=True, stable=True)[:, :width]
-    m = torch.clamp(nv, max=width)
-    keep = (torch.arange(width, device=dev)[None, :] < m[:, None]).to(torch.float64)
-    vp = torch.gather(out["vp"], 1, order[:, :, None].expand(-1, -1, 3)) * keep[:, :, None]
-    cnt = torch.gather(counts, 1, order) * keep
+    m = torch.clamp(nv, min=0, max=width)                # as records_kernel clamps num_vp (tests/test_gpu_records.py)
+    keep = torch.arange(width, device=dev)[None, :] < m[:, None]
+    # selected, not multiplied by 0: the padding is +0.0 like the kernel's, whatever sign (or NaN) the slot behind m holds
+    vp = torch.gather(out["vp"], 1, order[:, :, None].expand(-1, -1, 3))
+    vp = torch.where(keep[:, :, None], vp, torch.zeros_like(vp))
+    cnt = torch.gather(counts, 1, order)
+    cnt = torch.where(keep, cnt, torch.zeros_like(cnt))
     rec = torch.zeros((b, REC_WIDTH), dtype=torch.float64, device=dev)
     rec[:, 0] = image_ids.to(torch.float64)
     rec[:, 1] = out["status"].to(torch.float64)
