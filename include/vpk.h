@@ -478,6 +478,15 @@ int vpk_weight_matrix(vpk_handle* h, int n, int m, const double* p_vl, const dou
 /* calc_new_vanishing_point (:453-479) for every row of w [m][n]: vp_out m x 3, valid_out m. */
 int vpk_mstep(vpk_handle* h, int n, int m, const double* l, const double* w, double* vp_out,
               int32_t* valid_out);
+/* TEST HOOK: the whole M-step of one iteration on caller-supplied state -- calc_new_vanishing_point (:453-479), the
+ * variance update (:301-307) and the error / removal tests (:309-317; hard mode :353-392) -- through the same device
+ * function the batch kernel calls.  w, lvsq, p_vl [m][n]; assoc NULL = soft mode (every line, weights w[m]), else n
+ * int32 = hard mode (VP k takes the lines with assoc == k); cur m x 3 = the VPs of the previous iteration.
+ * Outputs: vp_out m x 3 and s_out m (rows the M-step does not write keep 0 and -1), err_out m (-1 = none),
+ * removed_out m.  Not used by any product path. */
+int vpk_mstep_full(vpk_handle* h, int n, int m, const double* l, const double* w, const double* lvsq, const double* p_vl,
+                   const int32_t* assoc, const double* cur, double max_stdd, double s_thresh, double* vp_out,
+                   double* s_out, double* err_out, int32_t* removed_out);
 /* calc_vp_line_counts (:482-512, thresh = 1.96^2 at :248,:419): v m x 3, s m, w [m][n] (the decision metric),
  * lweight n -> counts_out m, counts_w_out m, assoc_out n int64 (-1 = outlier). */
 int vpk_line_counts(vpk_handle* h, int n, int m, const double* lp, const double* v, const double* s, const double* w,

@@ -180,6 +180,59 @@ int sim_mstep(int n, int m, const double* l, const double* w, double* vp_out) {
     return 0;
 }
 
+// the matching wrapper of vpk_mstep_full (csrc/vpk_em.hip: mstep_full_kernel)
+int sim_mstep_full(int n, int m, const double* l, const double* w, const double* lvsq, const double* p_vl, const int* assoc,
+                   const double* cur, double max_stdd, double s_thresh, double* vp_out, double* s_out, double* err_out,
+                   int* removed_out) {
+    vpk_em_params p;
+    memset(&p, 0, sizeof(p));
+    p.use_weights = 1; p.num_init_vp = m; p.num_iter = 1; p.split_merge_freq = 10; p.s_thresh = s_thresh;
+    EmCtx c;
+    std::vector<double> buf;
+    make_ctx(c, buf, n, p, false, 0);
+    c.l = const_cast<double*>(l);
+    g_sh.M = m;
+    for (int k = 0; k < m; ++k)
+        for (int q = 0; q < n; ++q) {
+            c.w[(size_t)k * c.ldn + q] = w[(size_t)k * n + q];
+            c.lvsq[(size_t)k * c.ldn + q] = lvsq[(size_t)k * n + q];
+            c.pvl[(size_t)k * c.ldn + q] = p_vl[(size_t)k * n + q];
+        }
+    if (assoc)
+        for (int q = 0; q < n; ++q) c.assoc[q] = assoc[q];
+    for (int k = 0; k < 3 * m; ++k) { g_sh.cur[k] = cur[k]; g_sh.nxt[k] = 0.0; }
+    for (int k = 0; k < m; ++k) g_sh.s[k] = -1.0;
+    mstep(c, assoc ? 1 : 0, max_stdd);
+    for (int k = 0; k < 3 * m; ++k) vp_out[k] = g_sh.nxt[k];
+    for (int k = 0; k < m; ++k) { s_out[k] = g_sh.s[k]; err_out[k] = g_sh.err[k]; removed_out[k] = g_sh.removed[k]; }
+    return 0;
+}
+
+// calc_vp_line_counts on its own, as csrc/vpk_em.hip's line_counts_kernel sets it up
+int sim_line_counts(int n, int m, const double* lp, const double* v, const double* s, const double* w, const double* lweight,
+                    double thresh, double* counts_out, double* counts_w_out, long long* assoc_out) {
+    vpk_em_params p;
+    memset(&p, 0, sizeof(p));
+    p.use_weights = 1; p.num_init_vp = m; p.num_iter = 1; p.split_merge_freq = 10; p.outlier_thresh = thresh;
+    EmCtx c;
+    std::vector<double> buf;
+    make_ctx(c, buf, n, p, false, 0);
+    c.lp = lp;
+    for (int k = 0; k < n; ++k) c.lweight[k] = lweight[k];
+    for (int k = 0; k < 3 * m; ++k) g_sh.cur[k] = v[k];
+    for (int k = 0; k < m; ++k) g_sh.s[k] = s[k];
+    g_sh.M = m; g_sh.ncomp = 0; g_sh.sigma_prior = 1.0;
+    line_geometry_setup(c);
+    estep(c, g_sh.cur);
+    for (int k = 0; k < m; ++k)
+        for (int q = 0; q < n; ++q) c.w[(size_t)k * c.ldn + q] = w[(size_t)k * n + q];
+    assign_lines(c, true);
+    count_lines(c);
+    for (int k = 0; k < m; ++k) { counts_out[k] = g_sh.cnt[k]; counts_w_out[k] = g_sh.cntw[k]; }
+    for (int k = 0; k < n; ++k) assoc_out[k] = c.assoc[k];
+    return 0;
+}
+
 int sim_cluster2(int n, const double* ldist, int* labels_out, unsigned* flags_out) {
     std::vector<double> D(ldist, ldist + (size_t)n * n);
     std::vector<int> member(n), csize(n);

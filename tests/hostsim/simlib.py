@@ -147,6 +147,28 @@ def mstep(l, w):
     return vp
 
 
+def mstep_full(l, w, lvsq, p_vl, cur, assoc=None, max_stdd=1e-6, s_thresh=1e-200):
+    """The wrapper that matches the library's vpk_mstep_full: vp, s, err, removed."""
+    m, n = w.shape
+    D = ctypes.c_double
+    l, w, lvsq, p_vl, cur = (np.ascontiguousarray(a, dtype=np.float64) for a in (l, w, lvsq, p_vl, cur))
+    a = None if assoc is None else np.ascontiguousarray(assoc, dtype=np.int32)
+    vp = np.zeros((m, 3)); s = np.zeros(m); err = np.zeros(m); removed = np.zeros(m, np.int32)
+    lib().sim_mstep_full(n, m, _p(l, D), _p(w, D), _p(lvsq, D), _p(p_vl, D), _p(a, ctypes.c_int32), _p(cur, D),
+                         D(max_stdd), D(s_thresh), _p(vp, D), _p(s, D), _p(err, D), _p(removed, ctypes.c_int32))
+    return vp, s, err, removed
+
+
+def line_counts(lp, v, s, w, lweight, thresh=1.96 ** 2):
+    m, n = w.shape
+    D = ctypes.c_double
+    lp, v, s, w, lweight = (np.ascontiguousarray(a, dtype=np.float64) for a in (lp, v, s, w, lweight))
+    counts = np.zeros(m); cw = np.zeros(m); assoc = np.zeros(n, np.int64)
+    lib().sim_line_counts(n, m, _p(lp, D), _p(v, D), _p(s, D), _p(w, D), _p(lweight, D), D(thresh), _p(counts, D), _p(cw, D),
+                          _p(assoc, ctypes.c_longlong))
+    return counts, cw, assoc
+
+
 # ---- the rasteriser's arithmetic (csrc/raster_device.hpp) -----------------------------------------------------------------
 RASTER_SO = os.path.join(BUILD, "libvpk_hostsim_raster.so")
 RASTER_SRC = [os.path.join(HERE, "sim_raster.cpp"),

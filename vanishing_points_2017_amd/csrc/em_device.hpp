@@ -670,7 +670,10 @@ VPK_DEVFN void pairwise_setup(EmCtx& c, bool want_lsim) {
                 j = (valid && j >= 0 && j < N) ? j : 0;
                 double b[4] = {c.lp[4 * (size_t)j], c.lp[4 * (size_t)j + 1], c.lp[4 * (size_t)j + 2], c.lp[4 * (size_t)j + 3]};
                 ks[2 * KNN1 + q] = lines_cosangle(a, b, 9.0);                          // :55
-                ks[3 * KNN1 + q] = proximity(ks[KNN1 + q], len_a, line_length(b), 1.0);  // :65
+                // :65 lines_proximity measures the pair again: for the line itself (one of the k1 when N <= KNN1) that is
+                // its distance from itself, 0 (NaN for a segment without length), not the 4 of the sorted row (:82)
+                const double dq = j == ii ? line_distance_closest(a, b) : ks[KNN1 + q];
+                ks[3 * KNN1 + q] = proximity(dq, len_a, line_length(b), 1.0);
             }
             wave_sync();
             // np.argsort(cosphi)[::-1][0:k2] (:57-59): descending, ties -> later position first
@@ -773,7 +776,8 @@ VPK_DEVFN void pairwise_setup(EmCtx& c, bool want_lsim) {
             double b[4] = {c.lp[4 * (size_t)j], c.lp[4 * (size_t)j + 1], c.lp[4 * (size_t)j + 2],
                            c.lp[4 * (size_t)j + 3]};
             ks[2 * KNN1 + q] = lines_cosangle(a, b, 9.0);                          // :55
-            ks[3 * KNN1 + q] = proximity(ks[KNN1 + q], len_a, line_length(b), 1.0);  // :65
+            const double dq = j == i ? line_distance_closest(a, b) : ks[KNN1 + q];   // :65 (the line itself: see above)
+            ks[3 * KNN1 + q] = proximity(dq, len_a, line_length(b), 1.0);
         }
         wave_sync();
         // np.argsort(cosphi)[::-1][0:k2] (:57-59): descending, ties -> later position first.  Each of the

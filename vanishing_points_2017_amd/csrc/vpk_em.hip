@@ -314,10 +314,10 @@ __global__ __launch_bounds__(EM_BOUND) void init_vps_kernel(const float* cnn, co
 __global__ __launch_bounds__(EM_BOUND) void estep_kernel(int n, int m, const double* lp, const float* cnn,
                                                            const double* v, double* s, EmLayout L, double* ws,
                                                            double* p_v_out, double* lvsq_out, double* p_vl_out,
-                                                           double* p_l_out) {
+                                                           double* p_l_out, int smoother) {
     VPK_SHARED_DECL;
     EmCtx c;
-    c.N = n; c.lp = (cgdp)lp; c.cnn = (cgfp)cnn; c.wt_doubles = WT_DOUBLES;
+    c.N = n; c.lp = (cgdp)lp; c.cnn = (cgfp)cnn; c.wt_doubles = WT_DOUBLES; c.smoother = smoother;
     c.prm.use_weights = 1;
     bind_scratch(c, ws, L, false);
     prior_setup(c);
@@ -403,6 +403,35 @@ __global__ __launch_bounds__(EM_BOUND) void mstep_kernel(int n, int m, const dou
     }
 }
 
+// TEST HOOK (vpk_mstep_full): mstep() on caller-supplied state -- the context is filled like mstep_kernel's, the
+// arithmetic is mstep()'s own.  Rows the M-step does not write come back as vp = 0, s = -1.
+__global__ __launch_bounds__(EM_BOUND) void mstep_full_kernel(int n, int m, const double* l, const double* w,
+                                                                const double* lvsq, const double* p_vl, const int* assoc,
+                                                                const double* cur, double max_stdd, double s_thresh,
+                                                                EmLayout L, double* ws, double* vp_out, double* s_out,
+                                                                double* err_out, int* removed_out, int smoother) {
+    VPK_SHARED_DECL;
+    EmCtx c;
+    c.N = n; c.l = (gdp) const_cast<double*>(l); c.wt_doubles = WT_DOUBLES; c.smoother = smoother;
+    c.prm.s_thresh = s_thresh;
+    bind_scratch(c, ws, L, false);
+    if (tid() == 0) sh.M = m;
+    for (int p = tid(); p < m * n; p += nthreads()) {
+        int k = p / n, q = p % n;
+        c.w[(size_t)k * c.ldn + q] = w[p];
+        c.lvsq[(size_t)k * c.ldn + q] = lvsq[p];
+        c.pvl[(size_t)k * c.ldn + q] = p_vl[p];
+    }
+    if (assoc)
+        for (int q = tid(); q < n; q += nthreads()) c.assoc[q] = assoc[q];
+    for (int k = tid(); k < 3 * m; k += nthreads()) { sh.cur[k] = cur[k]; sh.nxt[k] = 0.0; }
+    for (int k = tid(); k < m; k += nthreads()) sh.s[k] = -1.0;
+    block_sync();
+    mstep(c, assoc ? 1 : 0, max_stdd);
+    for (int k = tid(); k < 3 * m; k += nthreads()) vp_out[k] = sh.nxt[k];
+    for (int k = tid(); k < m; k += nthreads()) { s_out[k] = sh.s[k]; err_out[k] = sh.err[k]; removed_out[k] = sh.removed[k]; }
+}
+
 // calc_vp_line_counts (vp_localisation.py:482-512) on its own: argmax VP per line, the outlier test against
 // calc_lvsq_single of that VP (:504) and lweight == 0 (:506), counts and weighted counts per VP.
 __global__ __launch_bounds__(EM_BOUND) void line_counts_kernel(int n, int m, const double* lp, const double* v,
@@ -470,6 +499,7 @@ int em_prepare(vpk_handle* h) {
     if ((rc = allow_lds(h, estep_kernel))) return rc;
     if ((rc = allow_lds(h, weight_matrix_kernel))) return rc;
     if ((rc = allow_lds(h, mstep_kernel))) return rc;
+    if ((rc = allow_lds(h, mstep_full_kernel))) return rc;
     if ((rc = allow_lds(h, cluster2_kernel))) return rc;
     if ((rc = allow_lds(h, line_counts_kernel))) return rc;
     h->em_ready = true;
@@ -809,7 +839,7 @@ int vpk_estep(vpk_handle* h, int n, int m, const double* lp, const float* cnn, c
     int rc = vpk_reserve(h, &h->small_ws, &h->small_ws_bytes, L.total_doubles * 8, "hipMalloc(workspace)");
     if (rc) return rc;
     hipLaunchKernelGGL(estep_kernel, dim3(1), dim3(EM_THREADS), EM_LDS_BYTES, h->stream, n, m, lp, cnn, v, s, L,
-                       (double*)h->small_ws, p_v_out, lvsq_out, p_vl_out, p_l_out);
+                       (double*)h->small_ws, p_v_out, lvsq_out, p_vl_out, p_l_out, h->em_smoother);
     VPK_HIP(h, hipGetLastError());
     return VPK_OK;
 }
@@ -841,6 +871,22 @@ int vpk_mstep(vpk_handle* h, int n, int m, const double* l, const double* w, dou
     if (rc) return rc;
     hipLaunchKernelGGL(mstep_kernel, dim3(1), dim3(EM_THREADS), EM_LDS_BYTES, h->stream, n, m, l, w, L, (double*)h->small_ws,
                        vp_out, valid_out);
+    VPK_HIP(h, hipGetLastError());
+    return VPK_OK;
+}
+
+int vpk_mstep_full(vpk_handle* h, int n, int m, const double* l, const double* w, const double* lvsq, const double* p_vl,
+                   const int32_t* assoc, const double* cur, double max_stdd, double s_thresh, double* vp_out,
+                   double* s_out, double* err_out, int32_t* removed_out) {
+    if (!h || n < 1 || m < 1 || m > MAXM || !l || !w || !lvsq || !p_vl || !cur || !vp_out || !s_out || !err_out || !removed_out)
+        return vpk_fail(h, VPK_ERR_ARG, "vpk_mstep_full: bad argument");
+    VPK_HIP(h, hipSetDevice(h->device));
+    { int rc0 = em_prepare(h); if (rc0) return rc0; }
+    EmLayout L = em_layout(n, (int)em_align((size_t)m, 8), EM_WAVES, false, false);
+    int rc = vpk_reserve(h, &h->small_ws, &h->small_ws_bytes, L.total_doubles * 8, "hipMalloc(workspace)");
+    if (rc) return rc;
+    hipLaunchKernelGGL(mstep_full_kernel, dim3(1), dim3(EM_THREADS), EM_LDS_BYTES, h->stream, n, m, l, w, lvsq, p_vl, assoc,
+                       cur, max_stdd, s_thresh, L, (double*)h->small_ws, vp_out, s_out, err_out, removed_out, h->em_smoother);
     VPK_HIP(h, hipGetLastError());
     return VPK_OK;
 }

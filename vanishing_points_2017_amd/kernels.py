@@ -92,6 +92,27 @@ def mstep(l, w, device=0):
     return vp.cpu().numpy(), valid.cpu().numpy()
 
 
+def mstep_full(l, w, lvsq, p_vl, cur, assoc=None, max_stdd=1e-6, s_thresh=1e-200, device=0):
+    """The whole M-step of one iteration (vp_localisation.py:284-322; with ``assoc`` the hard one, :353-392) on supplied
+    state: w, lvsq, p_vl (M,N), cur (M,3).  Returns vp (M,3), s, err, removed (vpk_mstep_full, a test hook)."""
+    rt = get_runtime(device)
+    t = rt.torch
+    m, n = w.shape
+    with rt.on_stream():
+        d_l, d_w = _up(rt, l, np.float64), _up(rt, w, np.float64)
+        d_lv, d_p, d_cur = _up(rt, lvsq, np.float64), _up(rt, p_vl, np.float64), _up(rt, cur, np.float64)
+        d_a = None if assoc is None else _up(rt, assoc, np.int32)
+        vp = t.empty((m, 3), dtype=t.float64, device=rt.tdev)
+        s = t.empty((m,), dtype=t.float64, device=rt.tdev)
+        err = t.empty((m,), dtype=t.float64, device=rt.tdev)
+        removed = t.empty((m,), dtype=t.int32, device=rt.tdev)
+        rt.check(rt.lib.vpk_mstep_full(rt.h, n, m, rt.ptr(d_l), rt.ptr(d_w), rt.ptr(d_lv), rt.ptr(d_p),
+                                       None if d_a is None else rt.ptr(d_a), rt.ptr(d_cur), float(max_stdd), float(s_thresh),
+                                       rt.ptr(vp), rt.ptr(s), rt.ptr(err), rt.ptr(removed)))
+    rt.synchronize()
+    return vp.cpu().numpy(), s.cpu().numpy(), err.cpu().numpy(), removed.cpu().numpy()
+
+
 def line_counts(lp, v, s, w, lweight, thresh=1.96 ** 2, device=0):
     """calc_vp_line_counts (vp_localisation.py:482-512): returns (counts, counts_weighted, assoc)."""
     rt = get_runtime(device)
