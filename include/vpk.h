@@ -495,6 +495,31 @@ int vpk_line_counts(vpk_handle* h, int n, int m, const double* lp, const double*
 int vpk_cluster2(vpk_handle* h, int n, const double* ldist, int32_t* labels_out,
                  uint32_t* flags_out);
 
+/* ---- the CNN prior outside the EM (batched; asynchronous on the handle's stream) ------------------------ */
+/* replaces: pdf_params -- probability_functions.py:62-96 -- for `batch` 20 x 20 float32 response maps at once: keep
+ * the 100 strongest cells (:84-87; equal values: the higher index first), divide by their float32 sum (:89) and by
+ * float32(2 pi sigma^2) (:90).  sigma = pi / (confidence * 20) (:71) is the caller's, in double; the means (:73-80) do
+ * not depend on the map and stay with the caller.  The same device function as the EM's prior (vpk_init_vps'
+ * weights_out is this, with confidence 1.282).
+ *   cnn batch x 400 fp32 (device, not modified) -> weights_out batch x 400 fp32 (device); an all-zero map gives NaN.
+ * batch = 0 does nothing; batch < 0 or sigma <= 0: VPK_ERR_ARG. */
+int vpk_prior_params(vpk_handle* h, int batch, const float* cnn, double sigma, float* weights_out);
+/* replaces: calc_pdf -- probability_functions.py:8-40 -- the wrapped Gaussian mixture over the (alpha, beta) half
+ * sphere, for `batch` mixtures of ncomp components at npts points each; with pts_dim = 3 also calc_angles -- :252-259
+ * -- in front of it (what calc_probabilities does for the VPs, :104-105).  One thread per point walks the components in
+ * index order, skipping those whose weight is not > 0 (:21), and adds the five exponentials of :22-36 times the weight
+ * to one chain (:38): the reference's order of summation.
+ *   means    ncomp x 2 fp64 (means_shared != 0) or batch x ncomp x 2 (alpha, beta)
+ *   weights  batch x ncomp fp64
+ *   pts      npts x pts_dim fp64 (pts_shared != 0) or batch x npts x pts_dim; pts_dim 2: (alpha, beta), 3: VPs (x, y, z)
+ *   angles_out  NULL or batch x npts x 2 fp64: the (alpha, beta) the density was taken at
+ *   pdf_out  batch x npts fp64
+ * All buffers on the device.  batch = 0 or npts = 0 does nothing; negative sizes, sigma <= 0 and pts_dim outside {2, 3}:
+ * VPK_ERR_ARG. */
+int vpk_mixture_pdf(vpk_handle* h, int batch, int ncomp, const double* means, int means_shared, const double* weights,
+                    double sigma, int npts, const double* pts, int pts_dim, int pts_shared, double* angles_out,
+                    double* pdf_out);
+
 /* diagnostics: y[i] = f(x[i]) for the device's double-precision exp / acos / asin / atan / sqrt / sin / cos / log (fn =
  * 0..7) as the EM kernels call them (same translation unit, same flags).  replaces: nothing -- it measures the premise
  * of the parity bar: the reference's probability_functions.py:99-176 evaluates these through NumPy / libm, and results

@@ -69,6 +69,7 @@ EXPORTS = [
     "vpk_lsd_detect_batch", "vpk_lsd_set_workspace_limit", "vpk_lsd_set_math",
     "vpk_image_prepare_batch", "vpk_lsd_rows_to_lines",
     "vpk_pipeline_step", "vpk_build_records", "vpk_record_width", "vpk_math_probe",
+    "vpk_prior_params", "vpk_mixture_pdf",
 ]
 
 _lib = None
@@ -152,6 +153,9 @@ def load():
     lib.vpk_lsd_set_math.argtypes = [c_void, ctypes.c_int]
     lib.vpk_image_prepare_batch.argtypes = [c_void, ctypes.c_int, c_void, c_void, c_void, c_void, c_void, c_void]
     lib.vpk_lsd_rows_to_lines.argtypes = [c_void, ctypes.c_int, c_void, c_void, ctypes.c_int, c_void, c_void, c_void, c_void]
+    lib.vpk_prior_params.argtypes = [c_void, ctypes.c_int, c_void, ctypes.c_double, c_void]
+    lib.vpk_mixture_pdf.argtypes = [c_void, ctypes.c_int, ctypes.c_int, c_void, ctypes.c_int, c_void, ctypes.c_double,
+                                    ctypes.c_int, c_void, ctypes.c_int, ctypes.c_int, c_void, c_void]
     _lib = lib
     return lib
 

@@ -20,13 +20,11 @@
 #include "wave_prims.hpp"
 #include "../../include/vpk.h"
 #include "em_layout.hpp"
+#include "prior_device.hpp"
 
 namespace vpk {
 
 constexpr int MAXM = 64;            // capacity of simultaneously live VP hypotheses
-constexpr int GRIDN = 20;           // CNN output grid (cnn/deploy.prototxt:283-296)
-constexpr int NCELL = GRIDN * GRIDN;
-constexpr int MAXCOMP = 100;        // prior keeps the 100 strongest cells (probability_functions.py:87)
 constexpr int MT = 8;               // VP tile of the smoothing kernel (accumulators per column)
 constexpr int PART_DOUBLES = 2048;  // LDS scratch of the setup phases (16 KiB): the head of the smoother's panel, not yet in use then
 constexpr int WT_DOUBLES = 6144;    // LDS operand tile of the smoother (48 KiB)
@@ -34,7 +32,6 @@ constexpr int KNN1 = 10;            // line_rating_knn k1 (vp_localisation.py:34
 constexpr int TRACE_COLS = 12;       // trace row: M, max_err, M_end, events, us_estep, us_smooth, us_mstep, us_total,
                                      //            us_split_select, us_split_cluster, us_split_fit, us_merge
 constexpr int KNN2 = 4;             // k2=4 at the call site (:230)
-constexpr double PI_D = 3.141592653589793238462643383279502884;
 
 struct Shared {
     double cur[MAXM * 3];   // v[i]   of the reference's history array
@@ -134,7 +131,6 @@ VPK_DEV double lap(long long& t) {
     t = now;
     return us;
 }
-VPK_DEV bool is_nan(double x) { return x != x; }
 // The reference's scalar code calls np.dot / np.linalg.norm on 2- and 3-vectors; NumPy's BLAS
 // evaluates those as a fused chain  fma(x_{n-1}, y_{n-1}, ... fma(x1, y1, x0*y0))  (verified on the
 // build container's NumPy 2.2.6 / OpenBLAS).  These helpers round the same way, which matters when a
@@ -179,11 +175,6 @@ VPK_DEVFN double block_max(Shared&, double v) {
     block_sync();
     return b;
 }
-
-// exp for arguments that are usually far below the underflow threshold (a VP against a distant mixture
-// component or line): exp(x) is exactly 0 for x < -745.14 in glibc and in ocml, so the ~50-instruction
-// evaluation is skipped there -- whole waves take the short path most of the time.
-VPK_DEV double exp_underflow(double x) { return x < -746.0 ? 0.0 : exp(x); }
 
 // symmetric 3x3 eigen-solver (cyclic Jacobi): A = J diag(ev) J^T, J orthogonal (columns = eigenvectors)
 VPK_DEV void eig3_full(double a00, double a01, double a02, double a11, double a12, double a22,
@@ -830,68 +821,24 @@ VPK_DEVFN void weights_setup(EmCtx& c) {
 // ---------------------------------------------------------------------------------------------
 // prior parameters and initial VPs from the CNN grid
 // ---------------------------------------------------------------------------------------------
-// numpy's float32 pairwise summation (np.sum over a contiguous float32 array), needed because
-// the prior weights are normalised in float32 (probability_functions.py:82-90)
-VPK_DEV float np_pairwise_block_f32(const float* a, int n) {   // 8 <= n <= 128
-    float r[8];
-    for (int j = 0; j < 8; ++j) r[j] = a[j];
-    int i;
-    for (i = 8; i < n - (n % 8); i += 8)
-        for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-    float res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res += a[i];
-    return res;
-}
-// n = 400 splits as (96 + 104) + (96 + 104): n2 = n/2 rounded down to a multiple of 8 at each level
-VPK_DEV float np_pairwise_sum_f32_400(const float* a) {
-    float lo = np_pairwise_block_f32(a, 96) + np_pairwise_block_f32(a + 96, 104);
-    float hi = np_pairwise_block_f32(a + 200, 96) + np_pairwise_block_f32(a + 296, 104);
-    return lo + hi;
-}
-
-// np.linspace(-(A-1)/A*pi/2, (A-1)/A*pi/2, A)[i] (probability_functions.py:73,75)
-VPK_DEV double grid_centre(int i) {
-    double start = -(GRIDN - 1.0) / GRIDN * PI_D / 2;
-    double stop = (GRIDN - 1.0) / GRIDN * PI_D / 2;
-    double step = (stop - start) / (GRIDN - 1);
-    return i == GRIDN - 1 ? stop : i * step + start;
-}
-
+// (the float32 pairwise sum, the grid centres and the keep-100 rule itself: prior_device.hpp)
 // pdf_params (probability_functions.py:62-96): keep the 100 strongest cells, normalise in f32.
 VPK_DEVFN void prior_setup(EmCtx& c) {
     Shared& sh = SH();
-    for (int i = tid(); i < NCELL; i += nthreads()) sh.wts[i] = c.cnn[i];
-    block_sync();
-    float* keep = (float*)SCRATCH();  // 400 floats
-    for (int i = tid(); i < NCELL; i += nthreads()) {
-        float wi = sh.wts[i];
-        int rank = 0;  // position in argsort(weights)[::-1]: ties -> higher index first
-        for (int j = 0; j < NCELL; ++j) {
-            float wj = sh.wts[j];
-            rank += (wj > wi) || (wj == wi && j > i);
-        }
-        keep[i] = rank < MAXCOMP ? wi : 0.f;
-    }
-    block_sync();
-    if (tid() == 0) {
-        sh.sigma_prior = PI_D / (1.282 * GRIDN);  // :71
-        ((float*)SCRATCH())[NCELL] = np_pairwise_sum_f32_400(keep);
-    }
-    block_sync();
+    float* keep = (float*)SCRATCH();  // 400 floats and their sum
+    if (tid() == 0) sh.sigma_prior = PI_D / (1.282 * GRIDN);  // :71
+    prior_keep_sum(c.cnn, sh.wts, keep);
     // normalise every cell in parallel, then list the positive ones in cell-index order (calc_pdf visits cells in
     // index order, :20-21): position = positive cells in earlier waves + positive cells in lower lanes.  (One thread
     // walking the 400 cells with two f32 divisions each was ~50 us per image.)
     {
-        const float sum = ((float*)SCRATCH())[NCELL];
-        const float dv = (float)(2 * PI_D * sh.sigma_prior * sh.sigma_prior);
+        const float sum = keep[NCELL];
+        const float dv = prior_norm_f32(sh.sigma_prior);
         int* wcount = (int*)(SCRATCH() + 256);            // per-wave counts (behind the 401 floats)
         for (int base = 0; base < NCELL; base += nthreads()) {   // one round for 512 threads
             const int i = base + tid();
             float w = 0.f;
-            if (i < NCELL) {
-                w = keep[i] / sum;
-                w = w / dv;
-            }
+            if (i < NCELL) w = prior_weight(keep[i], sum, dv);
             const unsigned long long pos = wave_ballot(i < NCELL && w > 0);
             if (lane() == 0) wcount[wave_id()] = popcount64(pos);
             block_sync();
@@ -1103,21 +1050,11 @@ VPK_DEVFN void estep(EmCtx& c, const double* X) {
         const int per_round = nwaves() * (WAVE / G);
         for (int m = wave_id() * (WAVE / G) + lane() / G; m < M; m += per_round) {
             double x0 = X[3 * m], x1 = X[3 * m + 1], x2 = X[3 * m + 2];
-            double beta = asin(x1);
-            double inner = x0 / cos(beta);
-            inner = inner < 1 ? inner : (is_nan(inner) ? inner : 1.0);
-            inner = inner > -1 ? inner : (is_nan(inner) ? inner : -1.0);
-            double alpha = asin(inner);
+            double alpha, beta;
+            vp_angles(x0, x1, alpha, beta);
             double acc = 0.0;
             for (int q = gl; q < sh.ncomp; q += G) {
-                double ma = sh.pma[q], mb = sh.pmb[q];
-                double d1 = (alpha - ma) * (alpha - ma) + (beta - mb) * (beta - mb);
-                double d2 = (alpha - ma + PI_D) * (alpha - ma + PI_D) + (beta + mb) * (beta + mb);
-                double d3 = (alpha - ma - PI_D) * (alpha - ma - PI_D) + (beta + mb) * (beta + mb);
-                double d4 = (alpha + ma) * (alpha + ma) + (beta - mb - PI_D) * (beta - mb - PI_D);
-                double e4 = exp_underflow(d4 * kk);          // the fifth term duplicates the fourth (:25-26)
-                double p = (((exp_underflow(d1 * kk) + exp_underflow(d2 * kk)) + exp_underflow(d3 * kk)) + e4) + e4;
-                acc += p * sh.pw[q];
+                acc += mixture_term(alpha, beta, sh.pma[q], sh.pmb[q], kk) * sh.pw[q];
             }
             acc = group_sum<G>(acc);
             if (gl == 0) {
@@ -2688,11 +2625,7 @@ VPK_DEVFN void write_result(EmCtx& c, EmOut& o, int status, int iterations) {
             double alpha = 0.0, beta = 0.0;
             if (ok) {
                 const double x0 = sh.nxt[3 * m], x1 = sh.nxt[3 * m + 1];
-                beta = asin(x1);
-                double inner = x0 / cos(beta);
-                inner = inner < 1 ? inner : (is_nan(inner) ? inner : 1.0);
-                inner = inner > -1 ? inner : (is_nan(inner) ? inner : -1.0);
-                alpha = asin(inner);
+                vp_angles(x0, x1, alpha, beta);
             }
             o.d_pv[m] = ok ? sh.pv[m] : 0.0;
             o.d_angles[2 * m] = alpha;
