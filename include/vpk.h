@@ -520,6 +520,33 @@ int vpk_mixture_pdf(vpk_handle* h, int batch, int ncomp, const double* means, in
                     double sigma, int npts, const double* pts, int pts_dim, int pts_shared, double* angles_out,
                     double* pdf_out);
 
+/* ---- line geometry outside the EM (batched; asynchronous on the handle's stream) ------------------------- */
+/* Both entries: lp sum(N) x 4 fp64 (device, not modified), image b's lines are lp[offsets[b] .. offsets[b + 1]); offsets
+ * host int64[batch + 1], not decreasing, as vpk_em_batch takes them.  batch = 0 and images without lines do nothing.
+ * batch < 0, decreasing offsets and sigma not > 0: VPK_ERR_ARG, nothing is written.  The pair functions are the EM's
+ * (vp_localisation.py:700-776: lines_similarity, lines_proximity, lines_points_cosangle with f = 9 -- both callers pass 9,
+ * :55 and :701 --, line_distance_closest), with the settings the EM fixes (sigma = 1 at :178, k1 = 10, k2 = 4 at :230) as
+ * arguments: the reference's own defaults differ (calc_lsim sigma = 0.1 at :87; line_rating_knn k2 = 3 at :34). */
+/* replaces: calc_lsim -- vp_localisation.py:87-108 -- for a batch: per image the symmetric N x N similarity matrix, zero
+ * diagonal (:104).  Every unordered pair (i, j < i) is evaluated once as lines_similarity(lp[i], lp[j], sigma) (:106) and
+ * stored to both halves (:95-97), so lsim == lsim.T bit for bit; at sigma = 1 the matrix is vpk_pairwise's bit for bit.
+ * mat_offsets host int64[batch + 1]: element offset of image b's row-major matrix (row stride N_b) in lsim_out;
+ * mat_offsets[b + 1] - mat_offsets[b] >= N_b^2, else VPK_ERR_ARG (the caller may pad; padding is not written).  One launch
+ * over (image, block of 16 rows); no distance matrix is written. */
+int vpk_line_similarity_batch(vpk_handle* h, int batch, const int64_t* offsets, const double* lp, double sigma,
+                              const int64_t* mat_offsets, double* lsim_out);
+/* replaces: line_rating_knn -- :34-72, before any clip -- + lines_angles -- :765-776 -- + line_length -- :761 -- for a
+ * batch, WITHOUT an N x N matrix: every row's distances (calc_ldist_parfun :75-84, the row itself counts 4) are evaluated
+ * on the fly and only the k1 nearest kept; of those the k2 with the largest sharpened cosine (:55-59; equal cosines: the
+ * later neighbour first, as argsort(...)[::-1] orders them) give mean(prox * cos) (:61-70).  k1 and k2 are clamped to N_b
+ * per image (:40-41) and the divisor is the clamped k2.  Equal distances: the lower index is the nearer.
+ *   k1 1..16, k2 1..k1, else VPK_ERR_ARG.  (Up to 16 elements NumPy's argsort is an insertion sort and its order among
+ *   equal cosines is defined; k2 > k1 is an IndexError at :63.)
+ *   lscore_out / langle_out / llen_out  sum(N) fp64 each (device); any of the three may be NULL and is then not computed
+ * At k1 = 10, k2 = 4, sigma = 1 the scores and angles are vpk_pairwise's bit for bit. */
+int vpk_line_rating_batch(vpk_handle* h, int batch, const int64_t* offsets, const double* lp, int k1, int k2,
+                          double sigma, double* lscore_out, double* langle_out, double* llen_out);
+
 /* diagnostics: y[i] = f(x[i]) for the device's double-precision exp / acos / asin / atan / sqrt / sin / cos / log (fn =
  * 0..7) as the EM kernels call them (same translation unit, same flags).  replaces: nothing -- it measures the premise
  * of the parity bar: the reference's probability_functions.py:99-176 evaluates these through NumPy / libm, and results

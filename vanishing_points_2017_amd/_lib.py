@@ -70,6 +70,7 @@ EXPORTS = [
     "vpk_image_prepare_batch", "vpk_lsd_rows_to_lines",
     "vpk_pipeline_step", "vpk_build_records", "vpk_record_width", "vpk_math_probe",
     "vpk_prior_params", "vpk_mixture_pdf",
+    "vpk_line_similarity_batch", "vpk_line_rating_batch",
 ]
 
 _lib = None
@@ -156,6 +157,9 @@ def load():
     lib.vpk_prior_params.argtypes = [c_void, ctypes.c_int, c_void, ctypes.c_double, c_void]
     lib.vpk_mixture_pdf.argtypes = [c_void, ctypes.c_int, ctypes.c_int, c_void, ctypes.c_int, c_void, ctypes.c_double,
                                     ctypes.c_int, c_void, ctypes.c_int, ctypes.c_int, c_void, c_void]
+    lib.vpk_line_similarity_batch.argtypes = [c_void, ctypes.c_int, c_void, c_void, ctypes.c_double, c_void, c_void]
+    lib.vpk_line_rating_batch.argtypes = [c_void, ctypes.c_int, c_void, c_void, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                          c_void, c_void, c_void]
     _lib = lib
     return lib
 

@@ -21,6 +21,7 @@
 #include "../../include/vpk.h"
 #include "em_layout.hpp"
 #include "prior_device.hpp"
+#include "line_device.hpp"
 
 namespace vpk {
 
@@ -121,9 +122,7 @@ VPK_DEV void bind_scratch(EmCtx& c, double* base_, const EmLayout& L, bool do_sp
 // ---------------------------------------------------------------------------------------------
 // small helpers
 // ---------------------------------------------------------------------------------------------
-VPK_DEV double clip(double x, double lo, double hi) {  // np.clip (NaN passes through)
-    return x < lo ? lo : (x > hi ? hi : x);
-}
+// (clip, dot2 and norm2: line_device.hpp)
 // phase stopwatch (thread 0, after a barrier): returns microseconds since the previous call
 VPK_DEV double lap(long long& t) {
     long long now = clock_ticks();
@@ -135,11 +134,9 @@ VPK_DEV double lap(long long& t) {
 // evaluates those as a fused chain  fma(x_{n-1}, y_{n-1}, ... fma(x1, y1, x0*y0))  (verified on the
 // build container's NumPy 2.2.6 / OpenBLAS).  These helpers round the same way, which matters when a
 // VP collapses onto a single line and 1 - |cos| is 0 or 1 ulp (sigma^2 at its 1e-200 floor).
-VPK_DEV double dot2(double ax, double ay, double bx, double by) { return fma(ay, by, ax * bx); }
 VPK_DEV double dot3(double ax, double ay, double az, double bx, double by, double bz) {
     return fma(az, bz, fma(ay, by, ax * bx));
 }
-VPK_DEV double norm2(double x, double y) { return sqrt(dot2(x, y, x, y)); }
 VPK_DEV double norm3(double x, double y, double z) { return sqrt(dot3(x, y, z, x, y, z)); }
 VPK_DEV double sign_np(double x) { return x > 0 ? 1.0 : (x < 0 ? -1.0 : (x == 0 ? 0.0 : x)); }
 
@@ -311,117 +308,6 @@ VPK_DEV void lapack_null_1row(double a, double b, double c, double out[3]) {
     out[0] = -tau * v2;
     out[1] = -tau * v2 * v1;
     out[2] = 1 - tau * v2 * v2;
-}
-
-// ---------------------------------------------------------------------------------------------
-// segment geometry (vp_localisation.py:700-776)
-// ---------------------------------------------------------------------------------------------
-// vp_localisation.py:743-758: the reference squares the NORM of (b - a) (:747)
-VPK_DEV double seg_point_dist(double ax, double ay, double bx, double by, double px, double py) {
-    double dx = bx - ax, dy = by - ay;
-    double nrm = norm2(dx, dy);
-    double param = dot2(px - ax, py - ay, dx, dy) / (nrm * nrm);
-    double cx, cy;
-    if (param < 0) {
-        cx = ax; cy = ay;
-    } else if (param > 1) {
-        cx = bx; cy = by;
-    } else {
-        cx = ax + param * dx; cy = ay + param * dy;
-    }
-    double ex = cx - px, ey = cy - py;
-    return norm2(ex, ey);
-}
-// Per-line quantities reused by every pair this line takes part in (all as the reference rounds them)
-struct LineGeom {
-    double x1, y1, x2, y2;   // end points
-    double dx, dy;           // (x2 - x1, y2 - y1): segment vector used by line_segment_point_distance
-    double nn;               // np.square(norm(d)) (:747)
-    double vx, vy;           // (x1 - x2, y1 - y2): direction used by lines_points_cosangle (:716)
-    double nv;               // norm(v)
-};
-VPK_DEV LineGeom line_geom(const double a[4]) {
-    LineGeom g;
-    g.x1 = a[0]; g.y1 = a[1]; g.x2 = a[2]; g.y2 = a[3];
-    g.dx = a[2] - a[0]; g.dy = a[3] - a[1];
-    const double nrm = norm2(g.dx, g.dy);
-    g.nn = nrm * nrm;
-    g.vx = a[0] - a[2]; g.vy = a[1] - a[3];
-    g.nv = norm2(g.vx, g.vy);
-    return g;
-}
-// squared distance from point p to segment s (vp_localisation.py:743-758 before the final sqrt)
-VPK_DEV double seg_point_dist_sq(const LineGeom& s, double px, double py) {
-    const double param = dot2(px - s.x1, py - s.y1, s.dx, s.dy) / s.nn;
-    double cx, cy;
-    if (param < 0) {
-        cx = s.x1; cy = s.y1;
-    } else if (param > 1) {
-        cx = s.x2; cy = s.y2;
-    } else {
-        cx = s.x1 + param * s.dx; cy = s.y1 + param * s.dy;
-    }
-    const double ex = cx - px, ey = cy - py;
-    return dot2(ex, ey, ex, ey);
-}
-// vp_localisation.py:727-740.  sqrt is monotonic and correctly rounded, so min(sqrt(a..d)) ==
-// sqrt(min(a..d)) bit for bit: one square root per pair instead of four.
-VPK_DEV double line_distance_closest(const LineGeom& a, const LineGeom& b) {
-    const double d1 = seg_point_dist_sq(a, b.x1, b.y1);
-    const double d2 = seg_point_dist_sq(a, b.x2, b.y2);
-    const double d4 = seg_point_dist_sq(b, a.x1, a.y1);
-    const double d5 = seg_point_dist_sq(b, a.x2, a.y2);
-    const double m = d1 < d2 ? d1 : d2;
-    const double q = d4 < d5 ? d4 : d5;
-    return sqrt(m < q ? m : q);
-}
-// cos(clip(9 * acos(c), -pi/2, pi/2)) for c in [0, 1] without acos/cos (vp_localisation.py:721-722 with
-// f = 9): with s = sin(phi) = sqrt((1 - c)(1 + c)), cos(9 phi) = Re((c + i s)^9), evaluated by repeated
-// squaring (unit-modulus products: ~1e-15 absolute error, the same order as libm's last-ulp noise through
-// the ill-conditioned acos near c = 1).  9 phi >= pi/2  <=>  c <= cos(pi/18): the clipped branch returns
-// numpy's cos(pi/2) = 6.123233995736766e-17.
-VPK_DEV double cos9_of_cos(double c) {
-    const double COS_PI_18 = 0.98480775301220802;     // cos(pi / 18)
-    if (!(c > COS_PI_18)) return (c != c) ? c : 6.123233995736766e-17;
-    if (c > 1.0) c = 1.0;                             // np.clip(cosdphi, -1, 1)
-    const double s = sqrt((1.0 - c) * (1.0 + c));
-    double re = c, im = s;                            // z
-    double r2 = re * re - im * im, i2 = 2 * re * im;  // z^2
-    double r4 = r2 * r2 - i2 * i2, i4 = 2 * r2 * i2;  // z^4
-    double r8 = r4 * r4 - i4 * i4, i8 = 2 * r4 * i4;  // z^8
-    return r8 * re - i8 * im;                         // Re(z^9)
-}
-VPK_DEV double lines_cosangle(const LineGeom& a, const LineGeom& b, double f) {   // :715-724, f = 9 only
-    const double c = fabs(dot2(a.vx, a.vy, b.vx, b.vy) / (a.nv * b.nv));
-    (void)f;
-    return cos9_of_cos(c);
-}
-// vp_localisation.py:727-740
-VPK_DEV double line_distance_closest(const double a[4], const double b[4]) {
-    double d1 = seg_point_dist(a[0], a[1], a[2], a[3], b[0], b[1]);
-    double d2 = seg_point_dist(a[0], a[1], a[2], a[3], b[2], b[3]);
-    double d4 = seg_point_dist(b[0], b[1], b[2], b[3], a[0], a[1]);
-    double d5 = seg_point_dist(b[0], b[1], b[2], b[3], a[2], a[3]);
-    double m = d1 < d2 ? d1 : d2;           // np.min of [d1,d2,d4,d5]; NaN handling not replicated
-    double q = d4 < d5 ? d4 : d5;
-    return m < q ? m : q;
-}
-// vp_localisation.py:715-724
-VPK_DEV double lines_cosangle(const double a[4], const double b[4], double f) {
-    double v1x = a[0] - a[2], v1y = a[1] - a[3];
-    double v2x = b[0] - b[2], v2y = b[1] - b[3];
-    double n1 = norm2(v1x, v1y), n2 = norm2(v2x, v2y);
-    double c = fabs(dot2(v1x, v1y, v2x, v2y) / (n1 * n2));
-    double dphi = fabs(acos(clip(c, -1.0, 1.0)));
-    return cos(clip(f * dphi, -PI_D / 2, PI_D / 2));
-}
-VPK_DEV double line_length(const double a[4]) {
-    return norm2(a[0] - a[2], a[1] - a[3]);
-}
-// vp_localisation.py:708-712 with the distance supplied
-VPK_DEV double proximity(double d, double len_a, double len_b, double sigma) {
-    double sg = sigma * (len_a < len_b ? len_a : len_b);
-    return exp(-(d * d) / (2 * sg * sg));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -682,10 +568,7 @@ VPK_DEVFN void pairwise_setup(EmCtx& c, bool want_lsim) {
                 double sum = 0.0;
                 for (int r = 0; r < k2; ++r) sum += ks[4 * KNN1 + r];                       // :68, in rank order
                 c.lscore[i] = sum / k2;                                                 // :70
-                double vx = a[0] - a[2], vy = a[1] - a[3];                              // lines_angles (:765-776)
-                double nr = norm2(vx, vy);
-                double phi = fabs(acos(clip(vx / nr, -1.0, 1.0)));
-                c.langle[i] = phi > PI_D / 2 ? PI_D - phi : phi;
+                c.langle[i] = line_angle(a);                                            // lines_angles (:765-776)
             }
             wave_sync();
         }
@@ -787,11 +670,7 @@ VPK_DEVFN void pairwise_setup(EmCtx& c, bool want_lsim) {
             double sum = 0.0;
             for (int r = 0; r < k2; ++r) sum += ks[4 * KNN1 + r];                       // :68, in rank order
             c.lscore[i] = sum / k2;                                                 // :70
-            // lines_angles (:765-776)
-            double vx = a[0] - a[2], vy = a[1] - a[3];
-            double nr = norm2(vx, vy);
-            double phi = fabs(acos(clip(vx / nr, -1.0, 1.0)));
-            c.langle[i] = phi > PI_D / 2 ? PI_D - phi : phi;
+            c.langle[i] = line_angle(a);                                            // lines_angles (:765-776)
         }
         wave_sync();
     }

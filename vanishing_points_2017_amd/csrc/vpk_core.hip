@@ -32,6 +32,26 @@ int vpk_reserve(vpk_handle* h, void** p, size_t* have, size_t want, const char* 
     return VPK_OK;
 }
 
+// copies `bytes` of `src` to s.dev through s's pinned staging, asynchronously on the handle's stream
+int vpk_stage_upload(vpk_handle* h, vpk_staged& s, const void* src, size_t bytes, const char* what) {
+    if (s.ev_valid) VPK_HIP(h, hipEventSynchronize(s.ev));    // the previous call's upload has left the staging
+    if (s.host_bytes < bytes) {
+        if (s.host) VPK_HIP(h, hipHostFree(s.host));
+        s.host = nullptr;
+        s.host_bytes = 0;
+        VPK_HIP(h, hipHostMalloc(&s.host, bytes, hipHostMallocDefault));
+        s.host_bytes = bytes;
+    }
+    if (!s.ev) VPK_HIP(h, hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+    memcpy(s.host, src, bytes);
+    const int rc = vpk_reserve(h, &s.dev, &s.dev_bytes, bytes, what);
+    if (rc) return rc;
+    VPK_HIP(h, hipMemcpyAsync(s.dev, s.host, bytes, hipMemcpyHostToDevice, h->stream));
+    VPK_HIP(h, hipEventRecord(s.ev, h->stream));
+    s.ev_valid = true;
+    return VPK_OK;
+}
+
 extern "C" {
 
 int vpk_version(void) { return VPK_VERSION; }
@@ -87,7 +107,7 @@ int vpk_destroy(vpk_handle* h) {
     if (h->lsd_hdr) (void)hipFree(h->lsd_hdr);
     if (h->lsd_host) (void)hipHostFree(h->lsd_host);
     if (h->lsd_ev) (void)hipEventDestroy(h->lsd_ev);
-    for (vpk_staged* s : {&h->fe_prep, &h->fe_rows}) {
+    for (vpk_staged* s : {&h->fe_prep, &h->fe_rows, &h->lines_hdr}) {
         if (s->dev) (void)hipFree(s->dev);
         if (s->host) (void)hipHostFree(s->host);
         if (s->ev) (void)hipEventDestroy(s->ev);

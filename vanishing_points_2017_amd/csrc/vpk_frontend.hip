@@ -109,26 +109,6 @@ __global__ void __launch_bounds__(PASS_THREADS) fe_rows_to_lines(const RowDesc* 
     }
 }
 
-// copies `bytes` of `src` to s.dev through s's pinned staging, asynchronously on the handle's stream
-int stage_upload(vpk_handle* h, vpk_staged& s, const void* src, size_t bytes, const char* what) {
-    if (s.ev_valid) VPK_HIP(h, hipEventSynchronize(s.ev));    // the previous call's upload has left the staging
-    if (s.host_bytes < bytes) {
-        if (s.host) VPK_HIP(h, hipHostFree(s.host));
-        s.host = nullptr;
-        s.host_bytes = 0;
-        VPK_HIP(h, hipHostMalloc(&s.host, bytes, hipHostMallocDefault));
-        s.host_bytes = bytes;
-    }
-    if (!s.ev) VPK_HIP(h, hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-    memcpy(s.host, src, bytes);
-    const int rc = vpk_reserve(h, &s.dev, &s.dev_bytes, bytes, what);
-    if (rc) return rc;
-    VPK_HIP(h, hipMemcpyAsync(s.dev, s.host, bytes, hipMemcpyHostToDevice, h->stream));
-    VPK_HIP(h, hipEventRecord(s.ev, h->stream));
-    s.ev_valid = true;
-    return VPK_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -192,7 +172,7 @@ int vpk_image_prepare_batch(vpk_handle* h, int batch, const int32_t* dims, const
     std::vector<unsigned char> hdr(desc_bytes + wt.size() * sizeof(int32_t));
     memcpy(hdr.data(), desc.data(), (size_t)batch * sizeof(PrepDesc));
     if (!wt.empty()) memcpy(hdr.data() + desc_bytes, wt.data(), wt.size() * sizeof(int32_t));
-    int rc = stage_upload(h, h->fe_prep, hdr.data(), hdr.size(), "vpk_image_prepare_batch: header");
+    int rc = vpk_stage_upload(h, h->fe_prep, hdr.data(), hdr.size(), "vpk_image_prepare_batch: header");
     if (rc) return rc;
     if (tmp_bytes) {
         rc = vpk_reserve(h, &h->fe_ws, &h->fe_ws_bytes, (size_t)tmp_bytes, "vpk_image_prepare_batch: workspace");
@@ -238,7 +218,7 @@ int vpk_lsd_rows_to_lines(vpk_handle* h, int batch, const int32_t* dims, const d
     if (max_n == 0) return VPK_OK;
     if (!rows) return vpk_fail(h, VPK_ERR_ARG, "vpk_lsd_rows_to_lines: rows is NULL");
     VPK_HIP(h, hipSetDevice(h->device));
-    const int rc = stage_upload(h, h->fe_rows, desc.data(), desc.size() * sizeof(RowDesc), "vpk_lsd_rows_to_lines: header");
+    const int rc = vpk_stage_upload(h, h->fe_rows, desc.data(), desc.size() * sizeof(RowDesc), "vpk_lsd_rows_to_lines: header");
     if (rc) return rc;
     const RowDesc* ddesc = (const RowDesc*)h->fe_rows.dev;
     for (int s = 0; s < batch; s += MAX_LAUNCH_IMAGES) {

@@ -97,12 +97,15 @@ struct vpk_handle {
     vpk_staged fe_prep, fe_rows;
     void* fe_ws = nullptr;
     size_t fe_ws_bytes = 0;
+    vpk_staged lines_hdr;            // vpk_line_similarity_batch / vpk_line_rating_batch (vpk_lines.hip): the offsets
 };
 
 int vpk_fail(vpk_handle* h, int code, const char* what);
 int vpk_fail_hip(vpk_handle* h, hipError_t e, const char* what);
 int vpk_reserve(vpk_handle* h, void** p, size_t* have, size_t want, const char* what);
 void vpk_cnn_free(vpk_handle* h);
+// copies `bytes` of `src` to s.dev through s's pinned staging, asynchronously on the handle's stream
+int vpk_stage_upload(vpk_handle* h, vpk_staged& s, const void* src, size_t bytes, const char* what);
 
 #define VPK_HIP(h, call)                                         \
     do {                                                         \
