@@ -547,6 +547,39 @@ int vpk_line_similarity_batch(vpk_handle* h, int batch, const int64_t* offsets, 
 int vpk_line_rating_batch(vpk_handle* h, int batch, const int64_t* offsets, const double* lp, int k1, int k2,
                           double sigma, double* lscore_out, double* langle_out, double* llen_out);
 
+/* ---- result overlays (batched; asynchronous on the handle's stream) ---------------------------------------- */
+/* Both entries blend primitives into 8-bit RGB images in place, by the renderer of DESIGN section 7d: a primitive of width
+ * w covers the points within w / 2 of its closed segment (a capsule; a disc when the segment has no length), coverage of
+ * a pixel is counted on its 4 x 4 sub-samples in fp64 with the distance of line_segment_point_distance --
+ * vp_localisation.py:743-758 -- before its square root, and with a = floor(255 * coverage * A / 255 + 0.5) every channel
+ * becomes (c a + d (255 - a) + 127) / 255 in integers.  The primitives of an image are blended in index order: the order
+ * is part of the result.  Pixel (x, y) covers [x, x + 1) x [y, y + 1), row 0 at the top.
+ *   pix_offsets   host int64[batch + 1]: image b's bytes start at rgb_inout[pix_offsets[b]], rows of 3 W_b bytes without
+ *                 padding; pix_offsets[b + 1] - pix_offsets[b] >= 3 W_b H_b (the caller may pad; padding is not written)
+ *   rgb_inout     device; every pixel of an image that has at least one primitive is read and written back (unchanged where
+ *                 no primitive reaches it), an image without primitives is not touched, and never a byte outside an image
+ *   *_offsets     host int64[batch + 1], not decreasing: image b's primitives are [offsets[b], offsets[b + 1])
+ *   *_rgba        device, 4 bytes per primitive (r, g, b, A), 4-byte aligned; opacity = A / 255
+ * A primitive with a coordinate or width that is not finite, or a width below 0, is not drawn.  batch = 0 and images
+ * without primitives do nothing.  batch < 0, a side below 1 and offsets that do not rise as described: VPK_ERR_ARG, and
+ * nothing is launched.  One launch over (image, tile of 16 x 16 pixels), one pixel per thread. */
+/* replaces: the ax1.plot calls of show_em_result -- result_plotting.py:93-97 (the lines of the best VPs, lw = 2) and :106-107
+ * (the horizon, lw = 10) -- for a batch of images of any sizes.
+ *   dims       host int32[2 batch]: W_b, H_b (>= 1)
+ *   seg_px     device fp64, sum(P) x 4: end points (px, py, qx, qy) in pixel coordinates (:56-59)
+ *   seg_width  device fp64, sum(P): w in pixels */
+int vpk_overlay_lines_batch(vpk_handle* h, int batch, const int32_t* dims, const int64_t* pix_offsets, uint8_t* rgb_inout,
+                            const int64_t* seg_offsets, const double* seg_px, const uint8_t* seg_rgba,
+                            const double* seg_width);
+/* replaces: the ax2.plot call of plot_result -- result_plotting.py:135-139 (one round marker per VP, alpha = 0.6) -- for a
+ * batch of square panels.
+ *   sizes          host int32[batch]: panel b is sizes[b] x sizes[b] pixels (>= 1)
+ *   mark_xy        device fp64, sum(P) x 2: centres in pixel coordinates
+ *   mark_diameter  device fp64, sum(P): diameters in pixels */
+int vpk_overlay_markers_batch(vpk_handle* h, int batch, const int32_t* sizes, const int64_t* pix_offsets,
+                              uint8_t* rgb_inout, const int64_t* mark_offsets, const double* mark_xy,
+                              const uint8_t* mark_rgba, const double* mark_diameter);
+
 /* diagnostics: y[i] = f(x[i]) for the device's double-precision exp / acos / asin / atan / sqrt / sin / cos / log (fn =
  * 0..7) as the EM kernels call them (same translation unit, same flags).  replaces: nothing -- it measures the premise
  * of the parity bar: the reference's probability_functions.py:99-176 evaluates these through NumPy / libm, and results

@@ -71,6 +71,7 @@ EXPORTS = [
     "vpk_pipeline_step", "vpk_build_records", "vpk_record_width", "vpk_math_probe",
     "vpk_prior_params", "vpk_mixture_pdf",
     "vpk_line_similarity_batch", "vpk_line_rating_batch",
+    "vpk_overlay_lines_batch", "vpk_overlay_markers_batch",
 ]
 
 _lib = None
@@ -160,6 +161,8 @@ def load():
     lib.vpk_line_similarity_batch.argtypes = [c_void, ctypes.c_int, c_void, c_void, ctypes.c_double, c_void, c_void]
     lib.vpk_line_rating_batch.argtypes = [c_void, ctypes.c_int, c_void, c_void, ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                           c_void, c_void, c_void]
+    lib.vpk_overlay_lines_batch.argtypes = [c_void, ctypes.c_int] + [c_void] * 7
+    lib.vpk_overlay_markers_batch.argtypes = [c_void, ctypes.c_int] + [c_void] * 7
     _lib = lib
     return lib
 

@@ -22,6 +22,7 @@ UNITS = {
     "vpk_em.hip": ["-ffp-contract=off"],
     "vpk_prior.hip": ["-ffp-contract=off"],    # the prior's arithmetic is shared with the EM unit (prior_device.hpp)
     "vpk_lines.hip": ["-ffp-contract=off"],    # the pair functions likewise (line_device.hpp)
+    "vpk_overlay.hip": ["-ffp-contract=off"],  # the capsule distance is line_device.hpp's too (overlay_device.hpp)
     "vpk_cnn.hip": [],
     "vpk_raster.hip": ["-ffp-contract=off"],   # the curve samples must round like NumPy's separate ufunc calls
     "vpk_horizon.hip": ["-ffp-contract=off"],

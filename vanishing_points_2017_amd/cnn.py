@@ -106,6 +106,10 @@ class Net(object):
         rt = self.rt
         t = rt.torch
         batch = int(sphere.shape[0])
+        if f32 and sphere.is_cuda:
+            # a float tensor is usually the result of a conversion the caller has just enqueued on ITS stream; the handle's
+            # stream is non-blocking and would read it while it is still being written
+            rt.stream.wait_stream(t.cuda.current_stream(sphere.device))
         with rt.on_stream():
             if f32:             # (on the handle's stream: the forward is ordered behind the conversion)
                 sphere = sphere.to(device=rt.tdev, dtype=t.float32).contiguous()

@@ -98,6 +98,7 @@ struct vpk_handle {
     void* fe_ws = nullptr;
     size_t fe_ws_bytes = 0;
     vpk_staged lines_hdr;            // vpk_line_similarity_batch / vpk_line_rating_batch (vpk_lines.hip): the offsets
+    vpk_staged overlay_hdr;          // vpk_overlay_lines_batch / vpk_overlay_markers_batch (vpk_overlay.hip): sizes + offsets
 };
 
 int vpk_fail(vpk_handle* h, int code, const char* what);

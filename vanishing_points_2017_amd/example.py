@@ -1,4 +1,5 @@
-"""Single-image example with the reference's flags (example.py:11-14): --gpu, --show.
+"""Single-image example with the reference's flags (example.py:11-14): --gpu, --show; --save-overlays DIR writes what the
+reference's --show displays (example.py:82) as one image per input, headless (result_plotting.py).
 
 With --source_folder DIR (the reference uses assets/examples, example.py:26) the images of DIR go through the
 reference's three calls -- create_data_pickles(cnn_input_size=500, target_size=640), run_cnn, run_em (example.py:36-39)
@@ -10,6 +11,27 @@ import argparse
 import numpy as np
 
 from . import calc_horizon, cnn, evaluation, synth
+
+
+def save_overlay(directory, name, panels):
+    """One PNG per image under --save-overlays: the image panel (lines by VP, horizon)."""
+    import os
+    from PIL import Image
+    os.makedirs(directory, exist_ok=True)
+    out = os.path.join(directory, name + "_overlay.png")
+    Image.fromarray(panels['image']).save(out)
+    print("  overlay:", out)
+    return out
+
+
+def save_file_overlay(directory, image_file, datum, horizon_px=None, device=0):
+    """--save-overlays for one image of --source_folder (example.py:82, to a file instead of a window): the image scaled
+    to fit 640 like the front end's, its lines by VP and the horizon (pixel end points).  An image without vanishing
+    points gets its plain (resized) image, so that every input has an overlay."""
+    import os
+    from . import result_plotting
+    panels = result_plotting.show_em_result(datum, image_file, target_size=640, horizon=horizon_px, device=device)
+    return save_overlay(directory, os.path.splitext(os.path.basename(image_file))[0], panels)
 
 
 def run_folder(args):
@@ -38,6 +60,8 @@ def run_folder(args):
         print(image_file, "%d x %d, %d line segments" % (width, height, datum['lines']['line_segments'].shape[0]))
         if res is None or res['vp'] is None:
             print("  no vanishing points")
+            if args.save_overlays:
+                save_file_overlay(args.save_overlays, image_file, datum, None, args.gpu)
             continue
         hp1, hp2, _, _, _, _ = calc_horizon.calculate_horizon_and_ortho_vp(res, maxbest=20, theta_vmin=np.pi / 10.)
         scale = max(width, height)
@@ -46,6 +70,8 @@ def run_folder(args):
             hp[1] = -hp[1] * scale / 2.0 + height / 2.0
         print("  VPs: %d, iterations: %d, horizon: (%.1f, %.1f) - (%.1f, %.1f)" % (
             res['vp'].shape[0], res['iterations'], hp1[0], hp1[1], hp2[0], hp2[1]))
+        if args.save_overlays:
+            save_file_overlay(args.save_overlays, image_file, datum, (hp1, hp2), args.gpu)
     return dataset
 
 
@@ -53,6 +79,8 @@ def main(argv=None):
     p = argparse.ArgumentParser(description='')
     p.add_argument('--gpu', default=0, type=int, help='GPU ID to use')
     p.add_argument('--show', dest='show', action='store_true', help='Show results (prints only)')
+    p.add_argument('--save-overlays', dest='save_overlays', default=None, metavar='DIR',
+                   help='write one overlay per image to DIR: lines coloured by vanishing point and the horizon')
     p.add_argument('--seed', default=1000, type=int)
     p.add_argument('--lines', default=800, type=int)
     p.add_argument('--source_folder', default=None, help='folder with images (jpg / png / pgm)')
@@ -78,11 +106,17 @@ def main(argv=None):
     res = datum['EM_result']
     hp1, hp2, _, _, _, _ = calc_horizon.calculate_horizon_and_ortho_vp(res, maxbest=20, theta_vmin=np.pi / 10.)
     height, width = sc["image_shape"]
+    horizon = ((hp1[0], hp1[1]), (hp2[0], hp2[1]))      # normalised, before the conversion below
     for hp in (hp1, hp2):
         hp[0] = hp[0] * 640 / 2.0 + width / 2.0
         hp[1] = -hp[1] * 640 / 2.0 + height / 2.0
     print(hp1)
     print(hp2)
+    if args.save_overlays:                             # the synthetic scene has no photograph: its lines on black
+        from . import result_plotting
+        image = np.zeros((int(height), int(width), 3), dtype=np.uint8)
+        panels = result_plotting.render_em_result(datum, image, horizon=horizon, device=args.gpu)
+        save_overlay(args.save_overlays, "synthetic_seed%d" % args.seed, panels)
     print("VPs: %d, iterations: %d, inlier lines: %d / %d" % (res['vp'].shape[0], res['iterations'],
                                                            int((res['vp_assoc'] >= 0).sum()), args.lines))
 
