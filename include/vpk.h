@@ -547,6 +547,61 @@ int vpk_line_similarity_batch(vpk_handle* h, int batch, const int64_t* offsets, 
 int vpk_line_rating_batch(vpk_handle* h, int batch, const int64_t* offsets, const double* lp, int k1, int k2,
                           double sigma, double* lscore_out, double* langle_out, double* llen_out);
 
+/* ---- VP set maintenance outside the EM (batched; asynchronous on the handle's stream) --------------------- */
+/* The three entries run one operation on a caller-supplied VP set per image, one workgroup per image, through the EM
+ * workgroup's own device functions.  Images are concatenated: image b's lines are [line_offsets[b], line_offsets[b + 1])
+ * and its VPs [vp_offsets[b], vp_offsets[b + 1]) (host int64[batch + 1] each, not decreasing, M_b <= 64 else
+ * VPK_ERR_LIMIT before anything is launched); its (M_b x N_b) matrix (row stride N_b) starts at element
+ * sum_{a < b} M_a N_a.  Everything else is a device pointer.  batch = 0 does nothing; an image with N_b = 0 or M_b = 0
+ * gets no workgroup and none of its outputs is written.  batch < 0, malformed offsets and null buffers: VPK_ERR_ARG, and
+ * no output is touched. */
+/* replaces: calc_vp_line_counts -- vp_localisation.py:482-512, distance_measure "angle" -- for a batch.
+ *   lp sum(N) x 4, v sum(M) x 3, s sum(M), metric [m][n] per image, lweights sum(N)
+ *   vp_assoc_in  NULL (:486-487: the argmax of the metric over the VPs, first maximum, a NaN counts as the maximum) or
+ *                sum(N) int64: entries below 0 skip the line (:494) and come back unchanged; entries of M_b or more
+ *                (an IndexError in the reference) skip it and come back as -1.  With it metric may be NULL.
+ *   counts_out / counts_w_out sum(M) fp64, vp_assoc_out sum(N) int64 (-1 = outlier :504 or zero weight :506)
+ * The outlier test is dist > thresh * sqrt(s[m]) on the caller's s as it stands: where it is false because s[m] is NaN or
+ * negative the line counts.  counts_w is a sum in the EM's order (lanes over lines), not the reference's running sum. */
+int vpk_vp_line_counts_batch(vpk_handle* h, int batch, const int64_t* line_offsets, const int64_t* vp_offsets,
+                             const double* lp, const double* v, const double* s, const double* metric,
+                             const double* lweights, double thresh, const int64_t* vp_assoc_in, double* counts_out,
+                             double* counts_w_out, int64_t* vp_assoc_out);
+/* replaces: split_best_vp -- vp_localisation.py:527-630, numClusters = 2 -- for a batch, on slice i of the history array.
+ *   l sum(N) x 3 (normalised lines), w [m][n] per image (weightMatrix), lweight / langles sum(N), min_diff (:614)
+ *   v_out / s_out  (sum(M) + batch) x 3 / (sum(M) + batch): image b's rows start at vp_offsets[b] + b; M_b + 1 rows are
+ *                  written, rows past m_out[b] as zeros
+ *   m_out batch int32 (M_b or M_b + 1), split_out batch int32 (the VP that was split -- worstVP :561 -- or -1 when the
+ *   set is unchanged), flags_out batch uint32 (VPK_EM_FLAG_SPLIT_TIE, _SPLIT_DISCONNECTED, _VP_OVERFLOW)
+ *   labels_out  NULL or sum(N) int32: where a worst VP was found (:560), its lines' cluster labels (:578), -1 elsewhere
+ * Kept as the reference has them: the in-image test reads VP m, not worstVPs[m] (:557); a cluster of fewer than 3 lines
+ * yields no VP and one VP alone changes nothing (:592, :604-617).  A split of a 64-VP set raises VPK_EM_FLAG_VP_OVERFLOW
+ * and returns the set as it was.  N_b <= 32768 (VPK_ERR_LIMIT). */
+int vpk_vp_split_batch(vpk_handle* h, int batch, const int64_t* line_offsets, const int64_t* vp_offsets, const double* lp,
+                       const double* l, const double* v, const double* s, const double* w, const double* lweight,
+                       const double* langles, double min_diff, double* v_out, double* s_out, int32_t* m_out,
+                       int32_t* split_out, uint32_t* flags_out, int32_t* labels_out);
+
+/* replaces: merge_vps with calc_angle_to_other_vp -- vp_localisation.py:633-697, distance_measure "angle" -- for a
+ * batch, on slice i of the history array.  While the smallest angle between two VPs (the first row-major minimum of the
+ * M x M angle matrix, :647-653; the diagonal counts pi) is below thresh: calc_probabilities and weight_matrix of the whole
+ * set (:658-659, the EM's E-step and smoother), the new VP k from w[j] + w[k] (:661) and its variance (:663-666), VP j
+ * deleted (:674-675).  s[k] is written before the abort test (:666-668): a merge given up because the new VP is None or
+ * s[k] > max_stdd returns the changed s[k]; the E-step floors s at 1e-200 in place (probability_functions.py:139).
+ *   l sum(N) x 3 (normalised lines), lweight sum(N), lsim per image a plain N_b x N_b matrix (row stride N_b; what
+ *   vpk_line_similarity_batch writes) at element lsim_offsets[b] (host int64[batch + 1], at least N_b^2 apart)
+ *   prior_weights batch x 400 fp32 and prior_sigma: what vpk_prior_params returns and was given; at most 100 positive
+ *   cells are used, as pdf_params leaves them, more raise VPK_VPSET_FLAG_PRIOR_TRUNCATED
+ *   v_out sum(M) x 3, s_out sum(M), keep_out sum(M) int32: image b's rows start at vp_offsets[b]; m_out[b] rows are
+ *   the merged set and the indices its VPs had in the input, rows past it zeros and -1; m_out, flags_out batch
+ * llen, which the reference passes on to calc_probabilities, is not read by the "angle" measure and is not taken. */
+#define VPK_VPSET_FLAG_PRIOR_TRUNCATED 8u
+int vpk_vp_merge_batch(vpk_handle* h, int batch, const int64_t* line_offsets, const int64_t* vp_offsets, const double* lp,
+                       const double* l, const double* v, const double* s, const double* lweight,
+                       const int64_t* lsim_offsets, const double* lsim, double wbias, const float* prior_weights,
+                       double prior_sigma, double thresh, double max_stdd, double* v_out, double* s_out, int32_t* m_out,
+                       int32_t* keep_out, uint32_t* flags_out);
+
 /* ---- result overlays (batched; asynchronous on the handle's stream) ---------------------------------------- */
 /* Both entries blend primitives into 8-bit RGB images in place, by the renderer of DESIGN section 7d: a primitive of width
  * w covers the points within w / 2 of its closed segment (a capsule; a disc when the segment has no length), coverage of

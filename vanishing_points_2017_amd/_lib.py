@@ -72,6 +72,7 @@ EXPORTS = [
     "vpk_prior_params", "vpk_mixture_pdf",
     "vpk_line_similarity_batch", "vpk_line_rating_batch",
     "vpk_overlay_lines_batch", "vpk_overlay_markers_batch",
+    "vpk_vp_line_counts_batch", "vpk_vp_split_batch", "vpk_vp_merge_batch",
 ]
 
 _lib = None
@@ -163,6 +164,10 @@ def load():
                                           c_void, c_void, c_void]
     lib.vpk_overlay_lines_batch.argtypes = [c_void, ctypes.c_int] + [c_void] * 7
     lib.vpk_overlay_markers_batch.argtypes = [c_void, ctypes.c_int] + [c_void] * 7
+    lib.vpk_vp_line_counts_batch.argtypes = [c_void, ctypes.c_int] + [c_void] * 7 + [ctypes.c_double] + [c_void] * 4
+    lib.vpk_vp_split_batch.argtypes = [c_void, ctypes.c_int] + [c_void] * 9 + [ctypes.c_double] + [c_void] * 6
+    lib.vpk_vp_merge_batch.argtypes = [c_void, ctypes.c_int] + [c_void] * 9 + [ctypes.c_double, c_void] + \
+                                      [ctypes.c_double] * 3 + [c_void] * 5
     _lib = lib
     return lib
 

@@ -23,6 +23,7 @@ UNITS = {
     "vpk_prior.hip": ["-ffp-contract=off"],    # the prior's arithmetic is shared with the EM unit (prior_device.hpp)
     "vpk_lines.hip": ["-ffp-contract=off"],    # the pair functions likewise (line_device.hpp)
     "vpk_overlay.hip": ["-ffp-contract=off"],  # the capsule distance is line_device.hpp's too (overlay_device.hpp)
+    "vpk_vpset.hip": ["-ffp-contract=off"],    # the EM's own phase functions on a caller's VP set (vpset_device.hpp)
     "vpk_cnn.hip": [],
     "vpk_raster.hip": ["-ffp-contract=off"],   # the curve samples must round like NumPy's separate ufunc calls
     "vpk_horizon.hip": ["-ffp-contract=off"],

@@ -2022,7 +2022,7 @@ VPK_DEV double max_err_of(const Shared& sh, int M) {
 // ---------------------------------------------------------------------------------------------
 // merge_vps (vp_localisation.py:633-697)
 // ---------------------------------------------------------------------------------------------
-VPK_DEVFN void merge_vps(EmCtx& c, bool use_next, double thresh) {
+VPK_DEVFN void merge_vps(EmCtx& c, bool use_next, double thresh, double max_stdd) {
     Shared& sh = SH();
     const int N = c.N;
     for (int guard = 0; guard < 4 * MAXM; ++guard) {
@@ -2066,7 +2066,7 @@ VPK_DEVFN void merge_vps(EmCtx& c, bool use_next, double thresh) {
             if (lane() == 0) {
                 double sk = exp(log(sv) - log(sp));
                 sh.s[k] = sk;                                 // :666 written BEFORE the abort test
-                int ok = valid && !(sk > 0.01);               // :668 (max_stdd = 0.01)
+                int ok = valid && !(sk > max_stdd);           // :668 (the EM passes the default, 0.01)
                 if (ok) {
                     double sg = sign_np(vp[2]);
                     X[3 * k] = vp[0] * sg; X[3 * k + 1] = vp[1] * sg; X[3 * k + 2] = vp[2] * sg;   // :672
@@ -2692,7 +2692,7 @@ VPK_DEVFN int em_run(EmCtx& c, EmOut& o, EmSlice& sl) {
         //  1e-200, cannot change s after the clamp at :307)
 
         if (max_err < P.final_convergence || i == P.num_iter - 1 || !P.do_iterations) {   // :335
-            if (P.do_merge) merge_vps(c, true, merge_thresh_final);                       // :339
+            if (P.do_merge) merge_vps(c, true, merge_thresh_final, 0.01);                 // :339
             trace_put(o, P.num_iter, 3, (double)sh.M);        // finalisation audit trail: M after merge
             if (sh.M == 0) { write_result(c, o, VPK_EM_NO_VP, i); return EM_DONE; }   // reference: argmax of empty (:349)
             estep(c, sh.cur);                                 // :344 (stale index i)
@@ -2751,7 +2751,7 @@ VPK_DEVFN int em_run(EmCtx& c, EmOut& o, EmSlice& sl) {
         if (i % P.split_merge_freq == 0 && i > 0 && i <= split_merge_it + P.split_merge_freq && P.do_merge) {
             int mb = sh.M;
             lap(tk);
-            merge_vps(c, true, P.merge_thresh);               // :444-448
+            merge_vps(c, true, P.merge_thresh, 0.01);         // :444-448
             trace_put(o, i, 11, lap(tk));
             if (sh.M != mb) events += 4;
         }

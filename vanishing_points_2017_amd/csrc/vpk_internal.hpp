@@ -99,6 +99,10 @@ struct vpk_handle {
     size_t fe_ws_bytes = 0;
     vpk_staged lines_hdr;            // vpk_line_similarity_batch / vpk_line_rating_batch (vpk_lines.hip): the offsets
     vpk_staged overlay_hdr;          // vpk_overlay_lines_batch / vpk_overlay_markers_batch (vpk_overlay.hip): sizes + offsets
+    vpk_staged vpset_hdr;            // vpk_vp_line_counts_batch / vpk_vp_split_batch (vpk_vpset.hip): offsets + active images
+    void* vpset_ws = nullptr;        // their per-image workspace (grown on demand)
+    size_t vpset_ws_bytes = 0;
+    bool vpset_ready = false;        // dynamic-LDS attribute set on the kernel
 };
 
 int vpk_fail(vpk_handle* h, int code, const char* what);

@@ -56,7 +56,8 @@ def _prims(geom, rgba, width, cols):
 def line_primitives(datum, width, height, maxbest=4, horizon_px=None):
     """The image panel's draw list (:53-107): (seg_px (P, 4), rgba (P, 4), width (P,)).  Every line whose vp_assoc is one
     of the best VPs, in line index order, in that VP's colour (lines of no VP, -1, or of a VP outside the best set are
-    not drawn); then the horizon, two end points in pixel coordinates, in cyan."""
+    not drawn); then the horizon, two end points in pixel coordinates, in cyan.  The counts and vp_assoc of
+    vp_localisation.calc_vp_line_counts, for any line set and VPs of the caller's, are an EM_result for this."""
     if datum.get('lines') is None:                               # :60-61 (raised, not asserted: python -O keeps it)
         raise AssertionError("the datum has no 'lines'")
     em_result = datum.get('EM_result')

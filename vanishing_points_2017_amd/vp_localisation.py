@@ -12,11 +12,16 @@ functions with sigma = 1 and k2 = 4 (:178, :230); the defaults here are the refe
 Thin mirrors of entry points the EM's unit tests already use: find_initial_vps (:111-165, vpk_init_vps), weight_matrix
 (:515-524, vpk_weight_matrix) and calc_new_vanishing_point (:453-479, vpk_mstep).
 
-Not here: calc_vp_line_counts, split_best_vp and merge_vps (they live inside the EM workgroup; kernels.line_counts and
-kernels.cluster2 are their fine-grained entries), the scalar pair helpers (lines_similarity, lines_proximity,
-lines_points_cosangle, line_distance_closest, line_segment_point_distance: device functions of csrc/line_device.hpp) and
-the distance measures other than "angle".  There is no host fallback: without the library and a GPU every call but
-line_length raises."""
+VP set maintenance (vpk_vp_line_counts_batch, vpk_vp_split_batch, vpk_vp_merge_batch; include/vpk.h): calc_vp_line_counts
+(:482-512), split_best_vp (:527-630) and merge_vps (:633-684) on a VP set of the caller's, through the EM workgroup's own
+device functions; calc_angle_to_other_vp (:687-697) on the host.  The ``*_batch`` forms take many images per launch and
+return device tensors.  Deliberate differences from the reference: the caller's ``v``, ``s`` and ``vp_assoc`` arrays are
+not modified (the reference writes into them; the results are new arrays); ``distance_measure`` other than "angle",
+``numClusters`` other than 2 and more than 64 VPs raise ValueError.
+
+Not here: the scalar pair helpers (lines_similarity, lines_proximity, lines_points_cosangle, line_distance_closest,
+line_segment_point_distance: device functions of csrc/line_device.hpp) and the distance measures other than "angle".
+There is no host fallback: without the library and a GPU every call but line_length and calc_angle_to_other_vp raises."""
 import numpy as np
 
 from . import em as _em
@@ -218,3 +223,320 @@ def calc_new_vanishing_point(l, w, device=0):
         return None
     vp, valid = _kernels.mstep(l, w[None, :], device=device)
     return vp[0] if valid[0] else None
+
+
+# ---- VP set maintenance ---------------------------------------------------------------------------------------------------
+MAX_VP = _em.MAX_VP                     # 64: capacity of the EM workgroup's VP arrays
+VP_FLAG_SPLIT_TIE, VP_FLAG_SPLIT_DISCONNECTED, VP_FLAG_OVERFLOW, VP_FLAG_PRIOR_TRUNCATED = 1, 2, 4, 8   # include/vpk.h
+
+
+def _check_measure(distance_measure):
+    if distance_measure != "angle":
+        raise ValueError("distance_measure %r is not supported: only \"angle\" runs on the GPU" % (distance_measure,))
+
+
+def _offsets_of(sizes):
+    return np.concatenate(([0], np.cumsum(sizes, dtype=np.int64))).astype(np.int64)
+
+
+def _check_offsets(off, total, what):
+    off = host_i64(off)
+    if off.ndim != 1 or off.shape[0] < 1 or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != total:
+        raise ValueError("%s offsets must rise from 0 to %d" % (what, total))
+    return off
+
+
+def _cat(rt, x, dtype, tail=()):
+    """A list of per-image arrays or tensors, or one concatenated array or tensor, as one contiguous device tensor of
+    shape (-1,) + tail.  The caller's data is only read."""
+    t = rt.torch
+    if isinstance(x, (list, tuple)):
+        if len(x) and isinstance(x[0], t.Tensor):
+            x = t.cat([a.to(device=rt.tdev, dtype=dtype).reshape((-1,) + tail) for a in x])
+        else:
+            npd = {t.float64: np.float64, t.float32: np.float32, t.int64: np.int64}[dtype]
+            arrs = [np.ascontiguousarray(a, dtype=npd).reshape((-1,) + tail) for a in x]
+            x = np.concatenate(arrs) if arrs else np.zeros((0,) + tail, dtype=npd)
+    if not isinstance(x, t.Tensor):
+        x = t.from_numpy(np.ascontiguousarray(x))
+    return x.to(device=rt.tdev, dtype=dtype).contiguous().reshape((-1,) + tail)
+
+
+def _sizes(x, offsets, what):
+    """Host int64 offsets of a batch given as a list (sizes from the list) or concatenated (offsets from the caller)."""
+    if isinstance(x, (list, tuple)):
+        return _offsets_of([int(a.shape[0]) if hasattr(a, 'shape') else len(a) for a in x])
+    if offsets is None:
+        raise ValueError("%s is one concatenated array: its offsets are needed" % what)
+    return _check_offsets(offsets, int(x.shape[0]), what)
+
+
+def _check_vp_limit(vp_off):
+    m = np.diff(vp_off)
+    if m.size and m.max() > MAX_VP:
+        raise ValueError("%d VPs: at most %d are supported" % (m.max(), MAX_VP))
+
+
+def calc_vp_line_counts_batch(vps, lps, ss, decision_metrics, lweights, distance_measure="angle", thresh=2.57,
+                              vp_assocs=None, line_offsets=None, vp_offsets=None, device=0):
+    """calc_vp_line_counts for many images in one launch.  Every argument is a list with one array per image -- vp (M_b, 3),
+    lp (N_b, 4), s (M_b,), decision_metric (M_b, N_b), lweights (N_b,), vp_assoc (N_b,) int64 -- or one concatenated
+    array / device tensor with ``line_offsets`` / ``vp_offsets`` (host int64, B + 1); the metrics are then concatenated
+    flat, image after image.  Returns (counts, counts_weighted, vp_assoc, line_offsets, vp_offsets): device tensors of
+    sum M, sum M and sum N (int64) elements.  An image without lines counts nothing; one without VPs associates nothing."""
+    _check_measure(distance_measure)
+    lo = _sizes(lps, line_offsets, "lps")
+    vo = _sizes(vps, vp_offsets, "vps")
+    if lo.shape != vo.shape:
+        raise ValueError("lps and vps describe %d and %d images" % (lo.shape[0] - 1, vo.shape[0] - 1))
+    _check_vp_limit(vo)
+    rt = _runtime(device)
+    t = rt.torch
+    with rt.on_stream():
+        d_lp = _cat(rt, lps, t.float64, (4,))
+        d_v = _cat(rt, vps, t.float64, (3,))
+        d_s = _cat(rt, ss, t.float64)
+        d_lw = _cat(rt, lweights, t.float64)
+        d_w = _cat(rt, decision_metrics, t.float64) if decision_metrics is not None else None
+        d_ain = _cat(rt, vp_assocs, t.int64) if vp_assocs is not None else None
+        if d_w is None and d_ain is None:
+            raise ValueError("decision_metrics or vp_assocs is needed")
+        need = int((np.diff(lo) * np.diff(vo)).sum())
+        if d_w is not None and d_w.shape[0] != need:
+            raise ValueError("the decision metrics hold %d elements, the images' M x N sum to %d" % (d_w.shape[0], need))
+        for a, n, what in ((d_s, vo[-1], "ss"), (d_lw, lo[-1], "lweights"), (d_ain, lo[-1], "vp_assocs")):
+            if a is not None and a.shape[0] != n:
+                raise ValueError("%s holds %d elements, expected %d" % (what, a.shape[0], n))
+        counts = t.zeros((int(vo[-1]),), dtype=t.float64, device=rt.tdev)
+        counts_w = t.zeros_like(counts)
+        assoc = d_ain.clone() if d_ain is not None else t.full((int(lo[-1]),), -1, dtype=t.int64, device=rt.tdev)
+        rt.check(rt.lib.vpk_vp_line_counts_batch(rt.h, lo.shape[0] - 1, _off_ptr(lo), _off_ptr(vo), rt.ptr(d_lp), rt.ptr(d_v),
+                                                 rt.ptr(d_s), rt.ptr(d_w), rt.ptr(d_lw), float(thresh), rt.ptr(d_ain),
+                                                 rt.ptr(counts), rt.ptr(counts_w), rt.ptr(assoc)))
+    rt.synchronize()
+    return counts, counts_w, assoc, lo, vo
+
+
+def calc_vp_line_counts(vp, l, lp, s, decision_metric, lweights, distance_measure, thresh=2.57, vp_assoc=None, device=0):
+    """calc_vp_line_counts (:482-512): (counts, counts_weighted, vp_assoc) of the lines ``lp`` against the VPs ``vp`` with
+    variances ``s``.  ``vp_assoc`` None: every line goes to the argmax of ``decision_metric`` (M, N) over the VPs (:487);
+    given, entries below 0 skip their line (:494).  A line farther than thresh * sqrt(s[m]) from its VP (:504) or of
+    weight 0 (:506) gets -1.  ``l`` is not read by the "angle" measure.  The result's vp_assoc is a new int64 array: the
+    caller's is not written.  It is what result_plotting.line_primitives takes as a datum's ``vp_assoc``."""
+    _check_measure(distance_measure)
+    vp = np.asarray(vp, dtype=np.float64).reshape(-1, 3)
+    lp = _check_lp(lp)
+    if vp.shape[0] > MAX_VP:
+        raise ValueError("%d VPs: at most %d are supported" % (vp.shape[0], MAX_VP))
+    if vp_assoc is None:
+        if vp.shape[0] == 0 and lp.shape[0] > 0:
+            raise ValueError("attempt to get argmax of an empty sequence")      # np.argmax at :487
+        assocs = None
+    else:
+        vp_assoc = np.asarray(vp_assoc)
+        if vp_assoc.size and vp_assoc.max() >= vp.shape[0]:
+            raise IndexError("vp_assoc names VP %d of %d" % (vp_assoc.max(), vp.shape[0]))      # vp[m] at :498
+        assocs = [vp_assoc.astype(np.int64)]
+    metrics = None if decision_metric is None else [np.asarray(decision_metric, dtype=np.float64).reshape(vp.shape[0], -1)]
+    c, cw, a, _, _ = calc_vp_line_counts_batch([vp], [lp], [np.asarray(s, dtype=np.float64)], metrics,
+                                               [np.asarray(lweights, dtype=np.float64)], thresh=thresh, vp_assocs=assocs,
+                                               device=device)
+    return c.cpu().numpy(), cw.cpu().numpy(), a.cpu().numpy()
+
+
+def split_best_vp_batch(vs, ss, linePoints, lines, weightMatrices, lineWeights, lineAngles, numClusters=2, min_diff=0.0001,
+                        line_offsets=None, vp_offsets=None, device=0):
+    """split_best_vp on slice i of many images' history arrays in one launch; arguments as in calc_vp_line_counts_batch
+    (vs: (M_b, 3) each, weightMatrices (M_b, N_b), lines (N_b, 3)).  Returns a dict of device tensors: 'v' (sum M + B, 3)
+    and 's' (sum M + B): image b's rows start at vp_offsets[b] + b, 'num_vp' (B,) of them are its set, the rest zeros;
+    'split' (B,) int32: the VP that was split or -1; 'flags' (B,) int32 (VP_FLAG_*); 'labels' (sum N,) int32: the cluster of
+    every line of the worst VP, -1 elsewhere; and the host offsets 'line_offsets', 'vp_offsets', 'out_offsets'."""
+    if numClusters != 2:
+        raise ValueError("numClusters = %r: only 2 is supported" % (numClusters,))
+    lo = _sizes(linePoints, line_offsets, "linePoints")
+    vo = _sizes(vs, vp_offsets, "vs")
+    if lo.shape != vo.shape:
+        raise ValueError("linePoints and vs describe %d and %d images" % (lo.shape[0] - 1, vo.shape[0] - 1))
+    _check_vp_limit(vo)
+    B = lo.shape[0] - 1
+    rt = _runtime(device)
+    t = rt.torch
+    with rt.on_stream():
+        d_lp = _cat(rt, linePoints, t.float64, (4,))
+        d_l = _cat(rt, lines, t.float64, (3,))
+        d_v = _cat(rt, vs, t.float64, (3,))
+        d_s = _cat(rt, ss, t.float64)
+        d_w = _cat(rt, weightMatrices, t.float64)
+        d_lw = _cat(rt, lineWeights, t.float64)
+        d_la = _cat(rt, lineAngles, t.float64)
+        if d_w.shape[0] != int((np.diff(lo) * np.diff(vo)).sum()):
+            raise ValueError("the weight matrices do not hold the images' M x N elements")
+        for a, n, what in ((d_l, lo[-1], "lines"), (d_s, vo[-1], "ss"), (d_lw, lo[-1], "lineWeights"), (d_la, lo[-1], "lineAngles")):
+            if a.shape[0] != n:
+                raise ValueError("%s holds %d rows, expected %d" % (what, a.shape[0], n))
+        oo = vo + np.arange(B + 1, dtype=np.int64)
+        v_out = t.zeros((int(oo[-1]), 3), dtype=t.float64, device=rt.tdev)
+        s_out = t.zeros((int(oo[-1]),), dtype=t.float64, device=rt.tdev)
+        num = t.from_numpy(np.diff(vo).astype(np.int32)).to(rt.tdev)
+        for b in np.nonzero((np.diff(lo) == 0) & (np.diff(vo) > 0))[0]:      # no lines: the set as it came
+            v_out[int(oo[b]):int(oo[b]) + int(vo[b + 1] - vo[b])] = d_v[int(vo[b]):int(vo[b + 1])]
+            s_out[int(oo[b]):int(oo[b]) + int(vo[b + 1] - vo[b])] = d_s[int(vo[b]):int(vo[b + 1])]
+        split = t.full((B,), -1, dtype=t.int32, device=rt.tdev)
+        flags = t.zeros((B,), dtype=t.int32, device=rt.tdev)
+        labels = t.full((int(lo[-1]),), -1, dtype=t.int32, device=rt.tdev)
+        rt.check(rt.lib.vpk_vp_split_batch(rt.h, B, _off_ptr(lo), _off_ptr(vo), rt.ptr(d_lp), rt.ptr(d_l), rt.ptr(d_v),
+                                           rt.ptr(d_s), rt.ptr(d_w), rt.ptr(d_lw), rt.ptr(d_la), float(min_diff), rt.ptr(v_out),
+                                           rt.ptr(s_out), rt.ptr(num), rt.ptr(split), rt.ptr(flags), rt.ptr(labels)))
+    rt.synchronize()
+    return {'v': v_out, 's': s_out, 'num_vp': num, 'split': split, 'flags': flags, 'labels': labels,
+            'line_offsets': lo, 'vp_offsets': vo, 'out_offsets': oo}
+
+
+def _history(v, s, i):
+    v = np.asarray(v, dtype=np.float64)
+    if v.ndim != 3 or v.shape[2] != 3:
+        raise ValueError("v must be the (T, M, 3) history array (got shape %r)" % (v.shape,))
+    s = np.asarray(s, dtype=np.float64).reshape(-1)
+    if s.shape[0] != v.shape[1]:
+        raise ValueError("s holds %d variances for %d VPs" % (s.shape[0], v.shape[1]))
+    if v.shape[1] > MAX_VP:
+        raise ValueError("%d VPs: at most %d are supported" % (v.shape[1], MAX_VP))
+    return v, s, v[i]
+
+
+def split_best_vp(i, v, s, linePoints, lines, weightMatrix, lineWeights, lineAngles, numClusters=2, min_diff=0.0001, device=0):
+    """split_best_vp (:527-630) on slice ``i`` of the (T, M, 3) history array ``v``: {'v', 's'}.  Where the worst VP is
+    split, 'v' has one more VP: a zero column appended to every slice, and only slice i written (:626-628).  Returned
+    arrays are new; the caller's v and s are not written."""
+    if numClusters != 2:
+        raise ValueError("numClusters = %r: only 2 is supported" % (numClusters,))
+    v, s, vi = _history(v, s, i)
+    M = v.shape[1]
+    lp = _check_lp(linePoints)
+    if M == 0 or lp.shape[0] == 0:
+        return {'v': v.copy(), 's': s.copy()}
+    r = split_best_vp_batch([vi], [s], [lp], [np.asarray(lines, dtype=np.float64)],
+                            [np.asarray(weightMatrix, dtype=np.float64).reshape(M, -1)], [lineWeights], [lineAngles],
+                            min_diff=min_diff, device=device)
+    if int(r['split'][0]) < 0:
+        return {'v': v.copy(), 's': s.copy()}
+    v2 = np.append(v, np.zeros((v.shape[0], 1, 3)), axis=1)
+    v2[i] = r['v'].cpu().numpy()[:M + 1]
+    return {'v': v2, 's': r['s'].cpu().numpy()[:M + 1]}
+
+
+def _lsim_layout(rt, lsims, sizes):
+    """(device tensor, host element offsets) of the images' N x N matrices.  A list of views into one allocation in rising
+    order -- what calc_lsim_batch returns -- is used where it lies; anything else is concatenated on the device."""
+    t = rt.torch
+    if isinstance(lsims, (list, tuple)) and len(lsims) and all(isinstance(a, t.Tensor) and a.is_cuda and a.dtype == t.float64
+                                                                 and a.is_contiguous() for a in lsims):
+        full = [a for a in lsims if a.numel()]                   # (an empty view has no address)
+        if full:
+            base, off, pos, ok = full[0].data_ptr(), [], 0, True
+            for a, n in zip(lsims, sizes):
+                o = (a.data_ptr() - base) // 8 if a.numel() else pos
+                ok = ok and o >= pos and (not a.numel() or a.untyped_storage().data_ptr() == full[0].untyped_storage().data_ptr())
+                off.append(o)
+                pos = o + int(n) * int(n)
+            if ok:
+                return (base, full[0]), host_i64(off + [pos])
+    d = _cat(rt, lsims, t.float64)
+    return (d.data_ptr(), d), _offsets_of(sizes * sizes)
+
+
+def merge_vps_batch(vs, ss, ls, thresh, lweights, lsims, wbias, pdfpar, lps, llens=None, distance_measure="angle",
+                    max_stdd=0.01, outlier_stdd=1e-6, line_offsets=None, vp_offsets=None, device=0):
+    """merge_vps on slice i of many images' history arrays in one launch; arguments as in calc_vp_line_counts_batch (vs:
+    (M_b, 3) each, ls (N_b, 3) normalised lines).  ``lsims``: the images' plain (N_b, N_b) matrices as a list -- the
+    list calc_lsim_batch returns is used where it lies -- or concatenated flat.  ``pdfpar``: PDFParams with weights (B, 400),
+    as pdf_params_batch returns.  ``llens`` is not read by the "angle" measure.  Returns a dict of device tensors: 'v'
+    (sum M, 3), 's' (sum M,) and 'kept' (sum M,) int32: image b's rows start at vp_offsets[b], 'num_vp' (B,) of them are the
+    merged set and the indices its VPs came with, the rest zeros and -1; 'flags' (B,) int32; and the host offsets.
+
+    Everything may stay on the device:
+
+        lscore, langle, llen, off = line_geometry_batch((d_lp, off), k1=10, k2=4)
+        lsims = calc_lsim_batch((d_lp, off), sigma=1)
+        par = pdf_params_batch(d_maps)
+        r = merge_vps_batch(d_v, d_s, d_l, 1e-3, llen * lscore.clamp(0.2, 1), lsims, 1, par, d_lp,
+                            line_offsets=off, vp_offsets=vp_off)"""
+    _check_measure(distance_measure)
+    lo = _sizes(lps, line_offsets, "lps")
+    vo = _sizes(vs, vp_offsets, "vs")
+    if lo.shape != vo.shape:
+        raise ValueError("lps and vs describe %d and %d images" % (lo.shape[0] - 1, vo.shape[0] - 1))
+    _check_vp_limit(vo)
+    B = lo.shape[0] - 1
+    rt = _runtime(device)
+    t = rt.torch
+    with rt.on_stream():
+        d_lp = _cat(rt, lps, t.float64, (4,))
+        d_l = _cat(rt, ls, t.float64, (3,))
+        d_v = _cat(rt, vs, t.float64, (3,))
+        d_s = _cat(rt, ss, t.float64)
+        d_lw = _cat(rt, lweights, t.float64)
+        (lsim_ptr, lsim_keep), lsim_off = _lsim_layout(rt, lsims, np.diff(lo))
+        if lsim_off.shape[0] != B + 1 or (np.diff(lsim_off) < np.diff(lo) ** 2).any():
+            raise ValueError("lsims must hold one N x N matrix per image")
+        d_pw = _cat(rt, pdfpar.weights, t.float32, (400,))
+        if d_pw.shape[0] != B:
+            raise ValueError("pdfpar.weights must be (%d, 400), one row per image" % B)
+        for a, n, what in ((d_l, lo[-1], "ls"), (d_s, vo[-1], "ss"), (d_lw, lo[-1], "lweights")):
+            if a.shape[0] != n:
+                raise ValueError("%s holds %d rows, expected %d" % (what, a.shape[0], n))
+        v_out = d_v.clone()
+        s_out = d_s.clone()
+        num = t.from_numpy(np.diff(vo).astype(np.int32)).to(rt.tdev)
+        kept = t.cat([t.arange(int(m), dtype=t.int32, device=rt.tdev) for m in np.diff(vo)]) if B else \
+            t.zeros((0,), dtype=t.int32, device=rt.tdev)
+        flags = t.zeros((B,), dtype=t.int32, device=rt.tdev)
+        import ctypes
+        rt.check(rt.lib.vpk_vp_merge_batch(rt.h, B, _off_ptr(lo), _off_ptr(vo), rt.ptr(d_lp), rt.ptr(d_l), rt.ptr(d_v),
+                                           rt.ptr(d_s), rt.ptr(d_lw), _off_ptr(lsim_off), ctypes.c_void_p(lsim_ptr), float(wbias),
+                                           rt.ptr(d_pw), float(pdfpar.sigma), float(thresh), float(max_stdd), rt.ptr(v_out),
+                                           rt.ptr(s_out), rt.ptr(num), rt.ptr(kept), rt.ptr(flags)))
+    rt.synchronize()
+    del lsim_keep
+    return {'v': v_out, 's': s_out, 'num_vp': num, 'kept': kept, 'flags': flags, 'line_offsets': lo, 'vp_offsets': vo}
+
+
+def merge_vps(i, v, s, l, thresh, lweight, lsim, wbias, pdfpar, lp, llen, distance_measure, max_stdd=0.01, outlier_stdd=1e-6,
+              device=0):
+    """merge_vps (:633-684) on slice ``i`` of the (T, M, 3) history array ``v``: {'v', 's'}.  While the two closest VPs
+    are closer than ``thresh``, they are merged into the second (column j is deleted from every slice, :674) until a merge
+    is given up (new VP None, or s[k] > max_stdd -- s[k] is returned as changed, :666-668).  ``pdfpar`` is what this
+    package's pdf_params returns.  Returned arrays are new; the caller's v and s are not written."""
+    _check_measure(distance_measure)
+    v, s, vi = _history(v, s, i)
+    M = v.shape[1]
+    lp = _check_lp(lp)
+    if M <= 1 or lp.shape[0] == 0:
+        return {'v': v.copy(), 's': s.copy()}
+    from .probability_functions import PDFParams, _grid_means
+    if not np.array_equal(np.asarray(pdfpar.means), _grid_means()):
+        raise ValueError("pdfpar.means must be the 20 x 20 grid of pdf_params")
+    w = np.asarray(pdfpar.weights, dtype=np.float32).reshape(1, -1)
+    if w.shape[1] != 400 or (w > 0).sum() > 100:
+        raise ValueError("pdfpar.weights must be pdf_params' 400 cell weights, at most 100 of them positive")
+    N = lp.shape[0]
+    r = merge_vps_batch([vi], [s], [np.asarray(l, dtype=np.float64)], thresh, [lweight],
+                        [np.asarray(lsim, dtype=np.float64).reshape(N, N)], wbias,
+                        PDFParams(means=None, weights=w, sigma=pdfpar.sigma), [lp], max_stdd=max_stdd, device=device)
+    m = int(r['num_vp'][0])
+    kept = r['kept'].cpu().numpy()[:m]
+    v2 = v[:, kept, :].copy()
+    v2[i] = r['v'].cpu().numpy()[:m]
+    return {'v': v2, 's': r['s'].cpu().numpy()[:m]}
+
+
+def calc_angle_to_other_vp(v, i, k):
+    """calc_angle_to_other_vp (:687-697), on the host: the angles of VP k of slice i against every VP of the slice, pi
+    for itself -- and the scalar pi where squeezing leaves a single VP (:693-694)."""
+    vi = np.asarray(v)[i]
+    d = np.dot(np.squeeze(vi), np.squeeze(vi[k]).T)
+    ang = np.abs(np.arccos(np.clip(np.abs(np.clip(d, -1, 1)), -1, 1)))
+    if np.ndim(ang) == 0:
+        return np.pi
+    ang[k] = np.pi
+    return ang
