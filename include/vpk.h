@@ -602,6 +602,33 @@ int vpk_vp_merge_batch(vpk_handle* h, int batch, const int64_t* line_offsets, co
                        double prior_sigma, double thresh, double max_stdd, double* v_out, double* s_out, int32_t* m_out,
                        int32_t* keep_out, uint32_t* flags_out);
 
+/* ---- the E-step outside the EM (batched; asynchronous on the handle's stream) ---------------------------- */
+/* replaces: calc_probabilities -- probability_functions.py:99-120 -- after its prior (calc_angles and calc_pdf, :104-105:
+ * vpk_mixture_pdf with pts_dim = 3 gives p_v and the angles), with calc_plv (:133-147), calc_pvl (:123-130) and the three
+ * distance measures calc_lvsq_angle (:157-176), calc_lvsq_dotprod (:150-154) and calc_lvsq_area (:179-209), for a ragged
+ * batch.  Images are concatenated as for the VP set entries above: image b's lines are [line_offsets[b],
+ * line_offsets[b + 1]) and its VPs [vp_offsets[b], vp_offsets[b + 1]) (host int64[batch + 1] each, not decreasing, the
+ * first not below 0; any M_b); its (M_b x N_b) matrices (row stride N_b) start at element sum_{a < b} M_a N_a.
+ * Everything else is a device pointer.
+ *   lp  sum(N) x 4     l  sum(N) x 3, read by VPK_DIST_DOTPROD only (else it may be NULL)     v  sum(M) x 3     s  sum(M)
+ *   p_v sum(M): the prior of every VP; may be NULL when neither p_l_out nor p_vl_out is given
+ *   s_floored_out sum(M): max(s, 1e-200) with a NaN replaced too (:139 writes this into the caller's s; s itself is only read)
+ *   lvsq_out / p_lv_out / p_vl_out  [m][n] per image     p_l_out sum(N)
+ *   Every output may be NULL and is then not computed.
+ * angle: the EM's expression, bit for bit.  dotprod: lv = (l0 v0 + l1 v1) + l2 v2 on v as given.  area: as the reference
+ * has it -- np.cross takes the 2-vector v_ as (vx, vy, 0), so the distance is measured from the line through the segment's
+ * MIDPOINT in direction v_; a negative radicand at :205 gives NaN.  p_l is one sum over the VPs in ascending order, floored
+ * at 1e-12 (:117, a NaN passes).  One thread per line, 64 lines per workgroup, the VPs' values staged 128 at a time; when
+ * neither p_l_out nor p_vl_out is given the grid also splits the VP range, and the bits are the same.
+ * batch = 0 does nothing; an image with N_b = 0 or M_b = 0 gets no workgroup and none of its outputs is written.  batch < 0,
+ * malformed offsets and an unknown measure: VPK_ERR_ARG.  lp, v, s (and l, p_v where the call reads them) are required
+ * only when there is work to do -- an image with lines and VPs, and an output that is not NULL: then a null one is
+ * VPK_ERR_ARG; a call with nothing to do returns VPK_OK whatever they are.  No error case touches an output. */
+enum vpk_dist_measure { VPK_DIST_ANGLE = 0, VPK_DIST_DOTPROD = 1, VPK_DIST_AREA = 2 };
+int vpk_estep_batch(vpk_handle* h, int batch, const int64_t* line_offsets, const int64_t* vp_offsets, const double* lp,
+                    const double* l, const double* v, const double* s, const double* p_v, int measure,
+                    double* s_floored_out, double* lvsq_out, double* p_lv_out, double* p_l_out, double* p_vl_out);
+
 /* ---- result overlays (batched; asynchronous on the handle's stream) ---------------------------------------- */
 /* Both entries blend primitives into 8-bit RGB images in place, by the renderer of DESIGN section 7d: a primitive of width
  * w covers the points within w / 2 of its closed segment (a capsule; a disc when the segment has no length), coverage of

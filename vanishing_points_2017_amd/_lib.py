@@ -73,6 +73,7 @@ EXPORTS = [
     "vpk_line_similarity_batch", "vpk_line_rating_batch",
     "vpk_overlay_lines_batch", "vpk_overlay_markers_batch",
     "vpk_vp_line_counts_batch", "vpk_vp_split_batch", "vpk_vp_merge_batch",
+    "vpk_estep_batch",
 ]
 
 _lib = None
@@ -168,6 +169,7 @@ def load():
     lib.vpk_vp_split_batch.argtypes = [c_void, ctypes.c_int] + [c_void] * 9 + [ctypes.c_double] + [c_void] * 6
     lib.vpk_vp_merge_batch.argtypes = [c_void, ctypes.c_int] + [c_void] * 9 + [ctypes.c_double, c_void] + \
                                       [ctypes.c_double] * 3 + [c_void] * 5
+    lib.vpk_estep_batch.argtypes = [c_void, ctypes.c_int] + [c_void] * 7 + [ctypes.c_int] + [c_void] * 5
     _lib = lib
     return lib
 

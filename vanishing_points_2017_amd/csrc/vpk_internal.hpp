@@ -103,6 +103,7 @@ struct vpk_handle {
     void* vpset_ws = nullptr;        // their per-image workspace (grown on demand)
     size_t vpset_ws_bytes = 0;
     bool vpset_ready = false;        // dynamic-LDS attribute set on the kernel
+    vpk_staged estep_hdr;            // vpk_estep_batch (vpk_estep.hip): offsets of lines, VPs, matrices and workgroups
 };
 
 int vpk_fail(vpk_handle* h, int code, const char* what);

@@ -1,11 +1,24 @@
-"""The prior's call surface of the reference's probability_functions.py (same names, same signatures), evaluated on
-the GPU: pdf_params (:62-96) by vpk_prior_params, calc_pdf (:8-40) by vpk_mixture_pdf (include/vpk.h).
+"""The call surface of the reference's probability_functions.py (same names, same signatures), evaluated on the GPU:
+pdf_params (:62-96) by vpk_prior_params, calc_pdf (:8-40) by vpk_mixture_pdf, and the E-step -- calc_probabilities
+(:99-120) with the calc_lvsq_* family (:150-249) -- by vpk_estep_batch (include/vpk.h), for all three distance measures.
 
-The reference's names take and return NumPy arrays.  The ``*_batch`` forms beside them take many response maps at once
-and return device tensors.  There is no host fallback: without the library and a GPU every density call raises.
+The reference's names take and return NumPy arrays.  The ``*_batch`` forms beside them take many images at once and
+return device tensors.  There is no host fallback: without the library and a GPU every density, distance and probability
+call raises.  Three functions are host NumPy by design and need no GPU: calc_angles, calc_plv (:133-147) and calc_pvl
+(:123-130).  The last two take a caller's lvsq / p_lv matrix, which no kernel reads: they are the reference's own few
+NumPy lines (bit-equal to it), for callers that hold such a matrix already.  They are not a fallback for anything:
+inside calc_probabilities both stages run in the kernel, and nothing else in this module computes on the host.
 
-Not here: calc_probabilities, calc_plv, calc_pvl and the calc_lvsq_* family (the E-step lives in the EM workgroup;
-vpk_estep is its fine-grained entry)."""
+Deliberate differences of the E-step from the reference:
+  - the caller's ``s`` is not written (calc_plv floors it in place at :139); calc_probabilities_batch returns the floored
+    values;
+  - an unknown ``distance_measure`` raises ValueError (the reference falls through to a NameError at :114);
+  - p_l is one sum over the VPs in ascending order, not np.dot's BLAS order (:116).
+The "area" measure is kept as the reference has it: np.cross of the 2-vector v_ (:200) measures from the line through the
+segment's midpoint in direction v_.  The EM itself, calc_vp_line_counts, split_best_vp and merge_vps still take "angle"
+only.
+
+Not here: calc_point (:261-266; dead, it overwrites its own first column) and calc_vp_line_triangles (no caller)."""
 from collections import namedtuple
 
 import numpy as np
@@ -155,6 +168,155 @@ def vp_prior_batch(maps, vps, device=0):
     return angles, pdf
 
 
+# ---- the E-step: device tensors -------------------------------------------------------------------------------------------
+DISTANCE_MEASURES = {"angle": 0, "dotprod": 1, "area": 2}     # include/vpk.h: VPK_DIST_*
+
+
+def _measure(distance_measure):
+    if not isinstance(distance_measure, str) or distance_measure not in DISTANCE_MEASURES:
+        raise ValueError("distance_measure %r: one of \"angle\", \"dotprod\", \"area\"" % (distance_measure,))
+    return DISTANCE_MEASURES[distance_measure]
+
+
+def _offsets_of(sizes):
+    return np.concatenate(([0], np.cumsum(sizes, dtype=np.int64))).astype(np.int64)
+
+
+def _cat_rows(rt, xs, width, what):
+    """A list of per-image (rows, width) arrays or tensors ((rows,) for width 0) as one contiguous float64 device tensor,
+    and the host offsets of the images' rows."""
+    t = rt.torch
+    tail = (width,) if width else ()
+    if not any(isinstance(x, t.Tensor) for x in xs):         # host arrays: one concatenation, one upload
+        parts = [np.asarray(x, dtype=np.float64) for x in xs]
+    else:
+        parts = [_to_device(rt, x, t.float64) for x in xs]
+    for d in parts:
+        if tuple(d.shape[1:]) != tail or len(d.shape) != len(tail) + 1:
+            raise ValueError("%s: every image needs shape (rows,%s), got %r" % (what, " %d" % width if width else "", tuple(d.shape)))
+    off = _offsets_of([int(p.shape[0]) for p in parts])
+    if not parts:
+        return t.zeros((0,) + tail, dtype=t.float64, device=rt.tdev), off
+    if isinstance(parts[0], t.Tensor):
+        return t.cat(parts).contiguous(), off
+    return _to_device(rt, np.concatenate(parts), t.float64), off
+
+
+def _off_ptr(a):
+    import ctypes
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _estep(rt, lo, vo, d_lp, d_l, d_v, d_s, d_pv, measure, want):
+    """vpk_estep_batch: the outputs named in ``want`` ('s', 'lvsq', 'p_lv', 'p_l', 'p_vl') as flat device tensors."""
+    t = rt.torch
+    total = int((np.diff(lo) * np.diff(vo)).sum())
+    shapes = {'s': int(vo[-1]), 'lvsq': total, 'p_lv': total, 'p_l': int(lo[-1]), 'p_vl': total}
+    # the matrices are written in full wherever an image has lines and VPs, and have no elements elsewhere; s and p_l of an
+    # image that gets no workgroup stay 0
+    out = {k: ((t.zeros if k in ('s', 'p_l') else t.empty)((shapes[k],), dtype=t.float64, device=rt.tdev) if k in want else None)
+           for k in shapes}
+    rt.check(rt.lib.vpk_estep_batch(rt.h, lo.shape[0] - 1, _off_ptr(lo), _off_ptr(vo), rt.ptr(d_lp), rt.ptr(d_l), rt.ptr(d_v),
+                                    rt.ptr(d_s), rt.ptr(d_pv), measure, rt.ptr(out['s']), rt.ptr(out['lvsq']),
+                                    rt.ptr(out['p_lv']), rt.ptr(out['p_l']), rt.ptr(out['p_vl'])))
+    return out
+
+
+def _estep_inputs(rt, vs, ls, lps, measure):
+    d_lp, lo = _cat_rows(rt, lps, 4, "lps")
+    d_v, vo = _cat_rows(rt, vs, 3, "vs")
+    if lo.shape != vo.shape:
+        raise ValueError("lps and vs describe %d and %d images" % (lo.shape[0] - 1, vo.shape[0] - 1))
+    d_l = None
+    if measure == DISTANCE_MEASURES["dotprod"]:
+        if ls is None or any(x is None for x in ls):
+            raise ValueError("the \"dotprod\" measure reads the homogeneous lines: ls is needed")
+        d_l, llo = _cat_rows(rt, ls, 3, "ls")
+        if not np.array_equal(llo, lo):
+            raise ValueError("ls and lps differ in their images' line counts")
+    return d_lp, d_l, d_v, lo, vo
+
+
+def _split_mats(flat, lo, vo, transposed):
+    """Per image the (M, N) matrix of a flat [m][n] buffer, or its (N, M) transposed view."""
+    out, at = [], 0
+    for b in range(lo.shape[0] - 1):
+        n, m = int(lo[b + 1] - lo[b]), int(vo[b + 1] - vo[b])
+        mat = flat[at:at + m * n].reshape(m, n)
+        out.append(mat.t() if transposed else mat)
+        at += m * n
+    return out
+
+
+def calc_lvsq_batch(vs, ls, lps, distance_measure="angle", device=0):
+    """calc_lvsq_angle / _dotprod / _area for many images in one launch.  ``vs``: per image the VPs (M_b, 3); ``ls``: per
+    image the homogeneous lines (N_b, 3) -- read by "dotprod" only, else it may be None --; ``lps``: per image the end
+    points (N_b, 4); NumPy arrays or tensors.  Returns a list with one (N_b, M_b) float64 device tensor per image: the
+    transposed view of the kernel's [m][n] buffer.  Any M_b; an image without lines or VPs gives an empty matrix.  No
+    chain crosses the VPs here, so the launch also splits the VP range: a few lines against thousands of hypotheses still
+    fill the machine."""
+    measure = _measure(distance_measure)
+    rt = _runtime(device)
+    with rt.on_stream():
+        d_lp, d_l, d_v, lo, vo = _estep_inputs(rt, vs, ls, lps, measure)
+        d_s = rt.torch.ones((int(vo[-1]),), dtype=rt.torch.float64, device=rt.tdev)
+        out = _estep(rt, lo, vo, d_lp, d_l, d_v, d_s, None, measure, ('lvsq',))
+    rt.synchronize()
+    return _split_mats(out['lvsq'], lo, vo, True)
+
+
+def _prior_ragged(rt, pdfpars_or_maps, d_v, vo):
+    """(angles (sum M, 2), p_v (sum M,)) of a ragged batch of VP sets through ONE vpk_mixture_pdf launch: the sets are padded
+    to the largest with the image centre, and the padding is dropped again by an index made from the host offsets."""
+    t = rt.torch
+    B = vo.shape[0] - 1
+    means, weights, sigma = _params_on_device(rt, pdfpars_or_maps)
+    if weights.shape[0] == 1 and B > 1 and means.dim() == 2:
+        weights = weights.expand(B, -1).contiguous()
+    if weights.shape[0] != B:
+        raise ValueError("%d priors for %d images" % (weights.shape[0], B))
+    sizes = np.diff(vo)
+    mmax = int(sizes.max()) if B else 0
+    if B == 0 or mmax == 0:
+        return (t.zeros((0, 2), dtype=t.float64, device=rt.tdev), t.zeros((0,), dtype=t.float64, device=rt.tdev))
+    idx = np.concatenate([b * mmax + np.arange(int(sizes[b]), dtype=np.int64) for b in range(B)])
+    d_idx = t.from_numpy(idx).to(rt.tdev)
+    pad = t.zeros((B * mmax, 3), dtype=t.float64, device=rt.tdev)
+    pad[:, 2] = 1.0
+    pad[d_idx] = d_v
+    angles, pdf = _mixture(rt, means, weights, sigma, pad.reshape(B, mmax, 3), want_angles=True)
+    return angles.reshape(B * mmax, 2)[d_idx].contiguous(), pdf.reshape(B * mmax)[d_idx].contiguous()
+
+
+def calc_probabilities_batch(pdfpars_or_maps, vs, ls, lps, ss, distance_measure="angle", device=0):
+    """calc_probabilities for many images: the prior of every VP (one vpk_mixture_pdf launch) and the E-step (one
+    vpk_estep_batch launch).  ``pdfpars_or_maps``: B x 20 x 20 response maps (pdf_params' defaults apply) or a PDFParams
+    (pdf_params_batch's, or any means / weights (B, ncomp) / sigma; one weight row serves every image); ``vs``, ``ls``,
+    ``lps`` as in calc_lvsq_batch; ``ss``: per image the variances (M_b,).  Nothing is copied to the host.  Returns a dict:
+    'pdf' a list with one PDF tuple per image -- v (M,), lv (N, M), vl (M, N), l (N,), lvsq (N, M), angles (M, 2), float64
+    device tensors, lv and lvsq transposed views of [m][n] buffers --, 's' a list of the variances floored at 1e-200 (the
+    caller's are not written), and the host offsets 'line_offsets' and 'vp_offsets'."""
+    measure = _measure(distance_measure)
+    if not _is_params(pdfpars_or_maps):
+        _check_maps(pdfpars_or_maps)
+    rt = _runtime(device)
+    with rt.on_stream():
+        d_lp, d_l, d_v, lo, vo = _estep_inputs(rt, vs, ls, lps, measure)
+        d_s, so = _cat_rows(rt, ss, 0, "ss")
+        if not np.array_equal(so, vo):
+            raise ValueError("ss and vs differ in their images' VP counts")
+        angles, p_v = _prior_ragged(rt, pdfpars_or_maps, d_v, vo)
+        out = _estep(rt, lo, vo, d_lp, d_l, d_v, d_s, p_v, measure, ('s', 'lvsq', 'p_lv', 'p_l', 'p_vl'))
+    rt.synchronize()
+    lvsq, p_lv, p_vl = (_split_mats(out[k], lo, vo, k != 'p_vl') for k in ('lvsq', 'p_lv', 'p_vl'))
+    pdfs, s_out = [], []
+    for b in range(lo.shape[0] - 1):
+        n0, n1, m0, m1 = int(lo[b]), int(lo[b + 1]), int(vo[b]), int(vo[b + 1])
+        pdfs.append(PDF(v=p_v[m0:m1], lv=p_lv[b], vl=p_vl[b], l=out['p_l'][n0:n1], lvsq=lvsq[b], angles=angles[m0:m1]))
+        s_out.append(out['s'][m0:m1])
+    return {'pdf': pdfs, 's': s_out, 'line_offsets': lo, 'vp_offsets': vo}
+
+
 def _grid_xy(N):
     X = np.arange(-np.pi / 2, np.pi / 2, np.pi * 1.0 / N)       # :277-279
     Y = np.arange(-np.pi / 2, np.pi / 2, np.pi * 1.0 / N)
@@ -215,6 +377,70 @@ def pdf_grid(cnn_response, N=50, device=0):
     pdfpar = pdf_params(cnn_response, device=device)
     X, Y = _grid_xy(N)
     return {'X': X, 'Y': Y, 'p': calc_pdf_grid(pdfpar, X, Y, device=device)}
+
+
+# ---- the E-step: the reference's names --------------------------------------------------------------------------------
+def calc_probabilities(i, pdfpar, v, l, lp, s, llen, distance_measure="angle", device=0):
+    """calc_probabilities (:99-120) on slice i of the history array ``v`` (iterations, M, 3): the PDF tuple v (M,), lv (N, M),
+    vl (M, N), l (N,), lvsq (N, M), angles (M, 2) that EM_result['distribution'] uses.  ``llen`` is read by no measure.
+    ``s`` is not written (see the module's list of differences)."""
+    _measure(distance_measure)
+    vi = np.asarray(v, dtype=np.float64)[i].reshape(-1, 3)
+    par = PDFParams(means=np.asarray(pdfpar.means), weights=np.asarray(pdfpar.weights).reshape(1, -1), sigma=pdfpar.sigma)
+    r = calc_probabilities_batch(par, [vi], [None if l is None else np.asarray(l, dtype=np.float64).reshape(-1, 3)],
+                                 [np.asarray(lp, dtype=np.float64).reshape(-1, 4)],
+                                 [np.asarray(s, dtype=np.float64).reshape(-1)], distance_measure=distance_measure,
+                                 device=device)['pdf'][0]
+    return PDF(*(np.ascontiguousarray(x.cpu().numpy()) for x in r))
+
+
+def calc_pvl(M, N, p_lv, p_v, p_l):
+    """calc_pvl (:123-130) on a caller's matrices, in NumPy (see the module docstring): p_vl[m, n] = p_lv[n, m] p_v[m] / p_l[n]."""
+    p_lv, p_v, p_l = np.asarray(p_lv), np.asarray(p_v), np.asarray(p_l)
+    return (p_lv[:N, :M] * p_v[None, :M]).T / p_l[None, :N]
+
+
+def calc_plv(M, v, s, lvsq, lp):
+    """calc_plv (:133-147) on a caller's lvsq (N, M), in NumPy (see the module docstring).  The caller's s is not written."""
+    s = np.asarray(s, dtype=np.float64)[:M]
+    sf = np.where(s > 1e-200, s, 1e-200)                        # :139
+    p_lv = np.exp(-(np.asarray(lvsq, dtype=np.float64) / (2 * sf)[None, :]))
+    return p_lv * (1.0 / np.sqrt(2 * np.pi * sf))[None, :]
+
+
+def _calc_lvsq(v, l, lp, distance_measure, device):
+    v = np.asarray(v, dtype=np.float64).reshape(3, -1)
+    ls = None if l is None else [np.asarray(l, dtype=np.float64).reshape(-1, 3)]
+    out = calc_lvsq_batch([np.ascontiguousarray(v.T)], ls, [np.asarray(lp, dtype=np.float64).reshape(-1, 4)],
+                          distance_measure=distance_measure, device=device)[0]
+    return np.ascontiguousarray(out.cpu().numpy())
+
+
+def calc_lvsq_dotprod(v, l, lp, llen, device=0):
+    """calc_lvsq_dotprod (:150-154): ``v`` 3 x M as in the reference, ``l`` (N, 3); returns (N, M)."""
+    return _calc_lvsq(v, l, lp, "dotprod", device)
+
+
+def calc_lvsq_angle(v, l, lp, llen, device=0):
+    """calc_lvsq_angle (:157-176): ``v`` 3 x M, ``lp`` (N, 4); returns (N, M).  ``l`` and ``llen`` are not read."""
+    return _calc_lvsq(v, None, lp, "angle", device)
+
+
+def calc_lvsq_area(v, l, lp, llen, device=0):
+    """calc_lvsq_area (:179-209): ``v`` 3 x M, ``lp`` (N, 4); returns (N, M).  ``l`` and ``llen`` are not read."""
+    return _calc_lvsq(v, None, lp, "area", device)
+
+
+def calc_lvsq_single(v, l, lp, device=0):
+    """calc_lvsq_single (:212-224): one VP (3,) against one segment (4,)."""
+    return _calc_lvsq(np.asarray(v, dtype=np.float64).reshape(3, 1), None, np.asarray(lp, dtype=np.float64).reshape(1, 4),
+                      "angle", device)[0, 0]
+
+
+def calc_lvsq_area_single(v, l, lp, device=0):
+    """calc_lvsq_area_single (:227-249): one VP (3,) against one segment (4,)."""
+    return _calc_lvsq(np.asarray(v, dtype=np.float64).reshape(3, 1), None, np.asarray(lp, dtype=np.float64).reshape(1, 4),
+                      "area", device)[0, 0]
 
 
 def vp_is_within_image(vp):
