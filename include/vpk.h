@@ -475,6 +475,22 @@ int vpk_estep(vpk_handle* h, int n, int m, const double* lp, const float* cnn, c
 /* weight_matrix (vp_localisation.py:515-524): p_vl [m][n], lsim n x n -> w_out [m][n]. */
 int vpk_weight_matrix(vpk_handle* h, int n, int m, const double* p_vl, const double* lweight,
                       const double* lsim, double bias, double* w_out);
+/* TEST HOOK: calc_probabilities followed by weight_matrix in ONE workgroup, as an iteration of vpk_em_batch runs them: the
+ * E-step leaves the smoother's operand panel p_vl * lweight in LDS where its plan allows (M <= 32 and the panel fits the
+ * budget) and the smoother consumes it instead of staging one -- the path neither vpk_estep (lweight = 1, panel unread)
+ * nor vpk_weight_matrix (no E-step: always staged) reaches.  Inputs as vpk_estep's (lp n x 4, cnn 400, v m x 3, s m floored
+ * in place) and vpk_weight_matrix's (lweight n, lsim n x n, bias).  Launched with the LDS budget of vpk_em_batch, so
+ * vpk_em_set_lds_panel and vpk_em_set_smoother steer it as they steer the batch.  Outputs: p_vl_out [m][n], w_out [m][n]
+ * and info_out, four int32 read from the device functions that decide, after the E-step and before the smoother:
+ *   [0] the smoother's plan for m hypotheses (0: no panel, smooth_full in passes or smooth_blocks; 1: smooth_full's panel;
+ *       2: the row-sliced panel; 3: the row-sliced kernel in passes),
+ *   [1] the panel flag as the E-step left it (0: none; W: smooth_full's [line][W]; 0x100 + W: the row-sliced layout),
+ *   [2] 1 when the sparse smoother applies (setting 2, n <= 448, a finite lsim), which then ignores the panel,
+ *   [3] VPs per pass: of the row-sliced kernel under plan 3, otherwise of smooth_full (min(32, 8 floor(budget / n / 8))).
+ * Not used by any product path. */
+int vpk_estep_smooth(vpk_handle* h, int n, int m, const double* lp, const float* cnn, const double* v, double* s,
+                     const double* lweight, const double* lsim, double bias, double* p_vl_out, double* w_out,
+                     int32_t* info_out);
 /* calc_new_vanishing_point (:453-479) for every row of w [m][n]: vp_out m x 3, valid_out m. */
 int vpk_mstep(vpk_handle* h, int n, int m, const double* l, const double* w, double* vp_out,
               int32_t* valid_out);

@@ -159,6 +159,52 @@ int sim_weight_matrix(int n, int m, const double* p_vl, const double* lweight, c
     return 0;
 }
 
+// the matching wrapper of vpk_estep_smooth (csrc/vpk_em.hip: estep_smooth_kernel): estep() then smooth(), the panel handed over
+// in LDS where the E-step planned one
+int sim_estep_smooth(int n, int m, const double* lp, const float* cnn, const double* v, double* s, const double* lweight,
+                     const double* lsim, double bias, double* p_vl_out, double* w_out, int* info_out) {
+    vpk_em_params p;
+    memset(&p, 0, sizeof(p));
+    p.use_weights = 1; p.num_init_vp = m; p.num_iter = 1; p.split_merge_freq = 10; p.wbias = bias;
+    EmCtx c;
+    std::vector<double> buf;
+    make_ctx(c, buf, n, p, false, 0);
+    c.lp = lp; c.cnn = cnn;
+    prior_setup(c);
+    g_sh.M = m; g_sh.ibuf[5] = 0; g_sh.ibuf[2] = 0;
+    for (int k = 0; k < 3 * m; ++k) g_sh.cur[k] = v[k];
+    for (int k = 0; k < m; ++k) g_sh.s[k] = s[k];
+    for (int i = 0; i < n; ++i) {
+        c.lweight[i] = lweight[i];
+        for (int j = 0; j < n; ++j) c.lsim[(size_t)i * c.ld + j] = lsim[(size_t)i * n + j];
+    }
+    for (int k = 0; k < n; ++k) {
+        double sum = 0;
+        for (int j = 0; j < n; ++j) sum += lsim[(size_t)j * n + k];
+        c.den[k] = 1 + bias * c.lweight[k] * sum;
+        if (!(fabs(sum) <= 1.7976931348623157e308)) g_sh.ibuf[2] = 1;
+    }
+    zero_tail_rows(c);
+    line_geometry_setup(c);
+    estep(c, g_sh.cur);
+    const int plan = smooth_plan(c, m);
+    int wfit = ((c.wt_doubles / n) / MT) * MT;
+    if (wfit > 32) wfit = 32;
+    info_out[0] = plan;
+    info_out[1] = g_sh.ibuf[5];
+    info_out[2] = (sparse_smoother_fits(c) && g_sh.ibuf[2] == 0) ? 1 : 0;
+    info_out[3] = plan == 3 ? rs_wfit(c) : wfit;
+    smooth(c);
+    for (int k = 0; k < m; ++k) {
+        s[k] = g_sh.s[k];
+        for (int q = 0; q < n; ++q) {
+            p_vl_out[(size_t)k * n + q] = c.pvl[(size_t)k * c.ldn + q];
+            w_out[(size_t)k * n + q] = c.w[(size_t)k * c.ldn + q];
+        }
+    }
+    return 0;
+}
+
 int sim_mstep(int n, int m, const double* l, const double* w, double* vp_out) {
     vpk_em_params p;
     memset(&p, 0, sizeof(p));

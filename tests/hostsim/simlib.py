@@ -121,13 +121,42 @@ def estep(lp, cnn, v, s):
     return pv, lvsq, pvl, s
 
 
-def weight_matrix(p_vl, lweight, lsim, bias=1.0):
+def _budget(lds_doubles):
+    """The LDS budget the phases plan with (the library's vpk_em_set_lds_panel); None = the host build's default."""
+    if lds_doubles is None:
+        os.environ.pop("VPK_SIM_WT_DOUBLES", None)
+    else:
+        os.environ["VPK_SIM_WT_DOUBLES"] = str(int(lds_doubles))
+
+
+def weight_matrix(p_vl, lweight, lsim, bias=1.0, lds_doubles=None):
     m, n = p_vl.shape
     p_vl = np.ascontiguousarray(p_vl); lweight = np.ascontiguousarray(lweight); lsim = np.ascontiguousarray(lsim)
     w = np.zeros((m, n))
     D = ctypes.c_double
-    lib().sim_weight_matrix(n, m, _p(p_vl, D), _p(lweight, D), _p(lsim, D), ctypes.c_double(bias), _p(w, D))
+    _budget(lds_doubles)
+    try:
+        lib().sim_weight_matrix(n, m, _p(p_vl, D), _p(lweight, D), _p(lsim, D), ctypes.c_double(bias), _p(w, D))
+    finally:
+        _budget(None)
     return w
+
+
+def estep_smooth(lp, cnn, v, s, lweight, lsim, bias=1.0, lds_doubles=None):
+    """The wrapper that matches the library's vpk_estep_smooth: p_vl (M,N), w (M,N), s (floored), info (4 int32)."""
+    n, m = lp.shape[0], v.shape[0]
+    D = ctypes.c_double
+    lp, v, lweight, lsim = (np.ascontiguousarray(a, dtype=np.float64) for a in (lp, v, lweight, lsim))
+    cnn = np.ascontiguousarray(cnn, dtype=np.float32)
+    s = np.ascontiguousarray(s, dtype=np.float64).copy()
+    pvl = np.zeros((m, n)); w = np.zeros((m, n)); info = np.zeros(4, np.int32)
+    _budget(lds_doubles)
+    try:
+        lib().sim_estep_smooth(n, m, _p(lp, D), _p(cnn, ctypes.c_float), _p(v, D), _p(s, D), _p(lweight, D), _p(lsim, D),
+                               D(bias), _p(pvl, D), _p(w, D), _p(info, ctypes.c_int32))
+    finally:
+        _budget(None)
+    return pvl, w, s, info
 
 
 def cluster2(ldist):

@@ -26,6 +26,7 @@ other summation order.  Neither number was fitted to device output.
 import numpy as np
 
 from em_phase_reference import LD, U, PI, ld, null_vector_reference, residual, estep_reference, _ratio  # noqa: F401
+from em_smoother_reference import smooth_reference
 
 MARGIN_MIN = LD(1e-9)
 GOLDEN_S_REL = 8.2e-14
@@ -253,14 +254,10 @@ def split_reference(vi, s, lp, l, w, lw, langle, min_diff=1e-4):
 # =============================================================================================================
 def weight_matrix_reference(p_vl, b_pvl, lw, lsim, bias):
     """weight_matrix (:515-524) in extended precision and the first-order bound of its fp64 evaluation from the bound of
-    p_vl: every term is non-negative, so the bound passes through the same operator, plus (N + 8) u of the result."""
-    lw_, ls = ld(lw), ld(lsim)
-    w_ = p_vl * lw_[None, :]
-    bw = b_pvl * lw_[None, :]
-    den = 1 + LD(bias) * lw_ * ls.sum(axis=0)
-    w = (w_ + LD(bias) * lw_[None, :] * (w_ @ ls)) / den[None, :]
-    b = (bw + LD(bias) * lw_[None, :] * (bw @ np.abs(ls))) / den[None, :] + (lw_.shape[0] + 8) * U * np.abs(w)
-    return w, b
+    p_vl: every term is non-negative, so the bound passes through the same operator, plus (N + 8) u of the result and the
+    resolution of underflowing products (em_smoother_reference.smooth_reference: the one statement of the formula)."""
+    lw_ = ld(lw)
+    return smooth_reference(p_vl * lw_[None, :], b_pvl * lw_[None, :], lw, lsim, bias)
 
 
 def angle_matrix(v):

@@ -65,7 +65,7 @@ EXPORTS = [
     "vpk_cnn_calibrate", "vpk_cnn_get_activation_scales", "vpk_cnn_set_activation_scales", "vpk_cnn_range_flags",
     "vpk_cnn_set_range_policy", "vpk_cnn_image_range_flags", "vpk_cnn_recomputed",
     "vpk_sphere_raster", "vpk_sphere_raster_flags", "vpk_sphere_raster_set_alternative", "vpk_em_batch", "vpk_em_workspace_bytes", "vpk_pairwise", "vpk_init_vps",
-    "vpk_estep", "vpk_weight_matrix", "vpk_mstep", "vpk_mstep_full", "vpk_line_counts", "vpk_cluster2", "vpk_horizon_batch", "vpk_lsd_detect",
+    "vpk_estep", "vpk_weight_matrix", "vpk_estep_smooth", "vpk_mstep", "vpk_mstep_full", "vpk_line_counts", "vpk_cluster2", "vpk_horizon_batch", "vpk_lsd_detect",
     "vpk_lsd_detect_batch", "vpk_lsd_set_workspace_limit", "vpk_lsd_set_math",
     "vpk_image_prepare_batch", "vpk_lsd_rows_to_lines",
     "vpk_pipeline_step", "vpk_build_records", "vpk_record_width", "vpk_math_probe",
@@ -121,6 +121,7 @@ def load():
     lib.vpk_estep.argtypes = [c_void, ctypes.c_int, ctypes.c_int] + [c_void] * 8
     lib.vpk_weight_matrix.argtypes = [c_void, ctypes.c_int, ctypes.c_int, c_void, c_void, c_void,
                                       ctypes.c_double, c_void]
+    lib.vpk_estep_smooth.argtypes = [c_void, ctypes.c_int, ctypes.c_int] + [c_void] * 6 + [ctypes.c_double] + [c_void] * 3
     lib.vpk_mstep.argtypes = [c_void, ctypes.c_int, ctypes.c_int, c_void, c_void, c_void, c_void]
     lib.vpk_mstep_full.argtypes = [c_void, ctypes.c_int, ctypes.c_int] + [c_void] * 6 + [ctypes.c_double, ctypes.c_double] + \
                                   [c_void] * 4

@@ -377,6 +377,57 @@ __global__ __launch_bounds__(EM_BOUND) void weight_matrix_kernel(int n, int m, c
     for (int p = tid(); p < m * n; p += nthreads()) w_out[p] = c.w[(size_t)(p / n) * c.ldn + p % n];
 }
 
+// TEST HOOK (vpk_estep_smooth): estep() followed by smooth() in ONE workgroup, so that the smoother consumes the operand panel
+// the E-step left in LDS (sh.ibuf[5]) -- the batch kernel's path, which vpk_weight_matrix (panel staged by the smoother) and
+// vpk_estep (lweight = 1, panel never read) do not reach.  The context is filled like estep_kernel's, with the caller's
+// lweight; lsim, den and the sh.ibuf[2] flag like weight_matrix_kernel's.  info_out: see include/vpk.h.
+__global__ __launch_bounds__(EM_BOUND) void estep_smooth_kernel(int n, int m, const double* lp, const float* cnn,
+                                                                  const double* v, double* s, const double* lweight,
+                                                                  const double* lsim, double bias, EmLayout L, double* ws,
+                                                                  double* p_vl_out, double* w_out, int* info_out,
+                                                                  int smoother, int wt_doubles) {
+    VPK_SHARED_DECL;
+    EmCtx c;
+    c.N = n; c.lp = (cgdp)lp; c.cnn = (cgfp)cnn; c.wt_doubles = wt_doubles; c.smoother = smoother;
+    c.prm.use_weights = 1;
+    c.prm.wbias = bias;
+    bind_scratch(c, ws, L, false);
+    prior_setup(c);
+    for (int p = tid(); p < n * n; p += nthreads())      // caller's matrix (row stride n) -> padded rows
+        c.lsim[(size_t)(p / n) * c.ld + p % n] = lsim[p];
+    for (int k = tid(); k < n; k += nthreads()) c.lweight[k] = lweight[k];
+    for (int k = tid(); k < 3 * m; k += nthreads()) sh.cur[k] = v[k];
+    for (int k = tid(); k < m; k += nthreads()) sh.s[k] = s[k];
+    if (tid() == 0) { sh.M = m; sh.ibuf[5] = 0; sh.ibuf[2] = 0; }
+    block_sync();
+    for (int k = tid(); k < n; k += nthreads()) {
+        double sum = 0.0;
+        for (int j = 0; j < n; ++j) sum += lsim[(size_t)j * n + k];
+        c.den[k] = 1 + bias * c.lweight[k] * sum;
+        if (!(fabs(sum) <= 1.7976931348623157e308)) sh.ibuf[2] = 1;       // (see weights_setup)
+    }
+    block_sync();
+    zero_tail_rows(c);
+    line_geometry_setup(c);
+    estep(c, sh.cur);
+    if (tid() == 0) {                                    // what smooth() is about to do, from its own deciding functions
+        const int plan = smooth_plan(c, m);
+        int wfit = ((c.wt_doubles / n) / MT) * MT;       // smooth_dispatch's pass width of smooth_full
+        if (wfit > 32) wfit = 32;
+        info_out[0] = plan;
+        info_out[1] = sh.ibuf[5];
+        info_out[2] = (sparse_smoother_fits(c) && sh.ibuf[2] == 0) ? 1 : 0;
+        info_out[3] = plan == 3 ? rs_wfit(c) : wfit;
+    }
+    smooth(c);                                           // (nothing between the two touches the panel region)
+    for (int k = tid(); k < m; k += nthreads()) s[k] = sh.s[k];
+    for (int p = tid(); p < m * n; p += nthreads()) {
+        const int k = p / n, q = p % n;
+        p_vl_out[p] = c.pvl[(size_t)k * c.ldn + q];
+        w_out[p] = c.w[(size_t)k * c.ldn + q];
+    }
+}
+
 __global__ __launch_bounds__(EM_BOUND) void mstep_kernel(int n, int m, const double* l, const double* w,
                                                            EmLayout L, double* ws, double* vp_out,
                                                            int* valid_out) {
@@ -498,6 +549,7 @@ int em_prepare(vpk_handle* h) {
     if ((rc = allow_lds(h, init_vps_kernel))) return rc;
     if ((rc = allow_lds(h, estep_kernel))) return rc;
     if ((rc = allow_lds(h, weight_matrix_kernel))) return rc;
+    if ((rc = allow_lds(h, estep_smooth_kernel))) return rc;
     if ((rc = allow_lds(h, mstep_kernel))) return rc;
     if ((rc = allow_lds(h, mstep_full_kernel))) return rc;
     if ((rc = allow_lds(h, cluster2_kernel))) return rc;
@@ -857,6 +909,24 @@ int vpk_weight_matrix(vpk_handle* h, int n, int m, const double* p_vl, const dou
     const EmMode mode = em_mode(h);
     hipLaunchKernelGGL(weight_matrix_kernel, dim3(1), dim3(EM_THREADS), mode.lds_bytes, h->stream, n, m, p_vl, lweight, lsim,
                        bias, L, (double*)h->small_ws, w_out, h->em_smoother, mode.wt_doubles);
+    VPK_HIP(h, hipGetLastError());
+    return VPK_OK;
+}
+
+int vpk_estep_smooth(vpk_handle* h, int n, int m, const double* lp, const float* cnn, const double* v, double* s,
+                     const double* lweight, const double* lsim, double bias, double* p_vl_out, double* w_out,
+                     int32_t* info_out) {
+    if (!h || n < 1 || m < 1 || m > MAXM || !lp || !cnn || !v || !s || !lweight || !lsim || !p_vl_out || !w_out || !info_out)
+        return vpk_fail(h, VPK_ERR_ARG, "vpk_estep_smooth: bad argument");
+    VPK_HIP(h, hipSetDevice(h->device));
+    { int rc0 = em_prepare(h); if (rc0) return rc0; }
+    EmLayout L = small_layout(n, m);
+    int rc = vpk_reserve(h, &h->small_ws, &h->small_ws_bytes, L.total_doubles * 8, "hipMalloc(workspace)");
+    if (rc) return rc;
+    // the batch kernel's LDS budget (as vpk_weight_matrix): the E-step plans the panel and the smoother takes it as they do there
+    const EmMode mode = em_mode(h);
+    hipLaunchKernelGGL(estep_smooth_kernel, dim3(1), dim3(EM_THREADS), mode.lds_bytes, h->stream, n, m, lp, cnn, v, s, lweight,
+                       lsim, bias, L, (double*)h->small_ws, p_vl_out, w_out, (int*)info_out, h->em_smoother, mode.wt_doubles);
     VPK_HIP(h, hipGetLastError());
     return VPK_OK;
 }

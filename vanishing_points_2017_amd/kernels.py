@@ -77,6 +77,25 @@ def weight_matrix(p_vl, lweight, lsim, bias=1.0, device=0):
     return w.cpu().numpy()
 
 
+def estep_smooth(lp, cnn, v, s, lweight, lsim, bias=1.0, device=0):
+    """calc_probabilities followed by weight_matrix in one workgroup, the smoother taking the operand panel the E-step left
+    in LDS where it planned one (vpk_estep_smooth, a test hook).  Returns p_vl (M,N), w (M,N), s (floored), info (4 int32)."""
+    rt = get_runtime(device)
+    t = rt.torch
+    n, m = lp.shape[0], v.shape[0]
+    with rt.on_stream():
+        d_lp, d_v, d_s = _up(rt, lp, np.float64), _up(rt, v, np.float64), _up(rt, s, np.float64)
+        d_cnn = _up(rt, np.asarray(cnn).reshape(400), np.float32)
+        d_lw, d_ls = _up(rt, lweight, np.float64), _up(rt, lsim, np.float64)
+        pvl = t.empty((m, n), dtype=t.float64, device=rt.tdev)
+        w = t.empty((m, n), dtype=t.float64, device=rt.tdev)
+        info = t.zeros((4,), dtype=t.int32, device=rt.tdev)
+        rt.check(rt.lib.vpk_estep_smooth(rt.h, n, m, rt.ptr(d_lp), rt.ptr(d_cnn), rt.ptr(d_v), rt.ptr(d_s), rt.ptr(d_lw),
+                                         rt.ptr(d_ls), float(bias), rt.ptr(pvl), rt.ptr(w), rt.ptr(info)))
+    rt.synchronize()
+    return pvl.cpu().numpy(), w.cpu().numpy(), d_s.cpu().numpy(), info.cpu().numpy()
+
+
 def mstep(l, w, device=0):
     """calc_new_vanishing_point (vp_localisation.py:453-479) for every row of w (M,N)."""
     rt = get_runtime(device)
