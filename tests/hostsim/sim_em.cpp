@@ -1,13 +1,13 @@
-// sim_em.cpp -- TEST-ONLY host build of the EM device source (see hip_sim.hpp).
+// sim_em.cpp -- TEST-ONLY host build of the EM device source (see hip_sim.hpp): the driver em_run on one image, and the
+// bodies of the library's fine-grained entry points (csrc/em_hooks.hpp, the file csrc/vpk_em.hip's fine-grained kernels call).
 #include "hip_sim.hpp"
-#include "../../vanishing_points_2017_amd/csrc/em_device.hpp"
+#include "../../vanishing_points_2017_amd/csrc/em_hooks.hpp"
 
 #include <stdlib.h>
 #include <vector>
 
 using namespace vpk;
 
-#define g_sh (SH())
 static std::vector<double> g_dbg;
 
 static void make_ctx(EmCtx& c, std::vector<double>& buf, int n, const vpk_em_params& p, bool has_init,
@@ -15,12 +15,20 @@ static void make_ctx(EmCtx& c, std::vector<double>& buf, int n, const vpk_em_par
     int mcap = em_mcap(p.num_init_vp, n_init, has_init, p.do_split != 0, p.num_iter, p.split_merge_freq, MAXM);
     EmLayout L = em_layout(n, mcap, 1, p.use_weights != 0, p.do_split != 0);
     buf.assign(L.total_doubles, 0.0);
-    memset(&c, 0, sizeof(c));
+    c = EmCtx{};
     c.N = n;
     c.prm = p;
     c.wt_doubles = WT_DOUBLES;
     if (const char* e = getenv("VPK_SIM_WT_DOUBLES")) c.wt_doubles = atoi(e);   // the LDS budget the phases plan with (vpk_em_set_lds_panel)
     bind_scratch(c, buf.data(), L, p.do_split != 0);
+}
+
+// the context of a fine-grained entry point: a slot for n lines and m VPs (what the hook bodies fill: em_hooks.hpp)
+static void sim_hook_ctx(EmCtx& c, std::vector<double>& buf, int n, int m) {
+    vpk_em_params p;
+    memset(&p, 0, sizeof(p));
+    p.use_weights = 1; p.num_init_vp = m; p.num_iter = 1; p.split_merge_freq = 10;
+    make_ctx(c, buf, n, p, false, 0);
 }
 
 extern "C" {
@@ -72,233 +80,80 @@ int sim_em_single(int n, double* l, const double* lp, const float* cnn, const un
 const double* sim_last_states() { return g_dbg.data(); }
 
 int sim_pairwise(int n, const double* lp, double* lsim_out, double* lscore_out, double* langle_out) {
-    vpk_em_params p;
-    memset(&p, 0, sizeof(p));
-    p.use_weights = 1; p.num_init_vp = 25; p.num_iter = 1; p.split_merge_freq = 10;
     EmCtx c;
     std::vector<double> buf;
-    make_ctx(c, buf, n, p, false, 0);
-    c.lp = lp;
-    pairwise_setup(c, true);
-    for (int i = 0; i < n; ++i) {
-        for (int j = 0; j < n; ++j) lsim_out[(size_t)i * n + j] = c.lsim[(size_t)i * c.ld + j];
-        lscore_out[i] = c.lscore[i];
-        langle_out[i] = c.langle[i];
-    }
+    sim_hook_ctx(c, buf, n, 25);
+    hook_pairwise(c, n, lp, lsim_out, lscore_out, langle_out);
     return 0;
 }
 
 int sim_init_vps(const float* cnn, const unsigned char* sphere, int ssize, int num_max, double* v0_out,
                  int* m0_out, float* weights_out) {
-    vpk_em_params p;
-    memset(&p, 0, sizeof(p));
-    p.use_weights = 1; p.num_init_vp = num_max; p.num_iter = 1; p.split_merge_freq = 10;
     EmCtx c;
     std::vector<double> buf;
-    make_ctx(c, buf, 8, p, false, 0);
-    c.cnn = cnn; c.sphere = sphere; c.ssize = ssize;
-    initial_vps(c);
-    *m0_out = g_sh.M;
-    for (int k = 0; k < 3 * g_sh.M; ++k) v0_out[k] = g_sh.cur[k];
-    prior_setup(c);
-    for (int k = 0; k < NCELL; ++k) weights_out[k] = g_sh.wts[k];
+    sim_hook_ctx(c, buf, 8, num_max);
+    hook_init_vps(c, cnn, sphere, ssize, num_max, v0_out, m0_out, weights_out);
     return 0;
 }
 
 int sim_estep(int n, int m, const double* lp, const float* cnn, const double* v, double* s,
               double* p_v_out, double* lvsq_out, double* p_vl_out) {
-    vpk_em_params p;
-    memset(&p, 0, sizeof(p));
-    p.use_weights = 1; p.num_init_vp = m; p.num_iter = 1; p.split_merge_freq = 10;
     EmCtx c;
     std::vector<double> buf;
-    make_ctx(c, buf, n, p, false, 0);
-    c.lp = lp; c.cnn = cnn;
-    prior_setup(c);
-    for (int k = 0; k < n; ++k) c.lweight[k] = 1.0;
-    g_sh.M = m;
-    for (int k = 0; k < 3 * m; ++k) g_sh.cur[k] = v[k];
-    for (int k = 0; k < m; ++k) g_sh.s[k] = s[k];
-    line_geometry_setup(c);
-    estep(c, g_sh.cur);
-    for (int k = 0; k < m; ++k) {
-        s[k] = g_sh.s[k];
-        p_v_out[k] = g_sh.pv[k];
-        for (int q = 0; q < n; ++q) {
-            lvsq_out[(size_t)k * n + q] = c.lvsq[(size_t)k * c.ldn + q];
-            p_vl_out[(size_t)k * n + q] = c.pvl[(size_t)k * c.ldn + q];
-        }
-    }
+    sim_hook_ctx(c, buf, n, m);
+    hook_estep(c, n, m, lp, cnn, v, s, p_v_out, lvsq_out, p_vl_out, nullptr);
     return 0;
 }
 
 int sim_weight_matrix(int n, int m, const double* p_vl, const double* lweight, const double* lsim,
                       double bias, double* w_out) {
-    vpk_em_params p;
-    memset(&p, 0, sizeof(p));
-    p.use_weights = 1; p.num_init_vp = m; p.num_iter = 1; p.split_merge_freq = 10; p.wbias = bias;
     EmCtx c;
     std::vector<double> buf;
-    make_ctx(c, buf, n, p, false, 0);
-    g_sh.M = m;
-    for (int i = 0; i < n; ++i) {
-        c.lweight[i] = lweight[i];
-        for (int j = 0; j < n; ++j) c.lsim[(size_t)i * c.ld + j] = lsim[(size_t)i * n + j];
-        for (int k = 0; k < m; ++k) c.wsrc[(size_t)i * c.mcap + k] = p_vl[(size_t)k * n + i] * lweight[i];
-    }
-    for (int k = 0; k < n; ++k) {
-        double sum = 0;
-        for (int j = 0; j < n; ++j) sum += c.lsim[(size_t)j * c.ld + k];
-        c.den[k] = 1 + bias * c.lweight[k] * sum;
-        for (int q = m; q < c.mcap; ++q) c.wsrc[(size_t)k * c.mcap + q] = 0.0;
-    }
-    g_sh.ibuf[5] = 0;
-    smooth(c);
-    for (int k = 0; k < m; ++k)
-        for (int q = 0; q < n; ++q) w_out[(size_t)k * n + q] = c.w[(size_t)k * c.ldn + q];
+    sim_hook_ctx(c, buf, n, m);
+    hook_weight_matrix(c, n, m, p_vl, lweight, lsim, bias, w_out);
     return 0;
 }
 
-// the matching wrapper of vpk_estep_smooth (csrc/vpk_em.hip: estep_smooth_kernel): estep() then smooth(), the panel handed over
-// in LDS where the E-step planned one
 int sim_estep_smooth(int n, int m, const double* lp, const float* cnn, const double* v, double* s, const double* lweight,
                      const double* lsim, double bias, double* p_vl_out, double* w_out, int* info_out) {
-    vpk_em_params p;
-    memset(&p, 0, sizeof(p));
-    p.use_weights = 1; p.num_init_vp = m; p.num_iter = 1; p.split_merge_freq = 10; p.wbias = bias;
     EmCtx c;
     std::vector<double> buf;
-    make_ctx(c, buf, n, p, false, 0);
-    c.lp = lp; c.cnn = cnn;
-    prior_setup(c);
-    g_sh.M = m; g_sh.ibuf[5] = 0; g_sh.ibuf[2] = 0;
-    for (int k = 0; k < 3 * m; ++k) g_sh.cur[k] = v[k];
-    for (int k = 0; k < m; ++k) g_sh.s[k] = s[k];
-    for (int i = 0; i < n; ++i) {
-        c.lweight[i] = lweight[i];
-        for (int j = 0; j < n; ++j) c.lsim[(size_t)i * c.ld + j] = lsim[(size_t)i * n + j];
-    }
-    for (int k = 0; k < n; ++k) {
-        double sum = 0;
-        for (int j = 0; j < n; ++j) sum += lsim[(size_t)j * n + k];
-        c.den[k] = 1 + bias * c.lweight[k] * sum;
-        if (!(fabs(sum) <= 1.7976931348623157e308)) g_sh.ibuf[2] = 1;
-    }
-    zero_tail_rows(c);
-    line_geometry_setup(c);
-    estep(c, g_sh.cur);
-    const int plan = smooth_plan(c, m);
-    int wfit = ((c.wt_doubles / n) / MT) * MT;
-    if (wfit > 32) wfit = 32;
-    info_out[0] = plan;
-    info_out[1] = g_sh.ibuf[5];
-    info_out[2] = (sparse_smoother_fits(c) && g_sh.ibuf[2] == 0) ? 1 : 0;
-    info_out[3] = plan == 3 ? rs_wfit(c) : wfit;
-    smooth(c);
-    for (int k = 0; k < m; ++k) {
-        s[k] = g_sh.s[k];
-        for (int q = 0; q < n; ++q) {
-            p_vl_out[(size_t)k * n + q] = c.pvl[(size_t)k * c.ldn + q];
-            w_out[(size_t)k * n + q] = c.w[(size_t)k * c.ldn + q];
-        }
-    }
+    sim_hook_ctx(c, buf, n, m);
+    hook_estep_smooth(c, n, m, lp, cnn, v, s, lweight, lsim, bias, p_vl_out, w_out, info_out);
     return 0;
 }
 
 int sim_mstep(int n, int m, const double* l, const double* w, double* vp_out) {
-    vpk_em_params p;
-    memset(&p, 0, sizeof(p));
-    p.use_weights = 1; p.num_init_vp = m; p.num_iter = 1; p.split_merge_freq = 10; p.s_thresh = 1e-200;
     EmCtx c;
     std::vector<double> buf;
-    make_ctx(c, buf, n, p, false, 0);
-    c.l = const_cast<double*>(l);
-    g_sh.M = m;
-    for (int k = 0; k < m; ++k)
-        for (int q = 0; q < n; ++q) {
-            c.w[(size_t)k * c.ldn + q] = w[(size_t)k * n + q];
-            c.lvsq[(size_t)k * c.ldn + q] = 1.0;
-            c.pvl[(size_t)k * c.ldn + q] = 1.0;
-        }
-    for (int k = 0; k < 3 * m; ++k) { g_sh.cur[k] = (k % 3 == 2) ? 1.0 : 0.0; g_sh.nxt[k] = 0.0; }
-    mstep(c, 0, 1e-6);
-    for (int k = 0; k < 3 * m; ++k) vp_out[k] = g_sh.nxt[k];
+    sim_hook_ctx(c, buf, n, m);
+    hook_mstep(c, n, m, l, w, vp_out, nullptr);
     return 0;
 }
 
-// the matching wrapper of vpk_mstep_full (csrc/vpk_em.hip: mstep_full_kernel)
 int sim_mstep_full(int n, int m, const double* l, const double* w, const double* lvsq, const double* p_vl, const int* assoc,
                    const double* cur, double max_stdd, double s_thresh, double* vp_out, double* s_out, double* err_out,
                    int* removed_out) {
-    vpk_em_params p;
-    memset(&p, 0, sizeof(p));
-    p.use_weights = 1; p.num_init_vp = m; p.num_iter = 1; p.split_merge_freq = 10; p.s_thresh = s_thresh;
     EmCtx c;
     std::vector<double> buf;
-    make_ctx(c, buf, n, p, false, 0);
-    c.l = const_cast<double*>(l);
-    g_sh.M = m;
-    for (int k = 0; k < m; ++k)
-        for (int q = 0; q < n; ++q) {
-            c.w[(size_t)k * c.ldn + q] = w[(size_t)k * n + q];
-            c.lvsq[(size_t)k * c.ldn + q] = lvsq[(size_t)k * n + q];
-            c.pvl[(size_t)k * c.ldn + q] = p_vl[(size_t)k * n + q];
-        }
-    if (assoc)
-        for (int q = 0; q < n; ++q) c.assoc[q] = assoc[q];
-    for (int k = 0; k < 3 * m; ++k) { g_sh.cur[k] = cur[k]; g_sh.nxt[k] = 0.0; }
-    for (int k = 0; k < m; ++k) g_sh.s[k] = -1.0;
-    mstep(c, assoc ? 1 : 0, max_stdd);
-    for (int k = 0; k < 3 * m; ++k) vp_out[k] = g_sh.nxt[k];
-    for (int k = 0; k < m; ++k) { s_out[k] = g_sh.s[k]; err_out[k] = g_sh.err[k]; removed_out[k] = g_sh.removed[k]; }
+    sim_hook_ctx(c, buf, n, m);
+    hook_mstep_full(c, n, m, l, w, lvsq, p_vl, assoc, cur, max_stdd, s_thresh, vp_out, s_out, err_out, removed_out);
     return 0;
 }
 
-// calc_vp_line_counts on its own, as csrc/vpk_em.hip's line_counts_kernel sets it up
 int sim_line_counts(int n, int m, const double* lp, const double* v, const double* s, const double* w, const double* lweight,
                     double thresh, double* counts_out, double* counts_w_out, long long* assoc_out) {
-    vpk_em_params p;
-    memset(&p, 0, sizeof(p));
-    p.use_weights = 1; p.num_init_vp = m; p.num_iter = 1; p.split_merge_freq = 10; p.outlier_thresh = thresh;
     EmCtx c;
     std::vector<double> buf;
-    make_ctx(c, buf, n, p, false, 0);
-    c.lp = lp;
-    for (int k = 0; k < n; ++k) c.lweight[k] = lweight[k];
-    for (int k = 0; k < 3 * m; ++k) g_sh.cur[k] = v[k];
-    for (int k = 0; k < m; ++k) g_sh.s[k] = s[k];
-    g_sh.M = m; g_sh.ncomp = 0; g_sh.sigma_prior = 1.0;
-    line_geometry_setup(c);
-    estep(c, g_sh.cur);
-    for (int k = 0; k < m; ++k)
-        for (int q = 0; q < n; ++q) c.w[(size_t)k * c.ldn + q] = w[(size_t)k * n + q];
-    assign_lines(c, true);
-    count_lines(c);
-    for (int k = 0; k < m; ++k) { counts_out[k] = g_sh.cnt[k]; counts_w_out[k] = g_sh.cntw[k]; }
-    for (int k = 0; k < n; ++k) assoc_out[k] = c.assoc[k];
+    sim_hook_ctx(c, buf, n, m);
+    hook_line_counts(c, n, m, lp, v, s, w, lweight, thresh, counts_out, counts_w_out, assoc_out);
     return 0;
 }
 
 int sim_cluster2(int n, const double* ldist, int* labels_out, unsigned* flags_out) {
-    std::vector<double> D(ldist, ldist + (size_t)n * n);
+    std::vector<double> D(ldist, ldist + (size_t)n * n);   // the working copy (the library's is in its workspace)
     std::vector<int> member(n), csize(n);
-    g_sh.flags = 0;
-    const int ld = n | 1;
-    if (n <= CLUSTER_LDS_MAX && cluster_lds_doubles(n) <= WT_DOUBLES) {   // same choice as the kernel
-        double* DL = WT();
-        for (int a = 0; a < n; ++a)
-            for (int b = 0; b < n; ++b) {
-                const double v = D[(size_t)a * n + b];
-                DL[a * ld + b] = (a == b || !(v + D[(size_t)b * n + a] != 0.0)) ? -1.0 : v;
-            }
-        cluster2_lds(n);
-        const int* lmember = cluster_lds_labels(DL, n);
-        for (int q = 0; q < n; ++q) member[q] = lmember[q];
-    } else {
-        cluster2(g_sh, n, D.data(), member.data(), csize.data());
-    }
-    for (int i = 0; i < n; ++i) labels_out[i] = member[i];
-    *flags_out = g_sh.flags;
+    hook_cluster2(n, D.data(), member.data(), csize.data(), labels_out, flags_out);
     return 0;
 }
 

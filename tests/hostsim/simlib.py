@@ -3,6 +3,7 @@
 Builds tests/hostsim/_build/libvpk_hostsim.so with g++ on first use.  See hip_sim.hpp for what
 this is (a single-lane logic check of the device code) and is not (a product path)."""
 import ctypes
+import glob
 import os
 import subprocess
 
@@ -11,9 +12,9 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 BUILD = os.path.join(HERE, "_build")
 SO = os.path.join(BUILD, "libvpk_hostsim.so")
-SRC = [os.path.join(HERE, "sim_em.cpp"), os.path.join(HERE, "hip_sim.hpp"),
-       os.path.join(HERE, "..", "..", "vanishing_points_2017_amd", "csrc", "em_device.hpp"),
-       os.path.join(HERE, "..", "..", "vanishing_points_2017_amd", "csrc", "em_layout.hpp")]
+CSRC = os.path.join(HERE, "..", "..", "vanishing_points_2017_amd", "csrc")
+# sim_em.cpp first (the one file g++ is given); every header it can reach makes the library stale
+SRC = [os.path.join(HERE, "sim_em.cpp")] + sorted(glob.glob(os.path.join(HERE, "*.hpp")) + glob.glob(os.path.join(CSRC, "*.hpp")))
 
 
 class EmParams(ctypes.Structure):

@@ -340,7 +340,7 @@ def test_row_sliced_smoother_gives_the_bits_of_the_round2_kernels():
 @pytest.mark.parametrize("n", [511, 512, 513, 700, 1000, 1023, 1200])
 def test_tiled_pair_pass_gives_the_bits_of_the_row_by_row_pass(n):
     """calc_lsim + line_rating_knn for images of 512 lines and more (round 6): pass 1 walks tiles of 16 rows x 64 columns so that a
-    mirrored 128-byte line is written whole by one wave (em_device.hpp: pairwise_tiles).  Same pair function, same positions:
+    mirrored 128-byte line is written whole by one wave (em_setup.hpp: pairwise_tiles).  Same pair function, same positions:
     lsim, the kNN score and the line angles must equal the row-by-row pass (vpk_em_set_smoother(1)) bit for bit; 511 lines
     take the row-by-row pass under both settings."""
     from vanishing_points_2017_amd import kernels, synth

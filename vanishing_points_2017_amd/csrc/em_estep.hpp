@@ -1,0 +1,255 @@
+// em_estep.hpp -- the E-step, with the panel geometry of the row-sliced smoother and the plan that chooses it: the E-step writes the
+// operand panel that plan describes, so the three stay together.
+// One part of em_device.hpp (the conventions, and why the unit is compiled with -ffp-contract=off, are there).
+#ifndef VPK_EM_ESTEP_HPP_
+#define VPK_EM_ESTEP_HPP_
+
+#include "em_ctx.hpp"
+
+namespace vpk {
+
+// ---- geometry of the row-sliced smoother (smooth_rows) -----------------------------------------------------------
+// The N rows of lsim are cut into EIGHT slices of jch = ceil(N / 8) consecutive rows (the summation order every stored
+// result was produced with: per (column, VP) eight ascending fma chains, then ((((p0 + p1) + p2) + ...) + p7).  The
+// operand panel w_[line][vp] is kept slice by slice, [slice][row in slice][W], with the slice stride padded to 16 mod 32
+// doubles so that the two slices whose rows one ds_read_b64 touches (lanes 0-31: two rows of 16 lanes) lie in
+// different halves of the 64 banks.
+constexpr int RS_TT = 4;                               // VPs per reduction round (one output per lane and round)
+constexpr int RS_RED_DOUBLES = RS_TT * 16 * 9;         // per wave: [vp][column][8 slices + 1 pad]
+constexpr int RS_PANEL_FLAG = 0x100;                   // sh.ibuf[5] = RS_PANEL_FLAG + W: the E-step left this layout
+VPK_DEV int rs_jchunk(int N) { return (N + 7) >> 3; }
+VPK_DEV int rs_sstride(int jch, int W) { const int q = jch * W; return q + ((16 - q) & 31); }
+VPK_DEV int rs_panel_doubles(int jch, int W) { return 8 * rs_sstride(jch, W) + 32; }   // + slack: lanes read 16 + i past a row
+VPK_DEV int rs_row(int n, int jch, int S, int W) { const int sl = n / jch; return sl * S + (n - sl * jch) * W; }
+// Which smoother the next smooth() takes for M hypotheses -- decided in ONE place because the E-step writes the panel in
+// that smoother's layout.  0: none in LDS (wsrc in HBM), 1: smooth_full's [line][W], 2: smooth_rows' sliced layout.
+// VPs per pass of smooth_rows when the whole panel does not fit: the widest multiple of 8 (<= 32) whose sliced panel and
+// the reduction scratch fit the LDS budget; 0 = not even 8
+VPK_DEV int rs_wfit(const EmCtx& c) {
+    const int jch = rs_jchunk(c.N);
+    for (int w = 32; w >= MT; w -= MT)
+        if (rs_panel_doubles(jch, w) + 8 * RS_RED_DOUBLES <= c.wt_doubles) return w;
+    return 0;
+}
+// Which smoother the next smooth() takes for M hypotheses -- decided in ONE place because the E-step writes the panel in
+// that smoother's layout.  0: none in LDS (wsrc in HBM; smooth_full in passes or smooth_blocks), 1: smooth_full's
+// [line][W], 2: smooth_rows' sliced layout, 3: wsrc in HBM, smooth_rows in passes of rs_wfit() VPs.
+VPK_DEV int smooth_plan(const EmCtx& c, int M) {
+    const int N = c.N;
+    if (!c.prm.use_weights || M <= 0) return 0;
+    const int Wp = ((M + MT - 1) / MT) * MT;
+    const bool rows_ok = WAVE == 64 && nwaves() == 8 && c.smoother != 1;
+    const int colw = N > WAVE ? 2 * WAVE : WAVE;                   // smooth_full's column groups: when they divide evenly
+    const bool direct = (((N + colw - 1) / colw) % 8) == 0;        // among the waves it sums ALL rows in one chain
+    if (M <= 32) {
+        if (rows_ok && !direct && rs_panel_doubles(rs_jchunk(N), Wp) + 8 * RS_RED_DOUBLES <= c.wt_doubles) return 2;
+        if ((long long)N * Wp <= c.wt_doubles) return 1;
+    }
+    // In passes: smooth_rows keeps smooth_full's eight-slice order, so it may stand in wherever smooth_full would run
+    // (a panel of at least 8 VPs fits the OLD layout: wfit >= 8), never for smooth_blocks (one chain per column).
+    if (rows_ok && !direct && (c.wt_doubles / N) / MT >= 1 && rs_wfit(c) >= MT) return 3;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// E-step: calc_probabilities (probability_functions.py:99-147, "angle" branch)
+// ---------------------------------------------------------------------------------------------
+// X points at sh.cur or sh.nxt.  Writes lvsq[m][n], pvl[m][n], wsrc[n][m]; floors sh.s (:139).
+// (Round 6, measured: the body inlined into em_run's main loop -- to save the callee-saved register traffic of one call per iteration,
+//  which did pay for the smoother's thin wrappers -- makes the E-step 2.5 x SLOWER, 51 -> 130 ms of workgroup time per YUD batch: inside
+//  em_run's register allocation the line loop spills.  The phases stay functions of their own.)
+VPK_DEVFN void estep(EmCtx& c, const double* X) {
+    Shared& sh = SH();
+    const int M = sh.M, N = c.N;
+    const double kk = -0.5 / (sh.sigma_prior * sh.sigma_prior);
+    long long tq_ = clock_ticks();
+    // prior p(v): a group of VPG lanes per VP (four VPs per wave: the asin/cos chains of four VPs run in one
+    // wave's lanes), lanes over mixture components (calc_angles :252-259, calc_pdf :8-40)
+    {
+        constexpr int G = VPG;
+        const int gl = lane() % G;
+        const int per_round = nwaves() * (WAVE / G);
+        for (int m = wave_id() * (WAVE / G) + lane() / G; m < M; m += per_round) {
+            double x0 = X[3 * m], x1 = X[3 * m + 1], x2 = X[3 * m + 2];
+            double alpha, beta;
+            vp_angles(x0, x1, alpha, beta);
+            double acc = 0.0;
+            for (int q = gl; q < sh.ncomp; q += G) {
+                acc += mixture_term(alpha, beta, sh.pma[q], sh.pmb[q], kk) * sh.pw[q];
+            }
+            acc = group_sum<G>(acc);
+            if (gl == 0) {
+                sh.pv[m] = acc;
+                sh.vx[m] = x0 / x2;                          // calc_lvsq_angle :165-166
+                sh.vy[m] = x1 / x2;
+                double sm = sh.s[m];
+                sm = sm > 1e-200 ? sm : 1e-200;              // calc_plv :139 (in place)
+                sh.s[m] = sm;
+                sh.k2[m] = 1.0 / sqrt(2 * PI_D * sm);        // :145
+            }
+        }
+    }
+    block_sync();
+    if (tid() == 0) sh.dbuf[14] += lap(tq_);
+    // When the smoother's whole operand panel fits in LDS the weights go there directly ([line][vp],
+    // Wp = M rounded to the VP tile) as well as to HBM, and smooth_full skips its staging pass.
+    const int Wp = ((M + MT - 1) / MT) * MT;
+    const int plan = smooth_plan(c, M);                      // 1: [line][Wp] for smooth_full, 2: slice by slice for smooth_rows
+    const bool panel = plan == 1 || plan == 2;
+    const int rs_jch = rs_jchunk(N), rs_S = rs_sstride(rs_jch, Wp);
+    double* wt = WT();
+    // one thread per line; the VP loop is unrolled four deep with the four sqrt/div/exp chains written
+    // side by side (independent until the ordered sum), because a lone wave per SIMD is bound by the
+    // latency of that dependent chain, not by issue
+    cgdp gmx = c.drow, gmy = c.drow + c.ldn, gvx = c.drow + 2 * (size_t)c.ldn, gvy = c.drow + 3 * (size_t)c.ldn,
+         gn2 = c.drow + 4 * (size_t)c.ldn;
+    constexpr int EU = 4;
+    // LANES PER LINE (round 6).  One thread per line leaves 512 - N threads idle and the busy ones with M dependent sqrt / div / exp
+    // chains each: at the YUD shape (N ~ 250, M ~ 22) the line part took as long as the smoother's row loops.  When the panel is in
+    // LDS and T N <= 512, T = 2, 4 or 8 ADJACENT lanes share a line, each a contiguous run of ceil(M / T) VPs.  Every (line, VP) value
+    // is the same expression as below; p_l (:116) is still ONE chain over the VPs in ascending order -- lane h takes the running sum
+    // from lane h - 1 and continues it over its own terms, re-read from the line's panel row -- so every output has the same bits.
+    int T = 1;
+    if (panel && WAVE == 64 && c.smoother != 1)              // (vpk_em_set_smoother(1): the forms of the earlier rounds, for the bit-equality test)
+        while (T < 8 && 2 * T * N <= nthreads()) T *= 2;
+    if (T > 1) {
+        const int n_ = tid() / T, h = tid() - n_ * T;
+        const bool on = n_ < N;
+        const int n = on ? n_ : N - 1;
+        const int Mh = (M + T - 1) / T;
+        const int m_lo = on ? (h * Mh < M ? h * Mh : M) : 0, m_hi = on ? (m_lo + Mh < M ? m_lo + Mh : M) : 0;
+        const double lmx = gmx[n], lmy = gmy[n], v2x = gvx[n], v2y = gvy[n], n2 = gn2[n];
+        const double lw = c.lweight[n];
+        gdp lvq = c.lvsq + n, pvq = c.pvl + n;
+        double* wl = wt + (plan == 2 ? (size_t)rs_row(n, rs_jch, rs_S, Wp) : (size_t)n * Wp);
+        int m = m_lo;
+        for (; m + EU <= m_hi; m += EU) {
+            double lv[EU], tt[EU];
+#pragma unroll
+            for (int u = 0; u < EU; ++u) {
+                const double v1x = lmx - sh.vx[m + u], v1y = lmy - sh.vy[m + u];
+                const double n1 = norm2(v1x, v1y);
+                const double cc = 1 - fabs(dot2(v1x, v1y, v2x, v2y) / (n1 * n2));
+                lv[u] = cc * cc;                             // :174
+            }
+#pragma unroll
+            for (int u = 0; u < EU; ++u)
+                tt[u] = (exp_underflow(-(lv[u] / (2 * sh.s[m + u]))) * sh.k2[m + u]) * sh.pv[m + u];   // calc_plv :137-145
+#pragma unroll
+            for (int u = 0; u < EU; ++u) {
+                lvq[(size_t)(m + u) * c.ldn] = lv[u];
+                wl[m + u] = tt[u];
+            }
+        }
+        for (; m < m_hi; ++m) {
+            const double v1x = lmx - sh.vx[m], v1y = lmy - sh.vy[m];
+            const double n1 = norm2(v1x, v1y);
+            const double cc = 1 - fabs(dot2(v1x, v1y, v2x, v2y) / (n1 * n2));
+            const double lv1 = cc * cc;
+            lvq[(size_t)m * c.ldn] = lv1;
+            wl[m] = (exp_underflow(-(lv1 / (2 * sh.s[m]))) * sh.k2[m]) * sh.pv[m];
+        }
+        double pl = 0.0;                                     // p_l = dot(p_lv, p_v) :116, in VP order, handed from lane to lane
+        for (int hh = 0; hh < T; ++hh) {
+            const double prev = wave_bcast(pl, (lane() + WAVE - 1) & (WAVE - 1));
+            if (h == hh) {
+                if (hh > 0) pl = prev;
+                for (m = m_lo; m < m_hi; ++m) pl += wl[m];
+            }
+        }
+        pl = wave_bcast(pl, lane() | (T - 1));               // the line's last lane holds the whole sum
+        pl = (pl > 1e-12 || is_nan(pl)) ? pl : 1e-12;        // :117
+        m = m_lo;
+        for (; m + EU <= m_hi; m += EU) {
+            double q[EU];
+#pragma unroll
+            for (int u = 0; u < EU; ++u) q[u] = wl[m + u];
+#pragma unroll
+            for (int u = 0; u < EU; ++u) q[u] = q[u] / pl;   // calc_pvl :128
+#pragma unroll
+            for (int u = 0; u < EU; ++u) {
+                pvq[(size_t)(m + u) * c.ldn] = q[u];
+                wl[m + u] = q[u] * lw;                       // weight_matrix :519
+            }
+        }
+        for (; m < m_hi; ++m) {
+            const double q1 = wl[m] / pl;
+            pvq[(size_t)m * c.ldn] = q1;
+            wl[m] = q1 * lw;
+        }
+        if (on && h == T - 1)
+            for (m = M; m < Wp; ++m) wl[m] = 0.0;            // padding of the last VP tile
+    } else
+    for (int n = tid(); n < N; n += nthreads()) {
+        const double lmx = gmx[n], lmy = gmy[n], v2x = gvx[n], v2y = gvy[n], n2 = gn2[n];
+        gdp lvq = c.lvsq + n, pvq = c.pvl + n;
+        double* wl = wt + (plan == 2 ? (size_t)rs_row(n, rs_jch, rs_S, Wp) : (size_t)n * Wp);   // this line's panel row; parks p_lv p_v until p_l is known
+        double pl = 0.0;
+        int m = 0;
+        for (; m + EU <= M; m += EU) {
+            double lv[EU], tt[EU];
+#pragma unroll
+            for (int u = 0; u < EU; ++u) {
+                const double v1x = lmx - sh.vx[m + u], v1y = lmy - sh.vy[m + u];
+                const double n1 = norm2(v1x, v1y);
+                const double cc = 1 - fabs(dot2(v1x, v1y, v2x, v2y) / (n1 * n2));
+                lv[u] = cc * cc;                             // :174
+            }
+#pragma unroll
+            for (int u = 0; u < EU; ++u)
+                tt[u] = (exp_underflow(-(lv[u] / (2 * sh.s[m + u]))) * sh.k2[m + u]) * sh.pv[m + u];   // calc_plv :137-145
+#pragma unroll
+            for (int u = 0; u < EU; ++u) {
+                lvq[(size_t)(m + u) * c.ldn] = lv[u];
+                if (panel) wl[m + u] = tt[u]; else pvq[(size_t)(m + u) * c.ldn] = tt[u];
+                pl += tt[u];                                 // p_l = dot(p_lv, p_v) :116, in VP order
+            }
+        }
+        for (; m < M; ++m) {
+            const double v1x = lmx - sh.vx[m], v1y = lmy - sh.vy[m];
+            const double n1 = norm2(v1x, v1y);
+            const double cc = 1 - fabs(dot2(v1x, v1y, v2x, v2y) / (n1 * n2));
+            const double lv1 = cc * cc;
+            lvq[(size_t)m * c.ldn] = lv1;
+            const double t1 = (exp_underflow(-(lv1 / (2 * sh.s[m]))) * sh.k2[m]) * sh.pv[m];
+            if (panel) wl[m] = t1; else pvq[(size_t)m * c.ldn] = t1;
+            pl += t1;
+        }
+        pl = (pl > 1e-12 || is_nan(pl)) ? pl : 1e-12;        // :117
+        const double lw = c.lweight[n];
+        gdp ws = c.wsrc + (size_t)n * c.mcap;
+        m = 0;
+        for (; m + EU <= M; m += EU) {
+            double q[EU];
+#pragma unroll
+            for (int u = 0; u < EU; ++u) q[u] = panel ? wl[m + u] : pvq[(size_t)(m + u) * c.ldn];
+#pragma unroll
+            for (int u = 0; u < EU; ++u) q[u] = q[u] / pl;   // calc_pvl :128
+#pragma unroll
+            for (int u = 0; u < EU; ++u) {
+                pvq[(size_t)(m + u) * c.ldn] = q[u];
+                if (panel) wl[m + u] = q[u] * lw;            // weight_matrix :519 (the HBM copy has no reader when the
+                else ws[m + u] = q[u] * lw;                  //   smoother takes the whole panel from LDS in one pass)
+            }
+        }
+        for (; m < M; ++m) {
+            const double q1 = (panel ? wl[m] : pvq[(size_t)m * c.ldn]) / pl;
+            pvq[(size_t)m * c.ldn] = q1;
+            if (panel) wl[m] = q1 * lw; else ws[m] = q1 * lw;
+        }
+        for (m = M; m < Wp; ++m) {                           // padding of the last VP tile
+            if (panel) wl[m] = 0.0; else ws[m] = 0.0;
+        }
+    }
+    if (plan == 2)                                           // zero operand rows where a short or empty slice has no line
+        for (int p = N * Wp + tid(); p < 8 * rs_jch * Wp; p += nthreads()) {
+            const int j = p / Wp;
+            wt[rs_row(j, rs_jch, rs_S, Wp) + (p - j * Wp)] = 0.0;
+        }
+    if (tid() == 0) sh.dbuf[15] += lap(tq_);
+    if (tid() == 0) sh.ibuf[5] = plan == 2 ? RS_PANEL_FLAG + Wp : (plan == 1 ? Wp : 0);   // consumed (and cleared) by smooth()
+    block_sync();
+}
+
+}  // namespace vpk
+#endif

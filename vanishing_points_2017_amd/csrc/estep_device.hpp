@@ -2,7 +2,7 @@
 // (:133-147), calc_pvl (:123-130) and the three distance measures calc_lvsq_angle (:157-176), calc_lvsq_dotprod (:150-154)
 // and calc_lvsq_area (:179-209) for a ragged batch of images, any number of VPs each.
 //
-// One user: vpk_estep.hip (vpk_estep_batch).  The EM workgroup keeps its own E-step (em_device.hpp: estep and
+// One user: vpk_estep.hip (vpk_estep_batch).  The EM workgroup keeps its own E-step (em_estep.hpp: estep, em_setup.hpp:
 // line_geometry_setup, "angle" only, at most 64 VPs, fused with the smoother's panel): its per-pair expression is RESTATED
 // here operand for operand instead of shared, so that this file cannot move the EM kernel's register allocation.
 // tests/test_gpu_estep_surface.py holds the two copies together bit for bit.
@@ -54,7 +54,7 @@ struct EstepArgs {
 };
 
 // ---- the per-line constants and the per-pair distance of each measure ---------------------------------------------------
-// angle: line_geometry_setup's five values (em_device.hpp; calc_lvsq_angle :169, :172 evaluates them for every VP) --
+// angle: line_geometry_setup's five values (em_setup.hpp; calc_lvsq_angle :169, :172 evaluates them for every VP) --
 //        midpoint, direction lp[0:2] - lp[2:4] and its norm
 // area:  midpoint (:192), the first end point (:194-195) and c = |lm - lp[2:4]| (:204)
 // dotprod: the homogeneous line (:151)
@@ -118,7 +118,7 @@ template <int MEASURE> VPK_DEV double estep_lvsq(const double (&g)[5], double w0
 
 // Tile `tile` of image b over the VP chunks [c_lo, c_hi), by a workgroup of ESTEP_TILE threads: one line per thread.
 // p_l (:116) is ONE chain over the VPs in ascending order of the terms p_lv p_v, floored at 1e-12 with NaN let through
-// (:117, as em_device.hpp's estep); the terms are parked in p_vl_out and divided in a second sweep (:128), in which a thread
+// (:117, as em_estep.hpp's estep); the terms are parked in p_vl_out and divided in a second sweep (:128), in which a thread
 // reads back only what it wrote itself.  Every output pointer may be null.
 template <int MEASURE> VPK_DEV void estep_tile(const EstepArgs& a, int b, long long tile, int c_lo, int c_hi) {
     double* st = reinterpret_cast<double*>(lds_base());      // [ESTEP_SLOTS][ESTEP_CHUNK]

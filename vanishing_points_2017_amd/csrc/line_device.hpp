@@ -2,7 +2,7 @@
 // (closest distance, the sharpened cosine, the proximity), calc_lsim (:87-108), line_rating_knn (:34-72), lines_angles
 // (:765-776) and line_length (:761) as device functions.
 //
-// Two users: the EM workgroup (em_device.hpp: pairwise_setup / pairwise_tiles, weights_setup) and the stand-alone batched
+// Two users: the EM workgroup (em_setup.hpp: pairwise_setup / pairwise_tiles, weights_setup) and the stand-alone batched
 // kernels of vpk_lines.hip (vpk_line_similarity_batch, vpk_line_rating_batch), whose bodies are the two functions at the end
 // of this file.  Written against the vocabulary of wave_prims.hpp only, so that tests/hostsim/sim_lines.cpp compiles it
 // unmodified with g++ (hip_sim.hpp: one lane, WAVE = 1, ROWG = 1).  Both device units are compiled with -ffp-contract=off:
@@ -163,7 +163,7 @@ struct LineBatchArgs {
 
 // calc_lsim (:87-108) for one block of LS_RB rows of one image, by one workgroup.
 //
-// The walk is pairwise_tiles' (em_device.hpp; the comment above it gives the reason): tiles of LS_RB rows x WAVE columns,
+// The walk is pairwise_tiles' (em_setup.hpp; the comment above it gives the reason): tiles of LS_RB rows x WAVE columns,
 // the tile's columns over the lanes, the rows' geometries in LDS.  Every unordered pair (i, j < i) is evaluated once with
 // a = line i and b = line j -- the reference's argument order (:105-106) and pairwise_setup's -- and stored to (i, j) and
 // (j, i).  The direct half of a tile is 512 contiguous bytes per row and store instruction.  The mirrored half of an

@@ -1,7 +1,7 @@
 // prior_device.hpp -- the CNN prior over the (alpha, beta) half sphere: pdf_params, calc_angles and calc_pdf of the
 // reference's probability_functions.py as device functions.
 //
-// Two users: the EM workgroup (em_device.hpp: prior_setup and the first stage of estep) and the stand-alone kernels of
+// Two users: the EM workgroup (em_setup.hpp: prior_setup, and the first stage of em_estep.hpp's estep) and the stand-alone kernels of
 // vpk_prior.hip (vpk_prior_params, vpk_mixture_pdf).  Written against the vocabulary of wave_prims.hpp only, so that
 // tests/hostsim/sim_prior.cpp compiles it unmodified with g++ (hip_sim.hpp: one lane, WAVE = 1).  Both device units are
 // compiled with -ffp-contract=off: products and sums round like the reference's separate NumPy ufunc calls.

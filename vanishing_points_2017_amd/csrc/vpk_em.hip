@@ -1,9 +1,10 @@
-// vpk_em.hip -- EM kernels and their C-ABI entry points (see include/vpk.h).
+// vpk_em.hip -- EM kernels and their C-ABI entry points (see include/vpk.h): the batch kernel with its time-slice
+// session, and the fine-grained single-workgroup entry points, whose bodies are em_hooks.hpp's.
 //
 // Compiled with -ffp-contract=off (see em_device.hpp).  One persistent workgroup of EM_THREADS
 // threads per slot; workgroups pull images from a device-side queue (largest N first), so a
 // ragged batch keeps every CU busy without host round trips.
-#include "em_device.hpp"
+#include "em_hooks.hpp"
 #include "vpk_internal.hpp"
 
 #include <algorithm>
@@ -284,255 +285,85 @@ __global__ void em_rotate_kernel(int* ctr, int cap_waiting, int cap_started) {
 }
 
 // ---- fine-grained kernels (one workgroup, unit parity) ------------------------------------------
+// The bodies are em_hooks.hpp's, which the tests' host build compiles too; a kernel only makes the context: value-initialised,
+// the launch's LDS budget and smoother, the scratch slot bound.
+VPK_DEV EmCtx kernel_ctx(int wt_doubles, int smoother) {
+    EmCtx c{};
+    c.wt_doubles = wt_doubles; c.smoother = smoother;
+    return c;
+}
+VPK_DEV EmCtx kernel_ctx(int wt_doubles, int smoother, double* ws, const EmLayout& L) {
+    EmCtx c = kernel_ctx(wt_doubles, smoother);
+    bind_scratch(c, ws, L, false);
+    return c;
+}
+
 __global__ __launch_bounds__(EM_BOUND) void pairwise_kernel(int n, const double* lp, EmLayout L, double* ws,
                                                               double* lsim_out, double* lscore_out,
                                                               double* langle_out, int smoother) {
-    EmCtx c;
-    c.N = n; c.lp = (cgdp)lp; c.wt_doubles = WT_DOUBLES; c.smoother = smoother;
-    c.prm.use_weights = 1;
-    bind_scratch(c, ws, L, false);
-    pairwise_setup(c, true);
-    for (int p = tid(); p < n * n; p += nthreads()) lsim_out[p] = c.lsim[(size_t)(p / n) * c.ld + p % n];
-    for (int i = tid(); i < n; i += nthreads()) { lscore_out[i] = c.lscore[i]; langle_out[i] = c.langle[i]; }
+    EmCtx c = kernel_ctx(WT_DOUBLES, smoother, ws, L);
+    hook_pairwise(c, n, lp, lsim_out, lscore_out, langle_out);
 }
 
 __global__ __launch_bounds__(EM_BOUND) void init_vps_kernel(const float* cnn, const unsigned char* sphere,
                                                               int ssize, int num_max, double* v0_out,
                                                               int* m0_out, float* weights_out) {
-    VPK_SHARED_DECL;
-    EmCtx c;
-    c.N = 0; c.cnn = (cgfp)cnn; c.sphere = (cgbp)sphere; c.ssize = ssize; c.wt_doubles = WT_DOUBLES;
-    c.prm.num_init_vp = num_max;
-    initial_vps(c);
-    for (int k = tid(); k < 3 * sh.M; k += nthreads()) v0_out[k] = sh.cur[k];
-    if (tid() == 0) *m0_out = sh.M;
-    block_sync();
-    prior_setup(c);
-    for (int k = tid(); k < NCELL; k += nthreads()) weights_out[k] = sh.wts[k];
+    EmCtx c = kernel_ctx(WT_DOUBLES, 0);
+    hook_init_vps(c, cnn, sphere, ssize, num_max, v0_out, m0_out, weights_out);
 }
 
 __global__ __launch_bounds__(EM_BOUND) void estep_kernel(int n, int m, const double* lp, const float* cnn,
                                                            const double* v, double* s, EmLayout L, double* ws,
                                                            double* p_v_out, double* lvsq_out, double* p_vl_out,
                                                            double* p_l_out, int smoother) {
-    VPK_SHARED_DECL;
-    EmCtx c;
-    c.N = n; c.lp = (cgdp)lp; c.cnn = (cgfp)cnn; c.wt_doubles = WT_DOUBLES; c.smoother = smoother;
-    c.prm.use_weights = 1;
-    bind_scratch(c, ws, L, false);
-    prior_setup(c);
-    for (int k = tid(); k < n; k += nthreads()) c.lweight[k] = 1.0;
-    for (int k = tid(); k < 3 * m; k += nthreads()) sh.cur[k] = v[k];
-    for (int k = tid(); k < m; k += nthreads()) sh.s[k] = s[k];
-    if (tid() == 0) sh.M = m;
-    block_sync();
-    line_geometry_setup(c);
-    estep(c, sh.cur);
-    for (int k = tid(); k < m; k += nthreads()) { s[k] = sh.s[k]; p_v_out[k] = sh.pv[k]; }
-    for (int p = tid(); p < m * n; p += nthreads()) {
-        int k = p / n, q = p % n;
-        lvsq_out[p] = c.lvsq[(size_t)k * c.ldn + q];
-        p_vl_out[p] = c.pvl[(size_t)k * c.ldn + q];
-    }
-    // p_l is not kept by the E-step; re-evaluate sum_m p_lv * p_v with the floor (:116-117)
-    for (int q = tid(); q < n; q += nthreads()) {
-        double pl = 0.0;
-        for (int k = 0; k < m; ++k) {
-            double lv = c.lvsq[(size_t)k * c.ldn + q];
-            pl += exp(-(lv / (2 * sh.s[k]))) * sh.k2[k] * sh.pv[k];
-        }
-        p_l_out[q] = (pl > 1e-12 || pl != pl) ? pl : 1e-12;
-    }
+    EmCtx c = kernel_ctx(WT_DOUBLES, smoother, ws, L);
+    hook_estep(c, n, m, lp, cnn, v, s, p_v_out, lvsq_out, p_vl_out, p_l_out);
 }
 
 __global__ __launch_bounds__(EM_BOUND) void weight_matrix_kernel(int n, int m, const double* p_vl,
                                                                    const double* lweight, const double* lsim,
                                                                    double bias, EmLayout L, double* ws,
                                                                    double* w_out, int smoother, int wt_doubles) {
-    VPK_SHARED_DECL;
-    EmCtx c;
-    c.N = n; c.wt_doubles = wt_doubles; c.smoother = smoother;
-    c.prm.use_weights = 1;
-    c.prm.wbias = bias;
-    bind_scratch(c, ws, L, false);
-    for (int p = tid(); p < n * n; p += nthreads())      // caller's matrix (row stride n) -> padded rows
-        c.lsim[(size_t)(p / n) * c.ld + p % n] = lsim[p];
-    if (tid() == 0) { sh.M = m; sh.ibuf[5] = 0; sh.ibuf[2] = 0; }   // no E-step ran: the operand panel is not in LDS
-    for (int i = tid(); i < n; i += nthreads()) c.lweight[i] = lweight[i];
-    for (int p = tid(); p < m * n; p += nthreads()) c.pvl[(size_t)(p / n) * c.ldn + p % n] = p_vl[p];   // (the sparse smoother's source)
-    for (int p = tid(); p < n * c.mcap; p += nthreads()) {
-        int i = p / c.mcap, k = p % c.mcap;
-        c.wsrc[(size_t)i * c.mcap + k] = k < m ? p_vl[(size_t)k * n + i] * lweight[i] : 0.0;
-    }
-    block_sync();
-    for (int k = tid(); k < n; k += nthreads()) {
-        double sum = 0.0;
-        for (int j = 0; j < n; ++j) sum += lsim[(size_t)j * n + k];
-        c.den[k] = 1 + bias * c.lweight[k] * sum;
-        if (!(fabs(sum) <= 1.7976931348623157e308)) sh.ibuf[2] = 1;       // (see weights_setup)
-    }
-    block_sync();
-    zero_tail_rows(c);
-    smooth(c);
-    for (int p = tid(); p < m * n; p += nthreads()) w_out[p] = c.w[(size_t)(p / n) * c.ldn + p % n];
+    EmCtx c = kernel_ctx(wt_doubles, smoother, ws, L);
+    hook_weight_matrix(c, n, m, p_vl, lweight, lsim, bias, w_out);
 }
 
-// TEST HOOK (vpk_estep_smooth): estep() followed by smooth() in ONE workgroup, so that the smoother consumes the operand panel
-// the E-step left in LDS (sh.ibuf[5]) -- the batch kernel's path, which vpk_weight_matrix (panel staged by the smoother) and
-// vpk_estep (lweight = 1, panel never read) do not reach.  The context is filled like estep_kernel's, with the caller's
-// lweight; lsim, den and the sh.ibuf[2] flag like weight_matrix_kernel's.  info_out: see include/vpk.h.
 __global__ __launch_bounds__(EM_BOUND) void estep_smooth_kernel(int n, int m, const double* lp, const float* cnn,
                                                                   const double* v, double* s, const double* lweight,
                                                                   const double* lsim, double bias, EmLayout L, double* ws,
                                                                   double* p_vl_out, double* w_out, int* info_out,
                                                                   int smoother, int wt_doubles) {
-    VPK_SHARED_DECL;
-    EmCtx c;
-    c.N = n; c.lp = (cgdp)lp; c.cnn = (cgfp)cnn; c.wt_doubles = wt_doubles; c.smoother = smoother;
-    c.prm.use_weights = 1;
-    c.prm.wbias = bias;
-    bind_scratch(c, ws, L, false);
-    prior_setup(c);
-    for (int p = tid(); p < n * n; p += nthreads())      // caller's matrix (row stride n) -> padded rows
-        c.lsim[(size_t)(p / n) * c.ld + p % n] = lsim[p];
-    for (int k = tid(); k < n; k += nthreads()) c.lweight[k] = lweight[k];
-    for (int k = tid(); k < 3 * m; k += nthreads()) sh.cur[k] = v[k];
-    for (int k = tid(); k < m; k += nthreads()) sh.s[k] = s[k];
-    if (tid() == 0) { sh.M = m; sh.ibuf[5] = 0; sh.ibuf[2] = 0; }
-    block_sync();
-    for (int k = tid(); k < n; k += nthreads()) {
-        double sum = 0.0;
-        for (int j = 0; j < n; ++j) sum += lsim[(size_t)j * n + k];
-        c.den[k] = 1 + bias * c.lweight[k] * sum;
-        if (!(fabs(sum) <= 1.7976931348623157e308)) sh.ibuf[2] = 1;       // (see weights_setup)
-    }
-    block_sync();
-    zero_tail_rows(c);
-    line_geometry_setup(c);
-    estep(c, sh.cur);
-    if (tid() == 0) {                                    // what smooth() is about to do, from its own deciding functions
-        const int plan = smooth_plan(c, m);
-        int wfit = ((c.wt_doubles / n) / MT) * MT;       // smooth_dispatch's pass width of smooth_full
-        if (wfit > 32) wfit = 32;
-        info_out[0] = plan;
-        info_out[1] = sh.ibuf[5];
-        info_out[2] = (sparse_smoother_fits(c) && sh.ibuf[2] == 0) ? 1 : 0;
-        info_out[3] = plan == 3 ? rs_wfit(c) : wfit;
-    }
-    smooth(c);                                           // (nothing between the two touches the panel region)
-    for (int k = tid(); k < m; k += nthreads()) s[k] = sh.s[k];
-    for (int p = tid(); p < m * n; p += nthreads()) {
-        const int k = p / n, q = p % n;
-        p_vl_out[p] = c.pvl[(size_t)k * c.ldn + q];
-        w_out[p] = c.w[(size_t)k * c.ldn + q];
-    }
+    EmCtx c = kernel_ctx(wt_doubles, smoother, ws, L);
+    hook_estep_smooth(c, n, m, lp, cnn, v, s, lweight, lsim, bias, p_vl_out, w_out, info_out);
 }
 
 __global__ __launch_bounds__(EM_BOUND) void mstep_kernel(int n, int m, const double* l, const double* w,
                                                            EmLayout L, double* ws, double* vp_out,
                                                            int* valid_out) {
-    VPK_SHARED_DECL;
-    EmCtx c;
-    c.N = n; c.l = (gdp) const_cast<double*>(l); c.wt_doubles = WT_DOUBLES;
-    c.prm.s_thresh = 1e-200;
-    bind_scratch(c, ws, L, false);
-    if (tid() == 0) sh.M = m;
-    for (int p = tid(); p < m * n; p += nthreads()) {
-        int k = p / n, q = p % n;
-        c.w[(size_t)k * c.ldn + q] = w[p];
-        c.lvsq[(size_t)k * c.ldn + q] = 1.0;
-        c.pvl[(size_t)k * c.ldn + q] = 1.0;
-    }
-    for (int k = tid(); k < 3 * m; k += nthreads()) { sh.cur[k] = (k % 3 == 2) ? 1.0 : 0.0; sh.nxt[k] = 0.0; }
-    block_sync();
-    mstep(c, 0, 1e-6);
-    for (int k = tid(); k < m; k += nthreads()) {
-        // "valid" mirrors calc_new_vanishing_point returning a vector (not None)
-        bool none = sh.removed[k] && sh.err[k] == -1.0 && !(sh.s[k] != sh.s[k]);
-        valid_out[k] = none ? 0 : 1;
-        for (int d = 0; d < 3; ++d) vp_out[3 * k + d] = none ? 0.0 : sh.nxt[3 * k + d];
-    }
+    EmCtx c = kernel_ctx(WT_DOUBLES, 0, ws, L);
+    hook_mstep(c, n, m, l, w, vp_out, valid_out);
 }
 
-// TEST HOOK (vpk_mstep_full): mstep() on caller-supplied state -- the context is filled like mstep_kernel's, the
-// arithmetic is mstep()'s own.  Rows the M-step does not write come back as vp = 0, s = -1.
 __global__ __launch_bounds__(EM_BOUND) void mstep_full_kernel(int n, int m, const double* l, const double* w,
                                                                 const double* lvsq, const double* p_vl, const int* assoc,
                                                                 const double* cur, double max_stdd, double s_thresh,
                                                                 EmLayout L, double* ws, double* vp_out, double* s_out,
                                                                 double* err_out, int* removed_out, int smoother) {
-    VPK_SHARED_DECL;
-    EmCtx c;
-    c.N = n; c.l = (gdp) const_cast<double*>(l); c.wt_doubles = WT_DOUBLES; c.smoother = smoother;
-    c.prm.s_thresh = s_thresh;
-    bind_scratch(c, ws, L, false);
-    if (tid() == 0) sh.M = m;
-    for (int p = tid(); p < m * n; p += nthreads()) {
-        int k = p / n, q = p % n;
-        c.w[(size_t)k * c.ldn + q] = w[p];
-        c.lvsq[(size_t)k * c.ldn + q] = lvsq[p];
-        c.pvl[(size_t)k * c.ldn + q] = p_vl[p];
-    }
-    if (assoc)
-        for (int q = tid(); q < n; q += nthreads()) c.assoc[q] = assoc[q];
-    for (int k = tid(); k < 3 * m; k += nthreads()) { sh.cur[k] = cur[k]; sh.nxt[k] = 0.0; }
-    for (int k = tid(); k < m; k += nthreads()) sh.s[k] = -1.0;
-    block_sync();
-    mstep(c, assoc ? 1 : 0, max_stdd);
-    for (int k = tid(); k < 3 * m; k += nthreads()) vp_out[k] = sh.nxt[k];
-    for (int k = tid(); k < m; k += nthreads()) { s_out[k] = sh.s[k]; err_out[k] = sh.err[k]; removed_out[k] = sh.removed[k]; }
+    EmCtx c = kernel_ctx(WT_DOUBLES, smoother, ws, L);
+    hook_mstep_full(c, n, m, l, w, lvsq, p_vl, assoc, cur, max_stdd, s_thresh, vp_out, s_out, err_out, removed_out);
 }
 
-// calc_vp_line_counts (vp_localisation.py:482-512) on its own: argmax VP per line, the outlier test against
-// calc_lvsq_single of that VP (:504) and lweight == 0 (:506), counts and weighted counts per VP.
 __global__ __launch_bounds__(EM_BOUND) void line_counts_kernel(int n, int m, const double* lp, const double* v,
                                                                  const double* s, const double* w, const double* lweight,
                                                                  double thresh, EmLayout L, double* ws, double* counts_out,
                                                                  double* counts_w_out, long long* assoc_out) {
-    VPK_SHARED_DECL;
-    EmCtx c;
-    c.N = n; c.lp = (cgdp)lp; c.wt_doubles = WT_DOUBLES;
-    c.prm.use_weights = 1;
-    c.prm.outlier_thresh = thresh;
-    bind_scratch(c, ws, L, false);
-    for (int k = tid(); k < n; k += nthreads()) c.lweight[k] = lweight[k];
-    for (int k = tid(); k < 3 * m; k += nthreads()) sh.cur[k] = v[k];
-    for (int k = tid(); k < m; k += nthreads()) sh.s[k] = s[k];
-    if (tid() == 0) { sh.M = m; sh.ncomp = 0; sh.sigma_prior = 1.0; }     // no prior: only lvsq is wanted from the E-step
-    block_sync();
-    line_geometry_setup(c);
-    estep(c, sh.cur);                                                     // lvsq[m][n] (probability_functions.py:157-176)
-    for (int p = tid(); p < m * n; p += nthreads()) c.w[(size_t)(p / n) * c.ldn + p % n] = w[p];
-    block_sync();
-    assign_lines(c, true);
-    count_lines(c);
-    for (int k = tid(); k < m; k += nthreads()) { counts_out[k] = sh.cnt[k]; counts_w_out[k] = sh.cntw[k]; }
-    for (int k = tid(); k < n; k += nthreads()) assoc_out[k] = c.assoc[k];
+    EmCtx c = kernel_ctx(WT_DOUBLES, 0, ws, L);
+    hook_line_counts(c, n, m, lp, v, s, w, lweight, thresh, counts_out, counts_w_out, assoc_out);
 }
 
 __global__ __launch_bounds__(EM_BOUND) void cluster2_kernel(int n, double* D, int* member, int* csize,
                                                               int* labels_out, unsigned* flags_out) {
-    VPK_SHARED_DECL;
-    if (tid() == 0) sh.flags = 0;
-    block_sync();
-    const int ld = n | 1;
-    if (n <= CLUSTER_LDS_MAX && cluster_lds_doubles(n) <= WT_DOUBLES) {   // same choice as split_vp
-        double* DL = WT();
-        for (int p = tid(); p < n * n; p += nthreads()) {
-            const int a = p / n, b = p % n;
-            const double v = D[p];
-            DL[a * ld + b] = (a == b || !(v + D[(size_t)b * n + a] != 0.0)) ? -1.0 : v;
-        }
-        block_sync();
-        cluster2_lds(n);
-        const int* lmember = cluster_lds_labels(DL, n);
-        for (int q = tid(); q < n; q += nthreads()) member[q] = lmember[q];
-        block_sync();
-    } else {
-        cluster2(sh, n, (gdp)D, (gip)member, (gip)csize);
-    }
-    for (int q = tid(); q < n; q += nthreads()) labels_out[q] = member[q];
-    if (tid() == 0) *flags_out = sh.flags;
+    hook_cluster2(n, D, member, csize, labels_out, flags_out);
 }
 
 template <typename K>
@@ -555,6 +386,21 @@ int em_prepare(vpk_handle* h) {
     if ((rc = allow_lds(h, cluster2_kernel))) return rc;
     if ((rc = allow_lds(h, line_counts_kernel))) return rc;
     h->em_ready = true;
+    return VPK_OK;
+}
+
+// What every fine-grained entry point does before its launch: the device, the kernels' LDS attribute and ws_bytes of
+// h->small_ws (0: none) ...
+int hook_begin(vpk_handle* h, size_t ws_bytes) {
+    VPK_HIP(h, hipSetDevice(h->device));
+    if (int rc = em_prepare(h)) return rc;
+    return ws_bytes ? vpk_reserve(h, &h->small_ws, &h->small_ws_bytes, ws_bytes, "hipMalloc(workspace)") : VPK_OK;
+}
+// ... and the launch itself: one workgroup on the handle's stream
+template <typename... P, typename... A>
+int hook_launch(vpk_handle* h, void (*kernel)(P...), size_t lds_bytes, A... args) {
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(EM_THREADS), lds_bytes, h->stream, args...);
+    VPK_HIP(h, hipGetLastError());
     return VPK_OK;
 }
 
@@ -640,6 +486,7 @@ int em_flush(vpk_handle* h) {
     return VPK_OK;
 }
 
+// the slot of a single-image call: m VPs, every array of the weighted EM, no split scratch
 EmLayout small_layout(int n, int m) {
     return em_layout(n, (int)em_align((size_t)(m > 0 ? m : 1), 8), EM_WAVES, true, false);
 }
@@ -857,15 +704,10 @@ int vpk_em_flush(vpk_handle* h) {
 int vpk_pairwise(vpk_handle* h, int n, const double* lp, double* lsim_out, double* lscore_out,
                  double* langle_out) {
     if (!h || n < 1 || !lp || !lsim_out || !lscore_out || !langle_out) return vpk_fail(h, VPK_ERR_ARG, "vpk_pairwise: bad argument");
-    VPK_HIP(h, hipSetDevice(h->device));
-    { int rc0 = em_prepare(h); if (rc0) return rc0; }
-    EmLayout L = small_layout(n, 8);
-    int rc = vpk_reserve(h, &h->small_ws, &h->small_ws_bytes, L.total_doubles * 8, "hipMalloc(workspace)");
-    if (rc) return rc;
-    hipLaunchKernelGGL(pairwise_kernel, dim3(1), dim3(EM_THREADS), EM_LDS_BYTES, h->stream, n, lp, L, (double*)h->small_ws,
-                       lsim_out, lscore_out, langle_out, h->em_smoother);
-    VPK_HIP(h, hipGetLastError());
-    return VPK_OK;
+    const EmLayout L = small_layout(n, 8);
+    if (int rc = hook_begin(h, L.total_doubles * 8)) return rc;
+    return hook_launch(h, pairwise_kernel, EM_LDS_BYTES, n, lp, L, (double*)h->small_ws, lsim_out, lscore_out, langle_out,
+                       h->em_smoother);
 }
 
 int vpk_init_vps(vpk_handle* h, const float* cnn, const uint8_t* sphere, int sphere_size, int num_max,
@@ -873,44 +715,30 @@ int vpk_init_vps(vpk_handle* h, const float* cnn, const uint8_t* sphere, int sph
     if (!h || !cnn || !sphere || !v0_out || !m0_out || !weights_out || num_max < 1 || num_max > MAXM ||
         sphere_size < GRIDN)
         return vpk_fail(h, VPK_ERR_ARG, "vpk_init_vps: bad argument");
-    VPK_HIP(h, hipSetDevice(h->device));
-    { int rc0 = em_prepare(h); if (rc0) return rc0; }
-    hipLaunchKernelGGL(init_vps_kernel, dim3(1), dim3(EM_THREADS), EM_LDS_BYTES, h->stream, cnn, sphere, sphere_size, num_max,
-                       v0_out, m0_out, weights_out);
-    VPK_HIP(h, hipGetLastError());
-    return VPK_OK;
+    if (int rc = hook_begin(h, 0)) return rc;
+    return hook_launch(h, init_vps_kernel, EM_LDS_BYTES, cnn, sphere, sphere_size, num_max, v0_out, (int*)m0_out, weights_out);
 }
 
 int vpk_estep(vpk_handle* h, int n, int m, const double* lp, const float* cnn, const double* v, double* s,
               double* p_v_out, double* lvsq_out, double* p_vl_out, double* p_l_out) {
     if (!h || n < 1 || m < 1 || m > MAXM || !lp || !cnn || !v || !s || !p_v_out || !lvsq_out || !p_vl_out || !p_l_out)
         return vpk_fail(h, VPK_ERR_ARG, "vpk_estep: bad argument");
-    VPK_HIP(h, hipSetDevice(h->device));
-    { int rc0 = em_prepare(h); if (rc0) return rc0; }
-    EmLayout L = small_layout(n, m);
-    int rc = vpk_reserve(h, &h->small_ws, &h->small_ws_bytes, L.total_doubles * 8, "hipMalloc(workspace)");
-    if (rc) return rc;
-    hipLaunchKernelGGL(estep_kernel, dim3(1), dim3(EM_THREADS), EM_LDS_BYTES, h->stream, n, m, lp, cnn, v, s, L,
-                       (double*)h->small_ws, p_v_out, lvsq_out, p_vl_out, p_l_out, h->em_smoother);
-    VPK_HIP(h, hipGetLastError());
-    return VPK_OK;
+    const EmLayout L = small_layout(n, m);
+    if (int rc = hook_begin(h, L.total_doubles * 8)) return rc;
+    return hook_launch(h, estep_kernel, EM_LDS_BYTES, n, m, lp, cnn, v, s, L, (double*)h->small_ws, p_v_out, lvsq_out,
+                       p_vl_out, p_l_out, h->em_smoother);
 }
 
 int vpk_weight_matrix(vpk_handle* h, int n, int m, const double* p_vl, const double* lweight,
                       const double* lsim, double bias, double* w_out) {
     if (!h || n < 1 || m < 1 || m > MAXM || !p_vl || !lweight || !lsim || !w_out)
         return vpk_fail(h, VPK_ERR_ARG, "vpk_weight_matrix: bad argument");
-    VPK_HIP(h, hipSetDevice(h->device));
-    { int rc0 = em_prepare(h); if (rc0) return rc0; }
-    EmLayout L = em_layout(n, (int)em_align((size_t)m, 8), EM_WAVES, true, false);
-    int rc = vpk_reserve(h, &h->small_ws, &h->small_ws_bytes, L.total_doubles * 8, "hipMalloc(workspace)");
-    if (rc) return rc;
+    const EmLayout L = small_layout(n, m);
+    if (int rc = hook_begin(h, L.total_doubles * 8)) return rc;
     // the batch kernel's LDS budget, so that this entry point takes the same smoother an image of this size takes there
     const EmMode mode = em_mode(h);
-    hipLaunchKernelGGL(weight_matrix_kernel, dim3(1), dim3(EM_THREADS), mode.lds_bytes, h->stream, n, m, p_vl, lweight, lsim,
-                       bias, L, (double*)h->small_ws, w_out, h->em_smoother, mode.wt_doubles);
-    VPK_HIP(h, hipGetLastError());
-    return VPK_OK;
+    return hook_launch(h, weight_matrix_kernel, mode.lds_bytes, n, m, p_vl, lweight, lsim, bias, L, (double*)h->small_ws,
+                       w_out, h->em_smoother, mode.wt_doubles);
 }
 
 int vpk_estep_smooth(vpk_handle* h, int n, int m, const double* lp, const float* cnn, const double* v, double* s,
@@ -918,31 +746,20 @@ int vpk_estep_smooth(vpk_handle* h, int n, int m, const double* lp, const float*
                      int32_t* info_out) {
     if (!h || n < 1 || m < 1 || m > MAXM || !lp || !cnn || !v || !s || !lweight || !lsim || !p_vl_out || !w_out || !info_out)
         return vpk_fail(h, VPK_ERR_ARG, "vpk_estep_smooth: bad argument");
-    VPK_HIP(h, hipSetDevice(h->device));
-    { int rc0 = em_prepare(h); if (rc0) return rc0; }
-    EmLayout L = small_layout(n, m);
-    int rc = vpk_reserve(h, &h->small_ws, &h->small_ws_bytes, L.total_doubles * 8, "hipMalloc(workspace)");
-    if (rc) return rc;
+    const EmLayout L = small_layout(n, m);
+    if (int rc = hook_begin(h, L.total_doubles * 8)) return rc;
     // the batch kernel's LDS budget (as vpk_weight_matrix): the E-step plans the panel and the smoother takes it as they do there
     const EmMode mode = em_mode(h);
-    hipLaunchKernelGGL(estep_smooth_kernel, dim3(1), dim3(EM_THREADS), mode.lds_bytes, h->stream, n, m, lp, cnn, v, s, lweight,
-                       lsim, bias, L, (double*)h->small_ws, p_vl_out, w_out, (int*)info_out, h->em_smoother, mode.wt_doubles);
-    VPK_HIP(h, hipGetLastError());
-    return VPK_OK;
+    return hook_launch(h, estep_smooth_kernel, mode.lds_bytes, n, m, lp, cnn, v, s, lweight, lsim, bias, L,
+                       (double*)h->small_ws, p_vl_out, w_out, (int*)info_out, h->em_smoother, mode.wt_doubles);
 }
 
 int vpk_mstep(vpk_handle* h, int n, int m, const double* l, const double* w, double* vp_out, int32_t* valid_out) {
     if (!h || n < 1 || m < 1 || m > MAXM || !l || !w || !vp_out || !valid_out)
         return vpk_fail(h, VPK_ERR_ARG, "vpk_mstep: bad argument");
-    VPK_HIP(h, hipSetDevice(h->device));
-    { int rc0 = em_prepare(h); if (rc0) return rc0; }
-    EmLayout L = em_layout(n, (int)em_align((size_t)m, 8), EM_WAVES, false, false);
-    int rc = vpk_reserve(h, &h->small_ws, &h->small_ws_bytes, L.total_doubles * 8, "hipMalloc(workspace)");
-    if (rc) return rc;
-    hipLaunchKernelGGL(mstep_kernel, dim3(1), dim3(EM_THREADS), EM_LDS_BYTES, h->stream, n, m, l, w, L, (double*)h->small_ws,
-                       vp_out, valid_out);
-    VPK_HIP(h, hipGetLastError());
-    return VPK_OK;
+    const EmLayout L = em_layout(n, (int)em_align((size_t)m, 8), EM_WAVES, false, false);
+    if (int rc = hook_begin(h, L.total_doubles * 8)) return rc;
+    return hook_launch(h, mstep_kernel, EM_LDS_BYTES, n, m, l, w, L, (double*)h->small_ws, vp_out, (int*)valid_out);
 }
 
 int vpk_mstep_full(vpk_handle* h, int n, int m, const double* l, const double* w, const double* lvsq, const double* p_vl,
@@ -950,46 +767,29 @@ int vpk_mstep_full(vpk_handle* h, int n, int m, const double* l, const double* w
                    double* s_out, double* err_out, int32_t* removed_out) {
     if (!h || n < 1 || m < 1 || m > MAXM || !l || !w || !lvsq || !p_vl || !cur || !vp_out || !s_out || !err_out || !removed_out)
         return vpk_fail(h, VPK_ERR_ARG, "vpk_mstep_full: bad argument");
-    VPK_HIP(h, hipSetDevice(h->device));
-    { int rc0 = em_prepare(h); if (rc0) return rc0; }
-    EmLayout L = em_layout(n, (int)em_align((size_t)m, 8), EM_WAVES, false, false);
-    int rc = vpk_reserve(h, &h->small_ws, &h->small_ws_bytes, L.total_doubles * 8, "hipMalloc(workspace)");
-    if (rc) return rc;
-    hipLaunchKernelGGL(mstep_full_kernel, dim3(1), dim3(EM_THREADS), EM_LDS_BYTES, h->stream, n, m, l, w, lvsq, p_vl, assoc,
-                       cur, max_stdd, s_thresh, L, (double*)h->small_ws, vp_out, s_out, err_out, removed_out, h->em_smoother);
-    VPK_HIP(h, hipGetLastError());
-    return VPK_OK;
+    const EmLayout L = em_layout(n, (int)em_align((size_t)m, 8), EM_WAVES, false, false);
+    if (int rc = hook_begin(h, L.total_doubles * 8)) return rc;
+    return hook_launch(h, mstep_full_kernel, EM_LDS_BYTES, n, m, l, w, lvsq, p_vl, (const int*)assoc, cur, max_stdd, s_thresh,
+                       L, (double*)h->small_ws, vp_out, s_out, err_out, (int*)removed_out, h->em_smoother);
 }
 
 int vpk_line_counts(vpk_handle* h, int n, int m, const double* lp, const double* v, const double* s, const double* w,
                     const double* lweight, double thresh, double* counts_out, double* counts_w_out, int64_t* assoc_out) {
     if (!h || n < 1 || m < 1 || m > MAXM || !lp || !v || !s || !w || !lweight || !counts_out || !counts_w_out || !assoc_out)
         return vpk_fail(h, VPK_ERR_ARG, "vpk_line_counts: bad argument");
-    VPK_HIP(h, hipSetDevice(h->device));
-    { int rc0 = em_prepare(h); if (rc0) return rc0; }
-    EmLayout L = small_layout(n, m);
-    int rc = vpk_reserve(h, &h->small_ws, &h->small_ws_bytes, L.total_doubles * 8, "hipMalloc(workspace)");
-    if (rc) return rc;
-    hipLaunchKernelGGL(line_counts_kernel, dim3(1), dim3(EM_THREADS), EM_LDS_BYTES, h->stream, n, m, lp, v, s, w, lweight,
-                       thresh, L, (double*)h->small_ws, counts_out, counts_w_out, (long long*)assoc_out);
-    VPK_HIP(h, hipGetLastError());
-    return VPK_OK;
+    const EmLayout L = small_layout(n, m);
+    if (int rc = hook_begin(h, L.total_doubles * 8)) return rc;
+    return hook_launch(h, line_counts_kernel, EM_LDS_BYTES, n, m, lp, v, s, w, lweight, thresh, L, (double*)h->small_ws,
+                       counts_out, counts_w_out, (long long*)assoc_out);
 }
 
 int vpk_cluster2(vpk_handle* h, int n, const double* ldist, int32_t* labels_out, uint32_t* flags_out) {
     if (!h || n < 3 || !ldist || !labels_out || !flags_out) return vpk_fail(h, VPK_ERR_ARG, "vpk_cluster2: bad argument");
-    VPK_HIP(h, hipSetDevice(h->device));
-    { int rc0 = em_prepare(h); if (rc0) return rc0; }
-    size_t need = (size_t)n * n * 8 + (size_t)2 * n * 4 + 64;
-    int rc = vpk_reserve(h, &h->small_ws, &h->small_ws_bytes, need, "hipMalloc(workspace)");
-    if (rc) return rc;
+    if (int rc = hook_begin(h, (size_t)n * n * 8 + (size_t)2 * n * 4 + 64)) return rc;
     double* D = (double*)h->small_ws;
     int* member = (int*)(D + (size_t)n * n);
     VPK_HIP(h, hipMemcpyAsync(D, ldist, (size_t)n * n * 8, hipMemcpyDeviceToDevice, h->stream));
-    hipLaunchKernelGGL(cluster2_kernel, dim3(1), dim3(EM_THREADS), EM_LDS_BYTES, h->stream, n, D, member, member + n,
-                       labels_out, flags_out);
-    VPK_HIP(h, hipGetLastError());
-    return VPK_OK;
+    return hook_launch(h, cluster2_kernel, EM_LDS_BYTES, n, D, member, member + n, (int*)labels_out, (unsigned*)flags_out);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // vpset_device.hpp -- VP set maintenance outside the EM: calc_vp_line_counts (vp_localisation.py:482-512),
 // split_best_vp (:527-630) and merge_vps (:633-684) on a caller-supplied VP set, one workgroup per image.  The phases are
-// the EM workgroup's own device functions (em_device.hpp: count_lines, split_vp with cluster2 / cluster2_lds, merge_vps
-// with estep, smooth, wave_null_vector and compact_vps); this header
+// the EM workgroup's own device functions (em_assign.hpp: count_lines, compact_vps; em_vpset.hpp: split_vp with cluster2 /
+// cluster2_lds, merge_vps with em_estep.hpp's estep, em_smooth.hpp's smooth and em_linalg.hpp's wave_null_vector); this header
 // binds an EmCtx and the Shared block to the caller's arrays instead of running the EM's set-up, and adds the one step
 // the EM never needs: the association from a caller's vp_assoc (:486, :494) tested against the caller's own s.
 #ifndef VPK_VPSET_DEVICE_HPP_
