@@ -645,6 +645,49 @@ int vpk_estep_batch(vpk_handle* h, int batch, const int64_t* line_offsets, const
                     const double* l, const double* v, const double* s, const double* p_v, int measure,
                     double* s_floored_out, double* lvsq_out, double* p_lv_out, double* p_l_out, double* p_vl_out);
 
+/* ---- the EM update outside the EM (batched; asynchronous on the handle's stream) -------------------------- */
+/* The batched forms of vpk_weight_matrix, vpk_mstep / vpk_mstep_full and vpk_init_vps: one workgroup per image through the
+ * same device functions, bit for bit what the single-image entries give image by image.  Conventions as for the VP set
+ * entries above: host int64[batch + 1] offsets (not decreasing, the first not below 0), device pointers otherwise, image
+ * b's [m][n] matrices (row stride N_b) at element sum_{a < b} M_a N_a.  M_b <= 64 and N_b <= 32768, else VPK_ERR_LIMIT
+ * before anything is launched.  batch = 0 does nothing; an image with N_b = 0 or M_b = 0 gets no work and none of its
+ * outputs is written.  batch < 0, malformed offsets and a null buffer the call would read or write: VPK_ERR_ARG.  No error
+ * case touches an output.
+ * The grid is min(images with work, cap) workgroups -- cap: vpk_em_set_workgroups when set, else a small multiple of the
+ * CU count -- each with ONE workspace slot sized for the batch's largest image; workgroup q takes the images q, q + grid,
+ * ... of a largest-first order.  A workspace beyond half of the device memory: VPK_ERR_LIMIT. */
+/* replaces: weight_matrix -- vp_localisation.py:515-524 -- for a batch.
+ *   p_vl [m][n] per image, lweight sum(N), lsim / lsim_offsets as vpk_vp_merge_batch takes them (plain N_b x N_b matrices,
+ *   at least N_b^2 apart: what vpk_line_similarity_batch writes), w_out [m][n] per image.
+ * Launched with the LDS budget of vpk_em_batch: vpk_em_set_lds_panel and vpk_em_set_smoother steer it as they steer
+ * vpk_weight_matrix. */
+int vpk_weight_matrix_batch(vpk_handle* h, int batch, const int64_t* line_offsets, const int64_t* vp_offsets,
+                            const double* p_vl, const double* lweight, const int64_t* lsim_offsets, const double* lsim,
+                            double bias, double* w_out);
+/* replaces: calc_new_vanishing_point -- vp_localisation.py:453-479 -- and the variance / error / removal step around it
+ * (:284-322 soft, :353-392 hard, with the row normalisation of :358) for a batch.
+ *   l sum(N) x 3 (normalised lines), w [m][n] per image
+ *   lvsq, p_vl   [m][n] per image; both given or both NULL
+ *     both NULL: vpk_mstep -- positions only, from unit state.  s_out, err_out and max_err_out must be NULL; cur and assoc
+ *                are not read.
+ *     both given: vpk_mstep_full.  assoc NULL = soft; assoc sum(N) int64 (what vpk_vp_line_counts_batch writes) = hard:
+ *                entries outside [0, M_b) -- the -1 of an outlier -- select no VP.  cur sum(M) x 3: the VPs of the previous
+ *                iteration.  Rows the M-step does not write come back as vp = 0, s = -1, err = -1.
+ *   vp_out sum(M) x 3, s_out / err_out sum(M)
+ *   removed_out  NULL or sum(M) int32: 1 where the reference appends m to to_be_removed
+ *   valid_out    NULL or sum(M) int32: 1 where a new VP was written
+ *   max_err_out  NULL or batch fp64: the np.maximum chain from 0 over the image's errors (:275, :313; a NaN sticks) */
+int vpk_mstep_batch(vpk_handle* h, int batch, const int64_t* line_offsets, const int64_t* vp_offsets, const double* l,
+                    const double* w, const double* lvsq, const double* p_vl, const int64_t* assoc, const double* cur,
+                    double max_stdd, double s_thresh, double* vp_out, double* s_out, double* err_out, int32_t* removed_out,
+                    int32_t* valid_out, double* max_err_out);
+/* replaces: find_initial_vps -- vp_localisation.py:111-165 -- for a batch.
+ *   cnn batch x 400 fp32, sphere batch x S x S uint8 (S = sphere_size >= 20), num_max 1..64 (else VPK_ERR_ARG)
+ *   v0_out batch x num_max x 3: rows past m0_out[b] are zeros; m0_out batch int32: 0 where the reference raises at :165
+ *   weights_out  NULL or batch x 400 fp32: the pdf_params weights, as vpk_init_vps returns them */
+int vpk_init_vps_batch(vpk_handle* h, int batch, const float* cnn, const uint8_t* sphere, int sphere_size, int num_max,
+                       double* v0_out, int32_t* m0_out, float* weights_out);
+
 /* ---- result overlays (batched; asynchronous on the handle's stream) ---------------------------------------- */
 /* Both entries blend primitives into 8-bit RGB images in place, by the renderer of DESIGN section 7d: a primitive of width
  * w covers the points within w / 2 of its closed segment (a capsule; a disc when the segment has no length), coverage of

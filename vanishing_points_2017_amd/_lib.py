@@ -74,6 +74,7 @@ EXPORTS = [
     "vpk_overlay_lines_batch", "vpk_overlay_markers_batch",
     "vpk_vp_line_counts_batch", "vpk_vp_split_batch", "vpk_vp_merge_batch",
     "vpk_estep_batch",
+    "vpk_weight_matrix_batch", "vpk_mstep_batch", "vpk_init_vps_batch",
 ]
 
 _lib = None
@@ -171,6 +172,9 @@ def load():
     lib.vpk_vp_merge_batch.argtypes = [c_void, ctypes.c_int] + [c_void] * 9 + [ctypes.c_double, c_void] + \
                                       [ctypes.c_double] * 3 + [c_void] * 5
     lib.vpk_estep_batch.argtypes = [c_void, ctypes.c_int] + [c_void] * 7 + [ctypes.c_int] + [c_void] * 5
+    lib.vpk_weight_matrix_batch.argtypes = [c_void, ctypes.c_int] + [c_void] * 6 + [ctypes.c_double, c_void]
+    lib.vpk_mstep_batch.argtypes = [c_void, ctypes.c_int] + [c_void] * 8 + [ctypes.c_double] * 2 + [c_void] * 6
+    lib.vpk_init_vps_batch.argtypes = [c_void, ctypes.c_int, c_void, c_void, ctypes.c_int, ctypes.c_int] + [c_void] * 3
     _lib = lib
     return lib
 

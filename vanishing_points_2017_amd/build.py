@@ -25,6 +25,7 @@ UNITS = {
     "vpk_overlay.hip": ["-ffp-contract=off"],  # the capsule distance is line_device.hpp's too (overlay_device.hpp)
     "vpk_vpset.hip": ["-ffp-contract=off"],    # the EM's own phase functions on a caller's VP set (vpset_device.hpp)
     "vpk_estep.hip": ["-ffp-contract=off"],    # the "angle" measure restates the EM unit's per-pair expression (estep_device.hpp)
+    "vpk_emstep.hip": ["-ffp-contract=off"],   # the bodies of the EM's fine-grained entry points for a batch (emstep_device.hpp)
     "vpk_cnn.hip": [],
     "vpk_raster.hip": ["-ffp-contract=off"],   # the curve samples must round like NumPy's separate ufunc calls
     "vpk_horizon.hip": ["-ffp-contract=off"],

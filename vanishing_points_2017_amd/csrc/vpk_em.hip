@@ -493,6 +493,12 @@ EmLayout small_layout(int n, int m) {
 
 }  // namespace
 
+// em_mode for the other units that launch the smoother (vpk_emstep.hip)
+vpk_em_lds vpk_em_lds_mode(const vpk_handle* h) {
+    const EmMode m = em_mode(h);
+    return vpk_em_lds{m.wt_doubles, m.lds_bytes, EM_LDS_BYTES_BIG};
+}
+
 namespace {
 // vpk_math_probe: the elementary functions exactly as this translation unit's kernels get them (same compiler flags, same
 // ocml entry points as em_device.hpp's calls), one argument per thread.

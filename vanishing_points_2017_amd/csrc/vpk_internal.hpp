@@ -104,7 +104,16 @@ struct vpk_handle {
     size_t vpset_ws_bytes = 0;
     bool vpset_ready = false;        // dynamic-LDS attribute set on the kernel
     vpk_staged estep_hdr;            // vpk_estep_batch (vpk_estep.hip): offsets of lines, VPs, matrices and workgroups
+    vpk_staged emstep_hdr;           // vpk_weight_matrix_batch / vpk_mstep_batch (vpk_emstep.hip): the image records
+    void* emstep_ws = nullptr;       // one slot per workgroup (grown on demand)
+    size_t emstep_ws_bytes = 0;
+    bool emstep_ready = false;       // dynamic-LDS attribute set on the kernel
 };
+
+// the LDS budget vpk_em_batch launches with under the handle's vpk_em_set_lds_panel setting (vpk_em.hip: em_mode): the
+// panel the phases plan with, the launch's dynamic LDS, and the most any setting asks for
+struct vpk_em_lds { int wt_doubles; size_t lds_bytes; size_t lds_bytes_max; };
+vpk_em_lds vpk_em_lds_mode(const vpk_handle* h);
 
 int vpk_fail(vpk_handle* h, int code, const char* what);
 int vpk_fail_hip(vpk_handle* h, hipError_t e, const char* what);

@@ -12,6 +12,13 @@ functions with sigma = 1 and k2 = 4 (:178, :230); the defaults here are the refe
 Thin mirrors of entry points the EM's unit tests already use: find_initial_vps (:111-165, vpk_init_vps), weight_matrix
 (:515-524, vpk_weight_matrix) and calc_new_vanishing_point (:453-479, vpk_mstep).
 
+The EM update for a batch (vpk_init_vps_batch, vpk_weight_matrix_batch, vpk_mstep_batch; include/vpk.h):
+find_initial_vps_batch, weight_matrix_batch, calc_new_vanishing_point_batch and mstep_batch -- the M-step with the variance,
+error and removal step around it (:284-322 soft, :353-392 hard) -- take many images per launch, return device tensors and
+give, image by image, the bits of the single-image entry points.  With the prior, the E-step and the VP set functions a
+whole EM iteration is composed of device-resident calls (mstep_batch's docstring), under any of the E-step's distance
+measures.
+
 VP set maintenance (vpk_vp_line_counts_batch, vpk_vp_split_batch, vpk_vp_merge_batch; include/vpk.h): calc_vp_line_counts
 (:482-512), split_best_vp (:527-630) and merge_vps (:633-684) on a VP set of the caller's, through the EM workgroup's own
 device functions; calc_angle_to_other_vp (:687-697) on the host.  The ``*_batch`` forms take many images per launch and
@@ -254,7 +261,7 @@ def _cat(rt, x, dtype, tail=()):
         if len(x) and isinstance(x[0], t.Tensor):
             x = t.cat([a.to(device=rt.tdev, dtype=dtype).reshape((-1,) + tail) for a in x])
         else:
-            npd = {t.float64: np.float64, t.float32: np.float32, t.int64: np.int64}[dtype]
+            npd = {t.float64: np.float64, t.float32: np.float32, t.int64: np.int64, t.uint8: np.uint8}[dtype]
             arrs = [np.ascontiguousarray(a, dtype=npd).reshape((-1,) + tail) for a in x]
             x = np.concatenate(arrs) if arrs else np.zeros((0,) + tail, dtype=npd)
     if not isinstance(x, t.Tensor):
@@ -528,6 +535,238 @@ def merge_vps(i, v, s, l, thresh, lweight, lsim, wbias, pdfpar, lp, llen, distan
     v2 = v[:, kept, :].copy()
     v2[i] = r['v'].cpu().numpy()[:m]
     return {'v': v2, 's': r['s'].cpu().numpy()[:m]}
+
+
+# ---- the EM update outside the EM: weights, M-step and initial VPs for a batch ----------------------------------------------
+MAX_LINES = 32768                       # per image (csrc/vpk_emstep.hip)
+
+
+def _numel(a):
+    return int(a.numel()) if hasattr(a, "numel") else int(np.asarray(a).size)
+
+
+def _shape(a):
+    return tuple(a.shape) if hasattr(a, "shape") else np.asarray(a).shape
+
+
+def _check_counts(lo, vo, what_l, what_v):
+    if lo.shape != vo.shape:
+        raise ValueError("%s and %s describe %d and %d images" % (what_l, what_v, lo.shape[0] - 1, vo.shape[0] - 1))
+    _check_vp_limit(vo)
+    n = np.diff(lo)
+    if n.size and n.max() > MAX_LINES:
+        raise ValueError("%d lines in one image: at most %d are supported" % (n.max(), MAX_LINES))
+
+
+def _check_rows(x, off, width, what):
+    """``x`` holds off[-1] rows of ``width`` elements (lists: image b off[b + 1] - off[b] of them); host only."""
+    if isinstance(x, (list, tuple)):
+        if len(x) != off.shape[0] - 1:
+            raise ValueError("%s holds %d images, expected %d" % (what, len(x), off.shape[0] - 1))
+        for b, a in enumerate(x):
+            if _numel(a) != int(off[b + 1] - off[b]) * width:
+                raise ValueError("%s[%d] holds %d elements, expected %d" % (what, b, _numel(a), int(off[b + 1] - off[b]) * width))
+    elif _numel(x) != int(off[-1]) * width:
+        raise ValueError("%s holds %d elements, expected %d" % (what, _numel(x), int(off[-1]) * width))
+
+
+def _check_mats(x, lo, vo, what, transposed=False):
+    """``x`` holds the images' M_b x N_b matrices: a list of (M_b, N_b) -- ``transposed``: (N_b, M_b) -- arrays or tensors,
+    or the [m][n] matrices concatenated flat, image after image; host only."""
+    n, m = np.diff(lo), np.diff(vo)
+    if isinstance(x, (list, tuple)):
+        if len(x) != n.shape[0]:
+            raise ValueError("%s holds %d images, expected %d" % (what, len(x), n.shape[0]))
+        for b, a in enumerate(x):
+            want = (int(n[b]), int(m[b])) if transposed else (int(m[b]), int(n[b]))
+            if _shape(a) != want and not (_numel(a) == 0 and want[0] * want[1] == 0):
+                raise ValueError("%s[%d] has shape %r, expected %r" % (what, b, _shape(a), want))
+    elif _numel(x) != int((n * m).sum()):
+        raise ValueError("%s holds %d elements, the images' M x N sum to %d" % (what, _numel(x), int((n * m).sum())))
+
+
+def _cat_mats(rt, x, transposed=False):
+    if transposed and isinstance(x, (list, tuple)):
+        x = [a.T if hasattr(a, "data_ptr") else np.asarray(a).T for a in x]      # back to [m][n]: free for a transposed view
+    return _cat(rt, x, rt.torch.float64)
+
+
+def _vp_sizes_of_mats(mats, vp_offsets, what):
+    """VP offsets from a list of (M_b, N_b) matrices, or the caller's for the flat form."""
+    if isinstance(mats, (list, tuple)):
+        for a in mats:
+            if len(_shape(a)) != 2:
+                raise ValueError("%s: every image's matrix must be two-dimensional (M_b, N_b)" % what)
+        return _offsets_of([_shape(a)[0] for a in mats])
+    if vp_offsets is None:
+        raise ValueError("%s is one concatenated array: vp_offsets is needed" % what)
+    vo = host_i64(vp_offsets)
+    if vo.ndim != 1 or vo.shape[0] < 1 or vo[0] != 0 or (np.diff(vo) < 0).any():
+        raise ValueError("vp_offsets must rise from 0")
+    return vo
+
+
+def _split_mn(buf, lo, vo):
+    n, m = np.diff(lo), np.diff(vo)
+    at = np.concatenate(([0], np.cumsum(n * m)))
+    return [buf[int(at[b]):int(at[b + 1])].view(int(m[b]), int(n[b])) for b in range(n.shape[0])]
+
+
+def find_initial_vps_batch(sphere_images, cnn_responses, num_max, device=0, want_weights=False):
+    """find_initial_vps for many images in one launch (vpk_init_vps_batch).  ``sphere_images``: (B, S, S) uint8, S >= 20,
+    or a list of (S, S) images of one size; ``cnn_responses``: (B, 20, 20) float32 or a list.  Returns (v0 (B, num_max, 3)
+    float64, num_vp (B,) int32) as device tensors: image b's VPs are v0[b, :num_vp[b]], the rows past them zeros, and
+    num_vp[b] = 0 where the reference raises at :165.  ``want_weights``: a third tensor, the (B, 400) float32 pdf_params
+    weights."""
+    num_max = int(num_max)
+    if num_max < 1 or num_max > MAX_VP:
+        raise ValueError("num_max = %d: 1 to %d initial VPs are supported" % (num_max, MAX_VP))
+    if isinstance(sphere_images, (list, tuple)):
+        sph = [_shape(a) for a in sphere_images]
+    else:
+        if len(_shape(sphere_images)) != 3:
+            raise ValueError("sphere_images must be (B, S, S) or a list of (S, S) images")
+        sph = [_shape(sphere_images)[1:]] * _shape(sphere_images)[0]
+    B = len(sph)
+    if any(len(s) != 2 or s[0] != s[1] or s != sph[0] for s in sph):
+        raise ValueError("the sphere images must be square and of one size")
+    if B and sph[0][0] < 20:
+        raise ValueError("sphere images of %d pixels: at least 20 are needed" % sph[0][0])
+    nc = len(cnn_responses) if isinstance(cnn_responses, (list, tuple)) else (_shape(cnn_responses)[0] if len(_shape(cnn_responses)) else -1)
+    if nc != B:
+        raise ValueError("sphere_images and cnn_responses describe %d and %d images" % (B, nc))
+    if isinstance(cnn_responses, (list, tuple)):
+        if any(_numel(a) != 400 for a in cnn_responses):
+            raise ValueError("every response map must hold 20 x 20 values")
+    elif _numel(cnn_responses) != 400 * B:
+        raise ValueError("cnn_responses must hold 20 x 20 values per image")
+    S = sph[0][0] if B else 20
+    rt = _runtime(device)
+    t = rt.torch
+    with rt.on_stream():
+        d_cnn = _cat(rt, cnn_responses, t.float32, (400,))
+        d_sp = _cat(rt, sphere_images, t.uint8, (S, S))
+        v0 = t.zeros((B, num_max, 3), dtype=t.float64, device=rt.tdev)
+        m0 = t.zeros((B,), dtype=t.int32, device=rt.tdev)
+        wts = t.zeros((B, 400), dtype=t.float32, device=rt.tdev) if want_weights else None
+        rt.check(rt.lib.vpk_init_vps_batch(rt.h, B, rt.ptr(d_cnn), rt.ptr(d_sp), S, num_max, rt.ptr(v0), rt.ptr(m0), rt.ptr(wts)))
+    rt.synchronize()
+    return (v0, m0, wts) if want_weights else (v0, m0)
+
+
+def weight_matrix_batch(p_vls, lweights, lsims, bias=0.001, line_offsets=None, vp_offsets=None, device=0):
+    """weight_matrix for many images in one launch (vpk_weight_matrix_batch).  ``p_vls``: a list of (M_b, N_b) arrays or
+    tensors, or the matrices concatenated flat with ``line_offsets`` / ``vp_offsets``; ``lweights``: (N_b,) each or
+    concatenated; ``lsims`` as in merge_vps_batch -- the list calc_lsim_batch returns is used where it lies.  ``bias``
+    defaults to the reference's own 0.001; the EM calls weight_matrix with wbias (1).  Returns a list of (M_b, N_b) float64
+    device tensors, views of one buffer in which the matrices follow each other without gaps."""
+    lo = _sizes(lweights, line_offsets, "lweights")
+    vo = _vp_sizes_of_mats(p_vls, vp_offsets, "p_vls")
+    _check_counts(lo, vo, "lweights", "p_vls")
+    _check_mats(p_vls, lo, vo, "p_vls")
+    n = np.diff(lo)
+    if isinstance(lsims, (list, tuple)):
+        if len(lsims) != n.shape[0] or any(_numel(a) != int(k) * int(k) for a, k in zip(lsims, n)):
+            raise ValueError("lsims must hold one N x N matrix per image")
+    elif _numel(lsims) != int((n * n).sum()):
+        raise ValueError("lsims must hold one N x N matrix per image")
+    B = lo.shape[0] - 1
+    rt = _runtime(device)
+    t = rt.torch
+    with rt.on_stream():
+        d_p = _cat_mats(rt, p_vls)
+        d_lw = _cat(rt, lweights, t.float64)
+        (lsim_ptr, lsim_keep), lsim_off = _lsim_layout(rt, lsims, n)
+        w = t.zeros((int((n * np.diff(vo)).sum()),), dtype=t.float64, device=rt.tdev)
+        import ctypes
+        rt.check(rt.lib.vpk_weight_matrix_batch(rt.h, B, _off_ptr(lo), _off_ptr(vo), rt.ptr(d_p), rt.ptr(d_lw), _off_ptr(lsim_off),
+                                                ctypes.c_void_p(lsim_ptr), float(bias), rt.ptr(w)))
+    rt.synchronize()
+    del lsim_keep
+    return _split_mn(w, lo, vo)
+
+
+def calc_new_vanishing_point_batch(ls, ws, line_offsets=None, vp_offsets=None, device=0):
+    """calc_new_vanishing_point for every row of many images' weight matrices in one launch (vpk_mstep_batch without
+    state).  ``ls``: (N_b, 3) normalised lines each, ``ws``: (M_b, N_b) each -- or concatenated with the offsets.  Returns
+    (vp (sum M, 3) float64, valid (sum M,) int32) as device tensors: vp is zero and valid 0 where the reference returns None."""
+    lo = _sizes(ls, line_offsets, "ls")
+    vo = _vp_sizes_of_mats(ws, vp_offsets, "ws")
+    _check_counts(lo, vo, "ls", "ws")
+    _check_rows(ls, lo, 3, "ls")
+    _check_mats(ws, lo, vo, "ws")
+    rt = _runtime(device)
+    t = rt.torch
+    with rt.on_stream():
+        d_l = _cat(rt, ls, t.float64, (3,))
+        d_w = _cat_mats(rt, ws)
+        vp = t.zeros((int(vo[-1]), 3), dtype=t.float64, device=rt.tdev)
+        valid = t.zeros((int(vo[-1]),), dtype=t.int32, device=rt.tdev)
+        rt.check(rt.lib.vpk_mstep_batch(rt.h, lo.shape[0] - 1, _off_ptr(lo), _off_ptr(vo), rt.ptr(d_l), rt.ptr(d_w), None, None,
+                                        None, None, 1e-6, 1e-200, rt.ptr(vp), None, None, None, rt.ptr(valid), None))
+    rt.synchronize()
+    return vp, valid
+
+
+def mstep_batch(ls, ws, lvsqs, p_vls, curs, assocs=None, max_stdd=1e-6, s_thresh=1e-200, line_offsets=None, vp_offsets=None,
+                device=0):
+    """The M-step of one EM iteration (:284-322; with ``assocs`` the hard one, :353-392) for many images in one launch
+    (vpk_mstep_batch).  Per image: ``ls`` (N_b, 3) normalised lines, ``ws`` (M_b, N_b) the decision metric, ``lvsqs``
+    (N_b, M_b) and ``p_vls`` (M_b, N_b) -- the shapes of the reference's PDF.lvsq and PDF.vl, so the tuples of
+    calc_probabilities_batch pass on unchanged --, ``curs`` (M_b, 3) the VPs of the previous iteration, ``assocs`` (N_b,)
+    int64 as calc_vp_line_counts_batch returns it (-1 selects no VP).  Lists, or concatenated with ``line_offsets`` /
+    ``vp_offsets`` (matrices then flat as [m][n], image after image).  Returns a dict of device tensors: 'v' (sum M, 3), 's'
+    and 'err' (sum M,), 'removed' and 'valid' (sum M,) int32, 'max_err' (B,) -- rows the M-step does not write are v = 0,
+    s = -1, err = -1; max_err of an image without lines or VPs is 0 -- and the host 'line_offsets', 'vp_offsets'.
+
+    One iteration that stays on the device (lps, ls: lists of per-image device tensors; off: the host offsets):
+
+        pair = (torch.cat(lps), off)
+        lsims = calc_lsim_batch(pair, sigma=1)
+        lscore, langle, llen, off = line_geometry_batch(pair, k1=10, k2=4)
+        lw = llen * lscore.clamp(0.2, 1)
+        v0, num = find_initial_vps_batch(spheres, maps, 25)
+        vs = [v0[b, :k] for b, k in enumerate(num.tolist())]              # (B counts: the one host copy)
+        e = calc_probabilities_batch(maps, vs, ls, lps, [v.new_full((len(v),), 1.2e-7) for v in vs])
+        w = weight_matrix_batch([p.vl for p in e['pdf']], lw, lsims, bias=1, line_offsets=off)
+        r = mstep_batch(ls, w, [p.lvsq for p in e['pdf']], [p.vl for p in e['pdf']], vs)
+        counts, counts_w, assoc, _, _ = calc_vp_line_counts_batch(r['v'], pair[0], r['s'], w, lw, line_offsets=off,
+                                                                  vp_offsets=r['vp_offsets'])"""
+    if (lvsqs is None) != (p_vls is None):
+        raise ValueError("lvsqs and p_vls are given together (calc_new_vanishing_point_batch takes neither)")
+    if lvsqs is None:
+        raise ValueError("mstep_batch needs lvsqs and p_vls: calc_new_vanishing_point_batch gives the positions alone")
+    lo = _sizes(ls, line_offsets, "ls")
+    vo = _sizes(curs, vp_offsets, "curs")
+    _check_counts(lo, vo, "ls", "curs")
+    _check_rows(ls, lo, 3, "ls")
+    _check_rows(curs, vo, 3, "curs")
+    _check_mats(ws, lo, vo, "ws")
+    _check_mats(lvsqs, lo, vo, "lvsqs", transposed=True)
+    _check_mats(p_vls, lo, vo, "p_vls")
+    if assocs is not None:
+        _check_rows(assocs, lo, 1, "assocs")
+    B = lo.shape[0] - 1
+    rt = _runtime(device)
+    t = rt.torch
+    with rt.on_stream():
+        d_l = _cat(rt, ls, t.float64, (3,))
+        d_cur = _cat(rt, curs, t.float64, (3,))
+        d_w, d_lv, d_p = _cat_mats(rt, ws), _cat_mats(rt, lvsqs, transposed=True), _cat_mats(rt, p_vls)
+        d_a = _cat(rt, assocs, t.int64) if assocs is not None else None
+        M = int(vo[-1])
+        vp = t.zeros((M, 3), dtype=t.float64, device=rt.tdev)
+        s = t.full((M,), -1.0, dtype=t.float64, device=rt.tdev)
+        err = t.full((M,), -1.0, dtype=t.float64, device=rt.tdev)
+        removed = t.zeros((M,), dtype=t.int32, device=rt.tdev)
+        valid = t.zeros((M,), dtype=t.int32, device=rt.tdev)
+        max_err = t.zeros((B,), dtype=t.float64, device=rt.tdev)
+        rt.check(rt.lib.vpk_mstep_batch(rt.h, B, _off_ptr(lo), _off_ptr(vo), rt.ptr(d_l), rt.ptr(d_w), rt.ptr(d_lv), rt.ptr(d_p),
+                                        rt.ptr(d_a), rt.ptr(d_cur), float(max_stdd), float(s_thresh), rt.ptr(vp), rt.ptr(s),
+                                        rt.ptr(err), rt.ptr(removed), rt.ptr(valid), rt.ptr(max_err)))
+    rt.synchronize()
+    return {'v': vp, 's': s, 'err': err, 'removed': removed, 'valid': valid, 'max_err': max_err, 'line_offsets': lo,
+            'vp_offsets': vo}
 
 
 def calc_angle_to_other_vp(v, i, k):
