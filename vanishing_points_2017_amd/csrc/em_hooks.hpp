@@ -229,12 +229,14 @@ VPK_DEV void hook_line_counts(EmCtx& c, int n, int m, const double* lp, const do
 }
 
 // ---- vpk_cluster2: D is the caller's n x n working copy (destroyed), member / csize n ints each ----------------------------
-VPK_DEV void hook_cluster2(int n, double* D, int* member, int* csize, int* labels_out, unsigned* flags_out) {
+// mode: EmCtx::smoother (1: the one-wave form of the LDS clustering); wt_doubles: the launch's LDS panel, as EmCtx::wt_doubles
+VPK_DEV void hook_cluster2(int n, double* D, int* member, int* csize, int* labels_out, unsigned* flags_out, int mode = 0,
+                           int wt_doubles = WT_DOUBLES) {
     Shared& sh = SH();
     if (tid() == 0) sh.flags = 0;
     block_sync();
     const int ld = n | 1;
-    if (n <= CLUSTER_LDS_MAX && cluster_lds_doubles(n) <= WT_DOUBLES) {   // same choice as split_vp
+    if (n <= CLUSTER_LDS_MAX && cluster_lds_doubles(n) <= wt_doubles) {   // same choice as split_vp
         double* DL = WT();
         for (int p = tid(); p < n * n; p += nthreads()) {
             const int a = p / n, b = p % n;
@@ -242,7 +244,7 @@ VPK_DEV void hook_cluster2(int n, double* D, int* member, int* csize, int* label
             DL[a * ld + b] = (a == b || !(v + D[(size_t)b * n + a] != 0.0)) ? -1.0 : v;
         }
         block_sync();
-        cluster2_lds(n);
+        cluster2_lds(n, mode);
         const int* lmember = cluster_lds_labels(DL, n);
         for (int q = tid(); q < n; q += nthreads()) member[q] = lmember[q];
         block_sync();

@@ -151,6 +151,11 @@ VPK_DEVFN int em_run(EmCtx& c, EmOut& o, EmSlice& sl) {
     long long tk = clock_ticks();
     const long long t_begin = tk;
     int first = 0;
+    // w, lvsq and p_vl in the slot are those of (sh.cur, sh.s, sh.M): the iteration's E-step + smoother would write the same
+    // values again and is left out.  True after the initial evaluation when the compaction behind it removed nothing
+    // (never for a resumed image) and after a split event that changed nothing (split_vp); vpk_em_set_smoother(h, 1)
+    // keeps every evaluation.
+    bool ew_valid = false;
     if (sl.start_iter >= 0) {
         restore_state(c);
         first = sl.start_iter;
@@ -198,9 +203,11 @@ VPK_DEVFN int em_run(EmCtx& c, EmOut& o, EmSlice& sl) {
     smooth(c);                                                // :246
     assign_lines(c, true);                                    // :247
     count_lines(c);
+    const int m_initial = sh.M;
     for (int m = tid(); m < sh.M; m += nthreads()) sh.removed[m] = sh.cnt[m] < 3;   // :250-251
     block_sync();
     compact_vps(c);
+    ew_valid = c.smoother != 1 && sh.M == m_initial;
     trace_put(o, P.num_iter, 1, lap(tk));
     }
 
@@ -220,12 +227,15 @@ VPK_DEVFN int em_run(EmCtx& c, EmOut& o, EmSlice& sl) {
         const long long t_iter = tk;
         if (sh.M == 0) { write_result(c, o, VPK_EM_NO_VP, 0); return EM_DONE; }     // :258-260
         double events = 0;
+        bool ew_skip = ew_valid;                              // (set for iteration 0 of a fresh image only: no split event there)
+        ew_valid = false;
         if (i % P.split_merge_freq == 0 && i > 0 && i < split_merge_it && P.do_split) {   // :262-269
             int mb = sh.M;
             if (tid() == 0) { sh.dbuf[11] = 0; sh.dbuf[12] = 0; sh.dbuf[13] = 0; }
             estep(c, sh.cur);
             smooth(c);
-            split_vp(c);
+            const int wrote = split_vp(c);
+            ew_skip = c.smoother != 1 && wrote == 0;
             if (sh.M != mb) events += 1;
             trace_put(o, i, 8, sh.dbuf[11]);
             trace_put(o, i, 9, sh.dbuf[12]);
@@ -238,9 +248,9 @@ VPK_DEVFN int em_run(EmCtx& c, EmOut& o, EmSlice& sl) {
             for (int m = 0; m < 3 * MAXM; ++m) q[1 + MAXM + m] = sh.cur[m];
         }
         lap(tk);
-        estep(c, sh.cur);                                     // :273
+        if (!ew_skip) estep(c, sh.cur);                       // :273
         trace_put(o, i, 4, lap(tk));
-        smooth(c);                                            // :282
+        if (!ew_skip) smooth(c);                              // :282
         trace_put(o, i, 5, lap(tk));
         double max_err = 0.0;
         if (P.do_iterations) {

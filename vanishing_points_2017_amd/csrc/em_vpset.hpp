@@ -149,21 +149,23 @@ VPK_DEVFN void cluster2(Shared&, int n, gdp D, gip member, gip csize) {
     block_sync();
 }
 
-// Same algorithm for small sets (the usual case: the lines of one VP; <= 72 lines in the YUD-shape bench), run by ONE
-// wave out of LDS so that a merge costs no workgroup barrier.  D is an n x ld matrix in LDS (ld odd, -1 = no edge; a
-// merged-away slot's row and column are set to -1, so the search needs no activity test per entry).  Per merge the
-// wave walks the active rows a with lanes over the columns b < a (consecutive LDS words, no index decoding), every
-// lane keeps its own best (distance, position), and ONE cross-lane arg-min ends the search -- a cross-lane
-// reduction of a double + index costs ~1000 cycles on this part (scripts/ubench/wave_reduce.hip), as much as walking
-// 30 rows, so the design minimises reductions, not LDS reads.  (Round 1 decoded a triangular pair index per entry:
-// ~10 us per merge; a per-row nearest-neighbour cache with a reduction per rescanned row was no faster.)
+// Same algorithm for small sets (the usual case: the lines of one VP; <= 72 lines in the YUD-shape bench) out of LDS.  D is an
+// n x ld matrix in LDS (ld odd, -1 = no edge; a merged-away slot's row and column are set to -1, so the search needs no
+// activity test per entry).  Per merge the active rows a are walked with lanes over the columns b < a (consecutive LDS
+// words, no index decoding), every lane keeps its own best (distance, position), and ONE cross-lane arg-min per wave ends
+// the search -- a cross-lane reduction of a double + index costs ~1000 cycles on this part (scripts/ubench/wave_reduce.hip),
+// as much as walking 30 rows, so the design minimises reductions, not LDS reads.  (Round 1 decoded a triangular pair index
+// per entry: ~10 us per merge; a per-row nearest-neighbour cache with a reduction per rescanned row was no faster.)
 // The matrix is the head of the LDS panel (WT()); behind it: member / csize [n] ints each.
+// Two bodies, same comparisons, same labels and flags: cluster2_lds_wave (rounds 2-6) has ONE wave do everything, so a merge
+// costs no workgroup barrier but the other waves wait for n - 2 walks of the whole triangle; cluster2_lds_block deals the
+// walk's trips of four rows to all waves and pays two barriers per merge.
 constexpr int CLUSTER_LDS_MAX = 128;
 VPK_DEV long long cluster_lds_doubles(int n) { return (long long)n * (n | 1) + (long long)n + 4; }
 VPK_DEV int* cluster_lds_labels(double* D, int n) {
     return reinterpret_cast<int*>(D + (size_t)n * (n | 1));
 }
-VPK_DEVFN void cluster2_lds(int n) {
+VPK_DEVFN void cluster2_lds_wave(int n) {
     Shared& sh = SH();
     // the matrix sits at the start of the LDS panel; deriving the pointer from the LDS symbol HERE (not taking it as
     // an argument of this non-inlined function) is what makes the accesses ds_read / ds_write instead of flat_*
@@ -248,13 +250,134 @@ VPK_DEVFN void cluster2_lds(int n) {
     block_sync();
 }
 
+// The whole workgroup on every merge.  The search's trips (four rows of one 64-column block, in the one-wave body's order)
+// are dealt to the waves round robin; a wave walks its trips as above and ends with its own arg-min.  The waves' results
+// -- minimum, its smallest position, and how often the minimum occurred (1 + the lane's tie mark, over the lanes that hold
+// it) -- go through sh.red_v / sh.red_i behind ONE barrier, and every wave reduces the (at most 16) candidates itself:
+// smallest distance, smallest position among equal distances, and the tie count summed over the waves whose minimum is
+// the global one (>= 2 exactly when the one-wave count is: the minimum sits at more than one position).  Every decision
+// that leaves the loop is taken from these exchanged words, so all waves take it together.  The update (Lance-Williams
+// average, the -1 row and column of the dead slot, member) has one slot per thread; a second barrier closes the merge.
+// csize of the merged pair is written by thread 0 AFTER that barrier and read after the next merge's first one: the
+// search in between does not look at it.
+// With one wave (the host build: one thread) this is the one-wave walk.
+VPK_DEVFN void cluster2_lds_block(int n) {
+    Shared& sh = SH();
+    double* D = WT();                                         // (from the LDS symbol, as above)
+    const int ld = n | 1;
+    int* member = cluster_lds_labels(D, n);
+    int* csize = member + n;
+    for (int a = tid(); a < n; a += nthreads()) { member[a] = a; csize[a] = 1; }
+    block_sync();
+    typedef unsigned long long u64;
+    const u64 NONE = 0x7fe0000000000000ull;                   // above every finite distance, below -1.0's pattern
+    constexpr int NOPOS = 0x7fffffff;
+    const int nw = nwaves() < 16 ? nwaves() : 16;             // red_i holds [position | tie count] x 16
+    const int w = wave_id();
+    int last_slot = -1;
+    bool tie_seen = false, disconnected = false;
+    for (int t = 0; t < n - 2; ++t) {
+        u64 bk = NONE;
+        int bi = NOPOS;
+        int ties = 0;
+        int trip0 = 0;                                        // trips of the column blocks before this one
+        for (int c0 = 0; c0 < n; c0 += WAVE) {
+            const int bq = c0 + lane();
+            const int astart = c0 > 0 ? c0 : 1;
+            const int ntrips = (n - astart + 3) / 4;
+            int first = (w - trip0) % nw;                     // this wave's first trip in the block
+            if (first < 0) first += nw;
+            for (int k = (w < nw ? first : ntrips); k < ntrips; k += nw) {
+                const int a0 = astart + 4 * k;
+                u64 key[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int a = a0 + u;
+                    const bool in = a < n && bq < a;
+                    key[u] = in ? __double_as_longlong(D[(in ? a : 0) * ld + (in ? bq : 0)]) : ~0ull;
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int pos = (a0 + u) * ld + bq;
+                    const bool eq = key[u] == bk && key[u] < NONE;
+                    const bool lt = key[u] < bk;
+                    ties = lt ? 0 : (eq ? 1 : ties);
+                    bi = (lt || (eq && pos < bi)) ? pos : bi;     // equal distances: the smallest position
+                    bk = lt ? key[u] : bk;
+                }
+            }
+            trip0 += ntrips;
+        }
+        double bv = bk < NONE ? __longlong_as_double((long long)bk) : 1e300;
+        if (!(bk < NONE)) bi = NOPOS;
+        const double myv = bv;
+        wave_argmin(bv, bi);
+        const int cnt = wave_sum_int((myv == bv && bi != NOPOS) ? 1 + ties : 0);
+        if (lane() == 0 && w < nw) { sh.red_v[w] = bv; sh.red_i[w] = bi; sh.red_i[16 + w] = cnt; }
+        block_sync();
+        double gv = sh.red_v[0];
+        int gi = sh.red_i[0];
+        for (int k = 1; k < nw; ++k) {
+            const double u = sh.red_v[k];
+            const int j = sh.red_i[k];
+            const bool take = (u < gv) || (u == gv && j < gi);
+            gv = take ? u : gv;
+            gi = take ? j : gi;
+        }
+        gi = uniform_int(gi);
+        if (gi == NOPOS) { disconnected = true; break; }      // graph exhausted (every wave reads the same words)
+        int gcnt = 0;
+        for (int k = 0; k < nw; ++k) gcnt += (sh.red_v[k] == gv && sh.red_i[k] != NOPOS) ? sh.red_i[16 + k] : 0;
+        if (gcnt >= 2) tie_seen = true;
+        const int ma = gi / ld, mb = gi - ma * ld;            // ma > mb; the merged cluster lives in slot ma
+        const int na = csize[ma], nb = csize[mb];
+        for (int cidx = tid(); cidx < n; cidx += nthreads()) {
+            if (member[cidx] == mb) member[cidx] = ma;
+            if (cidx == ma || cidx == mb) continue;
+            const double da = D[ma * ld + cidx], db = D[mb * ld + cidx];
+            double nv;
+            if (da >= 0 && db >= 0)
+                nv = (na * da + nb * db) / (double)(na + nb);  // average_merge
+            else
+                nv = da >= 0 ? da : db;                        // only one side connected (or none: -1)
+            D[ma * ld + cidx] = nv;                            // (dead slots hold -1 in every row: they stay -1)
+            D[cidx * ld + ma] = nv;
+            D[mb * ld + cidx] = -1.0;                          // slot mb leaves the search
+            D[cidx * ld + mb] = -1.0;
+        }
+        if (tid() == 0) { D[ma * ld + mb] = -1.0; D[mb * ld + ma] = -1.0; }
+        block_sync();
+        if (tid() == 0) { csize[ma] = na + nb; csize[mb] = 0; }
+        last_slot = ma;
+    }
+    for (int q = tid(); q < n; q += nthreads()) member[q] = (member[q] == last_slot) ? 0 : 1;
+    if (tid() == 0) {
+        if (tie_seen) sh.flags |= VPK_EM_FLAG_SPLIT_TIE;
+        if (disconnected) sh.flags |= VPK_EM_FLAG_SPLIT_DISCONNECTED;
+    }
+    block_sync();
+}
+
+// mode: EmCtx::smoother -- 1 selects the earlier form, as it does in the other phases (same bits either way).  Below 32 lines
+// the two barriers per merge cost more than the shared walk saves (measured per launch of vpk_cluster2, one wave | workgroup:
+// n = 9: 16 | 24 us, 24: 61 | 68, 28: 78 | 80, 32: 96 | 91, 48: 189 | 141, 64: 312 | 201, 72: 443 | 243, 126: 1606 | 583).
+constexpr int CLUSTER_BLOCK_MIN = 32;
+VPK_DEV void cluster2_lds(int n, int mode) {
+    if (mode == 1 || n < CLUSTER_BLOCK_MIN) cluster2_lds_wave(n); else cluster2_lds_block(n);
+}
+
 // ---------------------------------------------------------------------------------------------
 // split_best_vp (vp_localisation.py:527-630).  Expects w = weight matrix of sh.cur.
+// Returns, to every thread alike, what it changed of the state an E-step + smoother of sh.cur left behind: SPLIT_WROTE_VPS --
+// sh.cur / sh.s / sh.M (a split happened) --, SPLIT_WROTE_PVL -- the slot's p_vl rows (the directions of a very large set
+// were staged there).  0: w, lvsq and p_vl still belong to sh.cur, and the caller need not evaluate them again.  (The LDS
+// panel, assoc, idx and cl are overwritten in every case; nothing reads them before their next writer.)
 // ---------------------------------------------------------------------------------------------
-VPK_DEVFN void split_vp(EmCtx& c) {
+constexpr int SPLIT_WROTE_VPS = 1, SPLIT_WROTE_PVL = 2;
+VPK_DEVFN int split_vp(EmCtx& c) {
     Shared& sh = SH();
     const int M = sh.M, N = c.N;
-    if (M == 0 || c.cl == nullptr) return;
+    if (M == 0 || c.cl == nullptr) return 0;
     long long tq_ = clock_ticks();
     assign_lines(c, false);                                   // weightIndices (:536) == vpAssoc (:551)
     double wmx = -1e300;
@@ -287,50 +410,106 @@ VPK_DEVFN void split_vp(EmCtx& c) {
         }
     }
     block_sync();
-    if (tid() == 0) {
-        // worstVPs = argsort(stdd)[::-1] (:546-547): ascending with NaN last, reversed
-        int order[MAXM];
-        for (int m = 0; m < M; ++m) order[m] = m;
-        for (int i = 1; i < M; ++i) {                         // stable insertion sort
-            int key = order[i];
-            double kv = sh.err[key];
-            int j = i - 1;
-            while (j >= 0) {
-                double jv = sh.err[order[j]];
-                bool greater = (is_nan(jv) && !is_nan(kv)) || (jv > kv);
-                if (!greater) break;
-                order[j + 1] = order[j];
-                --j;
+    if (c.smoother != 1) {
+        // Wave 0, one lane per VP (thread 0's insertion sort through a private array and its serial scan were more than half of
+        // the selection: 6.2 of 11.2 CU-ms per YUD batch).  A stable sort puts VP m behind every VP that is smaller and every
+        // equal one with a smaller index -- `greater` is the comparison of the sort below --, so each lane counts its own
+        // position; the scan's first hit is the lowest set bit of a ballot; the compaction loads four chunks at a time.
+        if (wave_id() == 0) {
+            int* order = sh.removed;                          // scratch here: every user writes it before it reads it
+            for (int m = lane(); m < M; m += WAVE) {
+                const double kv = sh.err[m];
+                int pos = 0;
+                for (int j = 0; j < M; ++j) {
+                    const double jv = sh.err[j];
+                    const bool j_greater = (is_nan(jv) && !is_nan(kv)) || (jv > kv);
+                    const bool m_greater = (is_nan(kv) && !is_nan(jv)) || (kv > jv);
+                    pos += (m_greater || (j < m && !j_greater)) ? 1 : 0;
+                }
+                order[pos] = m;
             }
-            order[j + 1] = key;
-        }
-        int worst = -1;
-        for (int m = 0; m < M; ++m) {
-            int cand = order[M - 1 - m];
-            double px = sh.cur[3 * m] / sh.cur[3 * m + 2];    // :557 tests VP m, not worstVPs[m]
-            double py = sh.cur[3 * m + 1] / sh.cur[3 * m + 2];
-            if (sh.icnt[cand] > 8 && (px > -1 && py > -1 && px < 1 && py < 1)) { worst = cand; break; }
-        }
-        sh.ibuf[3] = worst;
-    }
-    block_sync();
-    if (wave_id() == 0) {                                     // assocLines, ascending (:552): ordered compaction
-        const int worst = sh.ibuf[3];
-        int nw = 0;
-        if (worst >= 0)
-            for (int n0 = 0; n0 < N; n0 += WAVE) {
-                const int n = n0 + lane();
-                const bool hit = n < N && c.assoc[n] == worst;
-                const unsigned long long mask = wave_ballot(hit);
-                if (hit) c.idx[nw + popcount64(mask & lanes_below())] = n;
-                nw += popcount64(mask);
+            wave_sync();
+            int worst = -1;
+            for (int m0 = 0; m0 < M && worst < 0; m0 += WAVE) {
+                const int m = m0 + lane();
+                int cand = -1;
+                bool ok = false;
+                if (m < M) {
+                    cand = order[M - 1 - m];
+                    const double px = sh.cur[3 * m] / sh.cur[3 * m + 2];    // :557 tests VP m, not worstVPs[m]
+                    const double py = sh.cur[3 * m + 1] / sh.cur[3 * m + 2];
+                    ok = sh.icnt[cand] > 8 && (px > -1 && py > -1 && px < 1 && py < 1);
+                }
+                const unsigned long long hits = wave_ballot(ok);
+                if (hits) worst = wave_bcast_int(cand, __builtin_ctzll(hits));
             }
-        if (lane() == 0) sh.ibuf[4] = nw;
+            int nw = 0;
+            if (worst >= 0)
+                for (int n0 = 0; n0 < N; n0 += 4 * WAVE) {
+                    int as[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const int n = n0 + u * WAVE + lane();
+                        as[u] = n < N ? c.assoc[n] : -1;
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const int n = n0 + u * WAVE + lane();
+                        const bool hit = as[u] == worst;      // (worst >= 0; -1 marks a line past the end)
+                        const unsigned long long mask = wave_ballot(hit);
+                        if (hit) c.idx[nw + popcount64(mask & lanes_below())] = n;
+                        nw += popcount64(mask);
+                    }
+                }
+            if (lane() == 0) { sh.ibuf[3] = worst; sh.ibuf[4] = nw; }
+        }
+        block_sync();
+    } else {
+        if (tid() == 0) {
+            // worstVPs = argsort(stdd)[::-1] (:546-547): ascending with NaN last, reversed
+            int order[MAXM];
+            for (int m = 0; m < M; ++m) order[m] = m;
+            for (int i = 1; i < M; ++i) {                         // stable insertion sort
+                int key = order[i];
+                double kv = sh.err[key];
+                int j = i - 1;
+                while (j >= 0) {
+                    double jv = sh.err[order[j]];
+                    bool greater = (is_nan(jv) && !is_nan(kv)) || (jv > kv);
+                    if (!greater) break;
+                    order[j + 1] = order[j];
+                    --j;
+                }
+                order[j + 1] = key;
+            }
+            int worst = -1;
+            for (int m = 0; m < M; ++m) {
+                int cand = order[M - 1 - m];
+                double px = sh.cur[3 * m] / sh.cur[3 * m + 2];    // :557 tests VP m, not worstVPs[m]
+                double py = sh.cur[3 * m + 1] / sh.cur[3 * m + 2];
+                if (sh.icnt[cand] > 8 && (px > -1 && py > -1 && px < 1 && py < 1)) { worst = cand; break; }
+            }
+            sh.ibuf[3] = worst;
+        }
+        block_sync();
+        if (wave_id() == 0) {                                     // assocLines, ascending (:552): ordered compaction
+            const int worst = sh.ibuf[3];
+            int nw = 0;
+            if (worst >= 0)
+                for (int n0 = 0; n0 < N; n0 += WAVE) {
+                    const int n = n0 + lane();
+                    const bool hit = n < N && c.assoc[n] == worst;
+                    const unsigned long long mask = wave_ballot(hit);
+                    if (hit) c.idx[nw + popcount64(mask & lanes_below())] = n;
+                    nw += popcount64(mask);
+                }
+            if (lane() == 0) sh.ibuf[4] = nw;
+        }
+        block_sync();
     }
-    block_sync();
     const int worst = sh.ibuf[3], nw = sh.ibuf[4];
     if (tid() == 0) sh.dbuf[11] += lap(tq_);
-    if (worst < 0) return;
+    if (worst < 0) return 0;
     const double stdd = sh.s[worst] / 2;                      // :566
     gip member = c.idx + N;          // idx has room for 3N ints
     gip csize = c.idx + 2 * N;
@@ -378,7 +557,7 @@ VPK_DEVFN void split_vp(EmCtx& c) {
     }
     block_sync();
     if (in_lds) {
-        cluster2_lds(nw);
+        cluster2_lds(nw, c.smoother);
         const int* lmember = cluster_lds_labels(DL, nw);
         for (int q = tid(); q < nw; q += nthreads()) member[q] = lmember[q];
         block_sync();
@@ -423,6 +602,7 @@ VPK_DEVFN void split_vp(EmCtx& c) {
             double ang = fabs(acos(clip(fabs(cphi), -1.0, 1.0)));
             if (ang > c.prm.merge_thresh) too_similar = false;
         }
+        sh.ibuf[0] = too_similar ? 0 : SPLIT_WROTE_VPS;
         if (!too_similar) {                                   // :617-628 (both clusters valid here)
             sh.cur[3 * worst] = v0[0]; sh.cur[3 * worst + 1] = v0[1]; sh.cur[3 * worst + 2] = v0[2];
             sh.s[worst] = stdd;
@@ -439,6 +619,7 @@ VPK_DEVFN void split_vp(EmCtx& c) {
     }
     if (tid() == 0) sh.dbuf[13] += lap(tq_);
     block_sync();
+    return sh.ibuf[0] | (dirs_lds ? 0 : SPLIT_WROTE_PVL);     // (ibuf[0]: next written by merge_vps, behind its barriers)
 }
 
 }  // namespace vpk

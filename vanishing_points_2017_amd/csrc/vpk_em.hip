@@ -362,8 +362,8 @@ __global__ __launch_bounds__(EM_BOUND) void line_counts_kernel(int n, int m, con
 }
 
 __global__ __launch_bounds__(EM_BOUND) void cluster2_kernel(int n, double* D, int* member, int* csize,
-                                                              int* labels_out, unsigned* flags_out) {
-    hook_cluster2(n, D, member, csize, labels_out, flags_out);
+                                                              int* labels_out, unsigned* flags_out, int smoother, int wt_doubles) {
+    hook_cluster2(n, D, member, csize, labels_out, flags_out, smoother, wt_doubles);
 }
 
 template <typename K>
@@ -795,7 +795,9 @@ int vpk_cluster2(vpk_handle* h, int n, const double* ldist, int32_t* labels_out,
     double* D = (double*)h->small_ws;
     int* member = (int*)(D + (size_t)n * n);
     VPK_HIP(h, hipMemcpyAsync(D, ldist, (size_t)n * n * 8, hipMemcpyDeviceToDevice, h->stream));
-    return hook_launch(h, cluster2_kernel, EM_LDS_BYTES, n, D, member, member + n, (int*)labels_out, (unsigned*)flags_out);
+    // the whole CU's LDS, as the batch kernel has it when it runs one workgroup per CU: sets of up to 126 lines cluster in LDS
+    return hook_launch(h, cluster2_kernel, EM_LDS_BYTES_BIG, n, D, member, member + n, (int*)labels_out, (unsigned*)flags_out,
+                       h->em_smoother, WT_DOUBLES_BIG);
 }
 
 }  // extern "C"
