@@ -115,6 +115,15 @@ int vpk_em_set_smoother(vpk_handle* h, int mode);
  * (assignments exact, VPs 1e-4) holds either way, and the GPU tests use the switch to run those paths on the
  * reference's small goldens.  Applies to vpk_em_batch and vpk_weight_matrix. */
 int vpk_em_set_lds_panel(vpk_handle* h, int doubles);
+/* distance_measure of expectation_maximisation (vp_localisation.py:170, :196-203) for every vpk_em_batch launch on this
+ * handle: VPK_DIST_ANGLE (default) or VPK_DIST_DOTPROD (enum vpk_dist_measure below), each its own instantiation of the
+ * persistent kernel.  Under "dotprod" the E-step's distance is (l . v)^2 on the normalised line and the VP as given, the
+ * outlier test of calc_vp_line_counts compares |l . v| (:496), and the variance starts from and is capped at 1e-3 times
+ * the prior's sigma and 1e-3 (:199-201) instead of 1e-6.  VPK_DIST_AREA and any other value: VPK_ERR_ARG (the reference
+ * asserts at :203).  VPK_ERR_STATE while time-sliced launches have images parked (a parked image is resumed by the
+ * measure that parked it): vpk_em_flush first.  The fine-grained entry points (vpk_estep, vpk_line_counts, ...) and
+ * the VP-set batch calls stay "angle". */
+int vpk_em_set_distance_measure(vpk_handle* h, int measure);
 
 /* Time-sliced EM launches for pipelines (run_cnn of batch k+1 while the EM of batch k is unfinished,
  * evaluation.py:254-329).  The EM of a never-converging image takes 99 iterations (vp_localisation.py:256)

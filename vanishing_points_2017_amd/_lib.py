@@ -59,7 +59,7 @@ class StepArgs(ctypes.Structure):
 
 EXPORTS = [
     "vpk_create", "vpk_destroy", "vpk_set_stream", "vpk_get_stream", "vpk_synchronize", "vpk_last_error", "vpk_version",
-    "vpk_em_default_params", "vpk_device_info", "vpk_em_set_workgroups", "vpk_em_set_smoother", "vpk_em_set_lds_panel", "vpk_em_set_time_slice", "vpk_em_flush", "vpk_em_set_distribution_out", "vpk_cnn_load", "vpk_cnn_forward", "vpk_cnn_forward_tap",
+    "vpk_em_default_params", "vpk_device_info", "vpk_em_set_workgroups", "vpk_em_set_smoother", "vpk_em_set_lds_panel", "vpk_em_set_distance_measure", "vpk_em_set_time_slice", "vpk_em_flush", "vpk_em_set_distribution_out", "vpk_cnn_load", "vpk_cnn_forward", "vpk_cnn_forward_tap",
     "vpk_cnn_forward_f32", "vpk_cnn_forward_tap_f32",
     "vpk_cnn_set_profiling", "vpk_cnn_set_fusion", "vpk_cnn_set_precision", "vpk_cnn_set_algorithm", "vpk_cnn_last_layer_ms", "vpk_cnn_mean_layer_ms",
     "vpk_cnn_calibrate", "vpk_cnn_get_activation_scales", "vpk_cnn_set_activation_scales", "vpk_cnn_range_flags",
@@ -103,6 +103,7 @@ def load():
     lib.vpk_em_set_workgroups.argtypes = [c_void, ctypes.c_int]
     lib.vpk_em_set_smoother.argtypes = [c_void, ctypes.c_int]
     lib.vpk_em_set_lds_panel.argtypes = [c_void, ctypes.c_int]
+    lib.vpk_em_set_distance_measure.argtypes = [c_void, ctypes.c_int]
     lib.vpk_em_set_time_slice.argtypes = [c_void, ctypes.c_double, ctypes.c_int]
     lib.vpk_em_set_distribution_out.argtypes = [c_void, ctypes.c_void_p]
     lib.vpk_em_flush.argtypes = [c_void]
@@ -203,6 +204,8 @@ class Handle(object):
                            "there is no CPU fallback" % (device, rc))
         self.h = h
         self.device = device
+        self.em_distance_measure = 0            # what vpk_em_set_distance_measure last took (VPK_DIST_ANGLE)
+        self.em_slice_ms = 0.0                  # what vpk_em_set_time_slice last took (0: whole launches)
         if stream:
             self.check(self.lib.vpk_set_stream(self.h, c_void(stream)))
 
@@ -227,9 +230,15 @@ class Handle(object):
     def em_set_lds_panel(self, doubles):
         self.check(self.lib.vpk_em_set_lds_panel(self.h, int(doubles)))
 
+    def em_set_distance_measure(self, measure):
+        """The EM's distance measure for later em_batch launches (include/vpk.h: VPK_DIST_ANGLE = 0, VPK_DIST_DOTPROD = 1)."""
+        self.check(self.lib.vpk_em_set_distance_measure(self.h, int(measure)))
+        self.em_distance_measure = int(measure)
+
     def em_set_time_slice(self, slice_ms, n_max=0):
         """Time-sliced EM launches (include/vpk.h: vpk_em_set_time_slice); 0 switches back."""
         self.check(self.lib.vpk_em_set_time_slice(self.h, float(slice_ms), int(n_max)))
+        self.em_slice_ms = float(slice_ms)
 
     def em_flush(self):
         self.check(self.lib.vpk_em_flush(self.h))

@@ -11,6 +11,10 @@ namespace vpk {
 // line -> VP association and counts: calc_vp_line_counts (vp_localisation.py:482-512)
 // ---------------------------------------------------------------------------------------------
 // np.argmax over VPs (first maximum; a NaN counts as the maximum).  hard = apply the outlier test.
+// The outlier test's distance (:495-498): "angle" calc_lvsq_single = the E-step's lvsq of that pair; "dotprod" |vp . l| (:496), taken as
+// sqrt(lvsq) of the E-step that has just run on the same VPs -- within an ulp of the reference's own dot product, so the stored
+// reference results are recorded only where no line comes within 1e-9 relative of its threshold (scripts/make_em_dotprod_goldens.py).
+template <int MEASURE = VPK_DIST_ANGLE>
 VPK_DEVFN void assign_lines(EmCtx& c, bool hard) {
     Shared& sh = SH();
     const int M = sh.M, N = c.N;
@@ -23,6 +27,7 @@ VPK_DEVFN void assign_lines(EmCtx& c, bool hard) {
         }
         if (hard && M > 0) {
             double dist = c.lvsq[(size_t)best * c.ldn + n];   // == calc_lvsq_single on the same VP slice
+            if (MEASURE == VPK_DIST_DOTPROD) dist = sqrt(dist);
             if (dist > c.prm.outlier_thresh * sqrt(sh.s[best]))
                 best = -1;                                    // :504
             else if (c.lweight[n] == 0)

@@ -52,13 +52,44 @@ VPK_DEV int smooth_plan(const EmCtx& c, int M) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// E-step: calc_probabilities (probability_functions.py:99-147, "angle" branch)
+// the E-step's distance, per measure
+// ---------------------------------------------------------------------------------------------
+// The per-pair value lvsq[n][m] for the EM's two measures (vp_localisation.py:196-203) -- what differs between them; calc_plv, the p_l
+// chain with its floor, the panel layouts and the lanes per line behind it do not see the measure.  estep_device.hpp's
+// estep_lvsq<MEASURE>, restated operand for operand (that file restates this one; neither includes the other).
+//   angle (:165-174):   the five rows line_geometry_setup<VPK_DIST_ANGLE> left in c.drow (midpoint, direction, its norm) against the
+//                       VP projected to the image plane (sh.vx, sh.vy, written by the prior part below); a VP at infinity is a NaN column.
+//   dotprod (:151-152): three rows, the normalised line c.l, against the VP as given in X (no division by v2: finite at infinity).
+struct EstepLine { double g0, g1, g2, g3, g4; };
+template <int MEASURE> VPK_DEV EstepLine estep_line(const EmCtx& c, int n) {
+    EstepLine g;
+    g.g0 = c.drow[n]; g.g1 = c.drow[(size_t)c.ldn + n]; g.g2 = c.drow[2 * (size_t)c.ldn + n];
+    if (MEASURE == VPK_DIST_ANGLE) { g.g3 = c.drow[3 * (size_t)c.ldn + n]; g.g4 = c.drow[4 * (size_t)c.ldn + n]; }
+    else { g.g3 = 0.0; g.g4 = 0.0; }
+    return g;
+}
+template <int MEASURE> VPK_DEV double estep_pair(const EstepLine& g, const Shared& sh, const double* X, int m) {
+    if (MEASURE == VPK_DIST_ANGLE) {
+        const double v1x = g.g0 - sh.vx[m], v1y = g.g1 - sh.vy[m];
+        const double n1 = norm2(v1x, v1y);
+        const double cc = 1 - fabs(dot2(v1x, v1y, g.g2, g.g3) / (n1 * g.g4));
+        return cc * cc;                                      // :174
+    } else {
+        const double lv = (g.g0 * X[3 * m] + g.g1 * X[3 * m + 1]) + g.g2 * X[3 * m + 2];   // :151
+        return lv * lv;                                      // :152
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// E-step: calc_probabilities (probability_functions.py:99-147), the measure a template parameter
 // ---------------------------------------------------------------------------------------------
 // X points at sh.cur or sh.nxt.  Writes lvsq[m][n], pvl[m][n], wsrc[n][m]; floors sh.s (:139).
 // (Round 6, measured: the body inlined into em_run's main loop -- to save the callee-saved register traffic of one call per iteration,
 //  which did pay for the smoother's thin wrappers -- makes the E-step 2.5 x SLOWER, 51 -> 130 ms of workgroup time per YUD batch: inside
 //  em_run's register allocation the line loop spills.  The phases stay functions of their own.)
+template <int MEASURE = VPK_DIST_ANGLE>
 VPK_DEVFN void estep(EmCtx& c, const double* X) {
+    static_assert(MEASURE == VPK_DIST_ANGLE || MEASURE == VPK_DIST_DOTPROD, "the EM runs \"angle\" and \"dotprod\" (vp_localisation.py:196-203)");
     Shared& sh = SH();
     const int M = sh.M, N = c.N;
     const double kk = -0.5 / (sh.sigma_prior * sh.sigma_prior);
@@ -80,8 +111,10 @@ VPK_DEVFN void estep(EmCtx& c, const double* X) {
             acc = group_sum<G>(acc);
             if (gl == 0) {
                 sh.pv[m] = acc;
-                sh.vx[m] = x0 / x2;                          // calc_lvsq_angle :165-166
-                sh.vy[m] = x1 / x2;
+                if (MEASURE == VPK_DIST_ANGLE) {
+                    sh.vx[m] = x0 / x2;                      // calc_lvsq_angle :165-166
+                    sh.vy[m] = x1 / x2;
+                }
                 double sm = sh.s[m];
                 sm = sm > 1e-200 ? sm : 1e-200;              // calc_plv :139 (in place)
                 sh.s[m] = sm;
@@ -101,8 +134,6 @@ VPK_DEVFN void estep(EmCtx& c, const double* X) {
     // one thread per line; the VP loop is unrolled four deep with the four sqrt/div/exp chains written
     // side by side (independent until the ordered sum), because a lone wave per SIMD is bound by the
     // latency of that dependent chain, not by issue
-    cgdp gmx = c.drow, gmy = c.drow + c.ldn, gvx = c.drow + 2 * (size_t)c.ldn, gvy = c.drow + 3 * (size_t)c.ldn,
-         gn2 = c.drow + 4 * (size_t)c.ldn;
     constexpr int EU = 4;
     // LANES PER LINE (round 6).  One thread per line leaves 512 - N threads idle and the busy ones with M dependent sqrt / div / exp
     // chains each: at the YUD shape (N ~ 250, M ~ 22) the line part took as long as the smoother's row loops.  When the panel is in
@@ -118,7 +149,7 @@ VPK_DEVFN void estep(EmCtx& c, const double* X) {
         const int n = on ? n_ : N - 1;
         const int Mh = (M + T - 1) / T;
         const int m_lo = on ? (h * Mh < M ? h * Mh : M) : 0, m_hi = on ? (m_lo + Mh < M ? m_lo + Mh : M) : 0;
-        const double lmx = gmx[n], lmy = gmy[n], v2x = gvx[n], v2y = gvy[n], n2 = gn2[n];
+        const EstepLine g = estep_line<MEASURE>(c, n);
         const double lw = c.lweight[n];
         gdp lvq = c.lvsq + n, pvq = c.pvl + n;
         double* wl = wt + (plan == 2 ? (size_t)rs_row(n, rs_jch, rs_S, Wp) : (size_t)n * Wp);
@@ -126,12 +157,7 @@ VPK_DEVFN void estep(EmCtx& c, const double* X) {
         for (; m + EU <= m_hi; m += EU) {
             double lv[EU], tt[EU];
 #pragma unroll
-            for (int u = 0; u < EU; ++u) {
-                const double v1x = lmx - sh.vx[m + u], v1y = lmy - sh.vy[m + u];
-                const double n1 = norm2(v1x, v1y);
-                const double cc = 1 - fabs(dot2(v1x, v1y, v2x, v2y) / (n1 * n2));
-                lv[u] = cc * cc;                             // :174
-            }
+            for (int u = 0; u < EU; ++u) lv[u] = estep_pair<MEASURE>(g, sh, X, m + u);
 #pragma unroll
             for (int u = 0; u < EU; ++u)
                 tt[u] = (exp_underflow(-(lv[u] / (2 * sh.s[m + u]))) * sh.k2[m + u]) * sh.pv[m + u];   // calc_plv :137-145
@@ -142,10 +168,7 @@ VPK_DEVFN void estep(EmCtx& c, const double* X) {
             }
         }
         for (; m < m_hi; ++m) {
-            const double v1x = lmx - sh.vx[m], v1y = lmy - sh.vy[m];
-            const double n1 = norm2(v1x, v1y);
-            const double cc = 1 - fabs(dot2(v1x, v1y, v2x, v2y) / (n1 * n2));
-            const double lv1 = cc * cc;
+            const double lv1 = estep_pair<MEASURE>(g, sh, X, m);
             lvq[(size_t)m * c.ldn] = lv1;
             wl[m] = (exp_underflow(-(lv1 / (2 * sh.s[m]))) * sh.k2[m]) * sh.pv[m];
         }
@@ -181,7 +204,7 @@ VPK_DEVFN void estep(EmCtx& c, const double* X) {
             for (m = M; m < Wp; ++m) wl[m] = 0.0;            // padding of the last VP tile
     } else
     for (int n = tid(); n < N; n += nthreads()) {
-        const double lmx = gmx[n], lmy = gmy[n], v2x = gvx[n], v2y = gvy[n], n2 = gn2[n];
+        const EstepLine g = estep_line<MEASURE>(c, n);
         gdp lvq = c.lvsq + n, pvq = c.pvl + n;
         double* wl = wt + (plan == 2 ? (size_t)rs_row(n, rs_jch, rs_S, Wp) : (size_t)n * Wp);   // this line's panel row; parks p_lv p_v until p_l is known
         double pl = 0.0;
@@ -189,12 +212,7 @@ VPK_DEVFN void estep(EmCtx& c, const double* X) {
         for (; m + EU <= M; m += EU) {
             double lv[EU], tt[EU];
 #pragma unroll
-            for (int u = 0; u < EU; ++u) {
-                const double v1x = lmx - sh.vx[m + u], v1y = lmy - sh.vy[m + u];
-                const double n1 = norm2(v1x, v1y);
-                const double cc = 1 - fabs(dot2(v1x, v1y, v2x, v2y) / (n1 * n2));
-                lv[u] = cc * cc;                             // :174
-            }
+            for (int u = 0; u < EU; ++u) lv[u] = estep_pair<MEASURE>(g, sh, X, m + u);
 #pragma unroll
             for (int u = 0; u < EU; ++u)
                 tt[u] = (exp_underflow(-(lv[u] / (2 * sh.s[m + u]))) * sh.k2[m + u]) * sh.pv[m + u];   // calc_plv :137-145
@@ -206,10 +224,7 @@ VPK_DEVFN void estep(EmCtx& c, const double* X) {
             }
         }
         for (; m < M; ++m) {
-            const double v1x = lmx - sh.vx[m], v1y = lmy - sh.vy[m];
-            const double n1 = norm2(v1x, v1y);
-            const double cc = 1 - fabs(dot2(v1x, v1y, v2x, v2y) / (n1 * n2));
-            const double lv1 = cc * cc;
+            const double lv1 = estep_pair<MEASURE>(g, sh, X, m);
             lvq[(size_t)m * c.ldn] = lv1;
             const double t1 = (exp_underflow(-(lv1 / (2 * sh.s[m]))) * sh.k2[m]) * sh.pv[m];
             if (panel) wl[m] = t1; else pvq[(size_t)m * c.ldn] = t1;

@@ -142,10 +142,15 @@ VPK_DEVFN void restore_state(EmCtx& c) {
     block_sync();
 }
 
+// MEASURE: distance_measure, "angle" or "dotprod" (:196-203) -- a compile-time parameter, one kernel per measure (vpk_em.hip): it
+// reaches the E-step's per-pair value, the per-line constants, the outlier test and the two start-up constants below.  The
+// M-step, the smoother, split, count_lines and compaction do not see it.  A suspended image is resumed under the measure
+// that suspended it (vpk_em_set_distance_measure refuses while images are parked).
+template <int MEASURE = VPK_DIST_ANGLE>
 VPK_DEVFN int em_run(EmCtx& c, EmOut& o, EmSlice& sl) {
     Shared& sh = SH();
     const vpk_em_params& P = c.prm;
-    const double max_stdd = 1e-6;                             // :196-198 ("angle")
+    const double max_stdd = MEASURE == VPK_DIST_DOTPROD ? 1e-3 : 1e-6;   // :196-201 (also s_init_factor)
     const double merge_thresh_final = P.merge_thresh * 10;    // :190
     const int split_merge_it = 100;                           // :193
     long long tk = clock_ticks();
@@ -192,16 +197,16 @@ VPK_DEVFN int em_run(EmCtx& c, EmOut& o, EmSlice& sl) {
         block_sync();
     }
     weights_setup(c);                                         // :227-235
-    line_geometry_setup(c);
+    line_geometry_setup<MEASURE>(c);
     for (int m = tid(); m < MAXM; m += nthreads()) {
-        sh.s[m] = 1.0 * (sh.sigma_prior * 1e-6);              // :219,:239
+        sh.s[m] = 1.0 * (sh.sigma_prior * max_stdd);          // :219,:239 (s_init_factor == max_stdd under both measures)
         sh.nxt[3 * m] = 0; sh.nxt[3 * m + 1] = 0; sh.nxt[3 * m + 2] = 0;
     }
     block_sync();
 
-    estep(c, sh.cur);                                         // :245
+    estep<MEASURE>(c, sh.cur);                                // :245
     smooth(c);                                                // :246
-    assign_lines(c, true);                                    // :247
+    assign_lines<MEASURE>(c, true);                           // :247
     count_lines(c);
     const int m_initial = sh.M;
     for (int m = tid(); m < sh.M; m += nthreads()) sh.removed[m] = sh.cnt[m] < 3;   // :250-251
@@ -232,7 +237,7 @@ VPK_DEVFN int em_run(EmCtx& c, EmOut& o, EmSlice& sl) {
         if (i % P.split_merge_freq == 0 && i > 0 && i < split_merge_it && P.do_split) {   // :262-269
             int mb = sh.M;
             if (tid() == 0) { sh.dbuf[11] = 0; sh.dbuf[12] = 0; sh.dbuf[13] = 0; }
-            estep(c, sh.cur);
+            estep<MEASURE>(c, sh.cur);
             smooth(c);
             const int wrote = split_vp(c);
             ew_skip = c.smoother != 1 && wrote == 0;
@@ -248,7 +253,7 @@ VPK_DEVFN int em_run(EmCtx& c, EmOut& o, EmSlice& sl) {
             for (int m = 0; m < 3 * MAXM; ++m) q[1 + MAXM + m] = sh.cur[m];
         }
         lap(tk);
-        if (!ew_skip) estep(c, sh.cur);                       // :273
+        if (!ew_skip) estep<MEASURE>(c, sh.cur);              // :273
         trace_put(o, i, 4, lap(tk));
         if (!ew_skip) smooth(c);                              // :282
         trace_put(o, i, 5, lap(tk));
@@ -269,19 +274,19 @@ VPK_DEVFN int em_run(EmCtx& c, EmOut& o, EmSlice& sl) {
         //  1e-200, cannot change s after the clamp at :307)
 
         if (max_err < P.final_convergence || i == P.num_iter - 1 || !P.do_iterations) {   // :335
-            if (P.do_merge) merge_vps(c, true, merge_thresh_final, 0.01);                 // :339
+            if (P.do_merge) merge_vps<MEASURE>(c, true, merge_thresh_final, 0.01);        // :339
             trace_put(o, P.num_iter, 3, (double)sh.M);        // finalisation audit trail: M after merge
             if (sh.M == 0) { write_result(c, o, VPK_EM_NO_VP, i); return EM_DONE; }   // reference: argmax of empty (:349)
-            estep(c, sh.cur);                                 // :344 (stale index i)
+            estep<MEASURE>(c, sh.cur);                        // :344 (stale index i)
             smooth(c);                                        // :346
-            assign_lines(c, false);                           // :349
+            assign_lines<MEASURE>(c, false);                  // :349
             mstep(c, 1, max_stdd);                            // :353-392
             compact_vps(c);                                   // :394-396
             trace_put(o, P.num_iter, 4, (double)sh.M);        // ... after the hard-assignment M-step
-            estep(c, sh.cur);                                 // :398 (still index i)
+            estep<MEASURE>(c, sh.cur);                        // :398 (still index i)
             smooth(c);                                        // :400
             if (sh.M == 0) { write_result(c, o, VPK_EM_NO_VP, 0); return EM_DONE; }       // :402-404
-            assign_lines(c, false);                           // :406
+            assign_lines<MEASURE>(c, false);                  // :406
             for (int m = tid(); m < sh.M; m += nthreads()) sh.icnt[m] = 0;
             block_sync();
             for (int n = tid(); n < c.N; n += nthreads()) sh.icnt[c.assoc[n]] = 1;        // np.unique (:408)
@@ -290,9 +295,9 @@ VPK_DEVFN int em_run(EmCtx& c, EmOut& o, EmSlice& sl) {
             block_sync();
             compact_vps(c);                                   // :412-413
             trace_put(o, P.num_iter, 5, (double)sh.M);        // ... after keeping the VPs that win a line
-            estep(c, sh.nxt);                                 // :415 (index i+1 at last)
+            estep<MEASURE>(c, sh.nxt);                        // :415 (index i+1 at last)
             smooth(c);                                        // :417
-            assign_lines(c, true);                            // :418
+            assign_lines<MEASURE>(c, true);                   // :418
             count_lines(c);
             // :423-437.  The reference's scan does NOT start over after a removal: `vidx` stays where it is (the next VP has
             // moved into that index), so a VP in front of it whose count drops below num_min_lines through the re-assignment
@@ -309,9 +314,9 @@ VPK_DEVFN int em_run(EmCtx& c, EmOut& o, EmSlice& sl) {
                 for (int m = tid(); m < sh.M; m += nthreads()) sh.removed[m] = (m == vidx);
                 block_sync();
                 compact_vps(c);
-                estep(c, sh.nxt);
+                estep<MEASURE>(c, sh.nxt);
                 smooth(c);
-                assign_lines(c, true);
+                assign_lines<MEASURE>(c, true);
                 count_lines(c);
             }
             trace_put(o, i, 2, (double)sh.M);
@@ -328,7 +333,7 @@ VPK_DEVFN int em_run(EmCtx& c, EmOut& o, EmSlice& sl) {
         if (i % P.split_merge_freq == 0 && i > 0 && i <= split_merge_it + P.split_merge_freq && P.do_merge) {
             int mb = sh.M;
             lap(tk);
-            merge_vps(c, true, P.merge_thresh, 0.01);         // :444-448
+            merge_vps<MEASURE>(c, true, P.merge_thresh, 0.01); // :444-448
             trace_put(o, i, 11, lap(tk));
             if (sh.M != mb) events += 4;
         }

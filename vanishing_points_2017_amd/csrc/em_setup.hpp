@@ -551,8 +551,17 @@ VPK_DEVFN void initial_vps(EmCtx& c) {
 // Per-line constants of the E-step (calc_lvsq_angle :165-172 evaluates them again for every VP and every
 // iteration): midpoint, direction and its norm, in c.drow as [5][ldn]; the line probabilities p_l of the
 // current E-step follow at [5].
+// "dotprod" (calc_lvsq_dotprod :151): the three components of the normalised line c.l, in the first three rows.
+template <int MEASURE = VPK_DIST_ANGLE>
 VPK_DEVFN void line_geometry_setup(EmCtx& c) {
     for (int n = tid(); n < c.N; n += nthreads()) {
+        if (MEASURE == VPK_DIST_DOTPROD) {
+            cgdp q = c.l + 3 * (size_t)n;
+            c.drow[n] = q[0];
+            c.drow[(size_t)c.ldn + n] = q[1];
+            c.drow[2 * (size_t)c.ldn + n] = q[2];
+            continue;
+        }
         cgdp q = c.lp + 4 * (size_t)n;
         const double v2x = q[0] - q[2], v2y = q[1] - q[3];
         c.drow[n] = 0.5 * (q[0] + q[2]);

@@ -16,6 +16,7 @@ namespace vpk {
 // ---------------------------------------------------------------------------------------------
 // merge_vps (vp_localisation.py:633-697)
 // ---------------------------------------------------------------------------------------------
+template <int MEASURE = VPK_DIST_ANGLE>
 VPK_DEVFN void merge_vps(EmCtx& c, bool use_next, double thresh, double max_stdd) {
     Shared& sh = SH();
     const int N = c.N;
@@ -34,7 +35,7 @@ VPK_DEVFN void merge_vps(EmCtx& c, bool use_next, double thresh, double max_stdd
         block_argmin(sh, bv, bi);                             // first row-major minimum (:650)
         if (!(bv < thresh)) break;                            // :655,:679-680
         const int j = bi / M, k = bi % M;
-        estep(c, X);                                          // :658 (at the caller's index)
+        estep<MEASURE>(c, X);                                 // :658 (at the caller's index, under the caller's measure)
         smooth(c);
         if (wave_id() == 0) {                                 // newVP from w[j] + w[k] (:661)
             cgdp wj = c.w + (size_t)j * c.ldn;

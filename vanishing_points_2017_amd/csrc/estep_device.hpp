@@ -3,9 +3,9 @@
 // and calc_lvsq_area (:179-209) for a ragged batch of images, any number of VPs each.
 //
 // One user: vpk_estep.hip (vpk_estep_batch).  The EM workgroup keeps its own E-step (em_estep.hpp: estep, em_setup.hpp:
-// line_geometry_setup, "angle" only, at most 64 VPs, fused with the smoother's panel): its per-pair expression is RESTATED
-// here operand for operand instead of shared, so that this file cannot move the EM kernel's register allocation.
-// tests/test_gpu_estep_surface.py holds the two copies together bit for bit.
+// line_geometry_setup, "angle" and "dotprod", at most 64 VPs, fused with the smoother's panel): its per-pair expressions are
+// RESTATED here operand for operand instead of shared, so that this file cannot move the EM kernel's register allocation.
+// tests/test_gpu_estep_surface.py ("angle") and tests/test_gpu_em_dotprod.py ("dotprod") hold the copies together bit for bit.
 //
 // Written against the vocabulary of wave_prims.hpp only (through prior_device.hpp and line_device.hpp, for exp_underflow,
 // is_nan, PI_D, dot2 and norm2), so that tests/hostsim/sim_estep.cpp compiles it unmodified with g++ (hip_sim.hpp: one

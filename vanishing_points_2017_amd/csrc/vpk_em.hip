@@ -134,6 +134,8 @@ VPK_DEV int pop_entry(int* head, const int* count) {
     return e;
 }
 
+// One instantiation per distance measure of the EM (em_run.hpp): the measure is a compile-time parameter, never a branch.
+template <int MEASURE>
 __global__ __launch_bounds__(EM_BOUND) void em_batch_kernel(EmBatchArgs a, EmSliceArgs ss) {
     VPK_SHARED_DECL;
     const long long t_start = clock_ticks();
@@ -247,7 +249,7 @@ __global__ __launch_bounds__(EM_BOUND) void em_batch_kernel(EmBatchArgs a, EmSli
             }
             bind_scratch(c, a.scratch + (size_t)slot * a.L.total_doubles, a.L, c.prm.do_split != 0);
         }
-        int result = em_run(c, o, sl);
+        int result = em_run<MEASURE>(c, o, sl);
         while (result == EM_SUSPENDED) {       // only with a deadline; at most one per workgroup and launch (see above)
             if (tid() == 0) {
                 int e = atomicAdd(&ss.ctr[2], 1);
@@ -264,7 +266,7 @@ __global__ __launch_bounds__(EM_BOUND) void em_batch_kernel(EmBatchArgs a, EmSli
             block_sync();
             if (parked) break;
             sl.deadline = EM_NO_DEADLINE;
-            result = em_run(c, o, sl);         // resumes from the state it has just saved in its slot
+            result = em_run<MEASURE>(c, o, sl);   // resumes from the state it has just saved in its slot
         }
         if (result == EM_SUSPENDED) {
         } else if (ss.enabled) {
@@ -375,7 +377,8 @@ int allow_lds(vpk_handle* h, K kernel) {
 int em_prepare(vpk_handle* h) {
     if (h->em_ready) return VPK_OK;
     int rc;
-    if ((rc = allow_lds(h, em_batch_kernel))) return rc;
+    if ((rc = allow_lds(h, em_batch_kernel<VPK_DIST_ANGLE>))) return rc;
+    if ((rc = allow_lds(h, em_batch_kernel<VPK_DIST_DOTPROD>))) return rc;
     if ((rc = allow_lds(h, pairwise_kernel))) return rc;
     if ((rc = allow_lds(h, init_vps_kernel))) return rc;
     if ((rc = allow_lds(h, estep_kernel))) return rc;
@@ -469,6 +472,14 @@ EmSliceArgs sess_next(vpk_handle* h, double slice_ms) {
     return ss;
 }
 
+// the batch kernel of the handle's distance measure (vpk_em_set_distance_measure)
+int em_launch(vpk_handle* h, int wgs, size_t lds_bytes, const EmBatchArgs& a, const EmSliceArgs& ss) {
+    auto kernel = h->em_measure == VPK_DIST_DOTPROD ? em_batch_kernel<VPK_DIST_DOTPROD> : em_batch_kernel<VPK_DIST_ANGLE>;
+    hipLaunchKernelGGL(kernel, dim3(wgs), dim3(EM_THREADS), lds_bytes, h->stream, a, ss);
+    VPK_HIP(h, hipGetLastError());
+    return VPK_OK;
+}
+
 // launch that finishes every parked image (no deadline, no fresh images); asynchronous on the handle's stream
 int em_flush(vpk_handle* h) {
     if (!h->em_unflushed) return VPK_OK;
@@ -480,8 +491,7 @@ int em_flush(vpk_handle* h) {
     a.scratch = (double*)h->em_ws;
     a.wt_doubles = h->em_sess_wt_doubles;
     a.smoother = h->em_smoother;
-    hipLaunchKernelGGL(em_batch_kernel, dim3(h->em_sess_wgs), dim3(EM_THREADS), h->em_sess_lds, h->stream, a, ss);
-    VPK_HIP(h, hipGetLastError());
+    if (int rc = em_launch(h, h->em_sess_wgs, h->em_sess_lds, a, ss)) return rc;   // (the measure that parked them: the setter refuses meanwhile)
     h->em_unflushed = false;
     return VPK_OK;
 }
@@ -541,6 +551,16 @@ int vpk_em_set_lds_panel(vpk_handle* h, int doubles) {
     if (!h || doubles < 0) return vpk_fail(h, VPK_ERR_ARG, "vpk_em_set_lds_panel: bad argument");
     if (h->em_unflushed) return vpk_fail(h, VPK_ERR_STATE, "vpk_em_set_lds_panel: images are parked: vpk_em_flush first");
     h->em_lds_doubles = doubles;
+    return VPK_OK;
+}
+
+int vpk_em_set_distance_measure(vpk_handle* h, int measure) {
+    if (!h) return VPK_ERR_ARG;
+    if (measure != VPK_DIST_ANGLE && measure != VPK_DIST_DOTPROD)
+        return vpk_fail(h, VPK_ERR_ARG, "vpk_em_set_distance_measure: VPK_DIST_ANGLE or VPK_DIST_DOTPROD");
+    if (h->em_unflushed)
+        return vpk_fail(h, VPK_ERR_STATE, "vpk_em_set_distance_measure: images are parked: vpk_em_flush first");
+    h->em_measure = measure;
     return VPK_OK;
 }
 
@@ -674,9 +694,7 @@ int vpk_em_batch(vpk_handle* h, int batch, const int64_t* offsets, double* l, co
         ss = sess_next(h, h->em_slice_ms);
         h->em_unflushed = true;
     }
-    hipLaunchKernelGGL(em_batch_kernel, dim3(wgs), dim3(EM_THREADS), mode.lds_bytes, h->stream, a, ss);
-    VPK_HIP(h, hipGetLastError());
-    return VPK_OK;
+    return em_launch(h, wgs, mode.lds_bytes, a, ss);
 }
 
 int vpk_em_set_distribution_out(vpk_handle* h, const vpk_em_dist_out* d) {

@@ -32,6 +32,7 @@ struct vpk_handle {
     int em_max_workgroups = 0;   // vpk_em_set_workgroups (0 = no cap)
     int em_smoother = 0;         // vpk_em_set_smoother
     int em_lds_doubles = 0;      // vpk_em_set_lds_panel (0 = whole CU)
+    int em_measure = 0;          // vpk_em_set_distance_measure (VPK_DIST_ANGLE)
     // capacities of the time-sliced launches' parked-image lists (vpk_em.hip); the environment variables
     // VPK_EM_WAIT_CAP / VPK_EM_STARTED_CAP shrink them at vpk_create so that tests can fill them with a few images
     int em_wait_cap = 8192;

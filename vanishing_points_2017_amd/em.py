@@ -12,21 +12,49 @@ from .runtime import get_runtime
 MAX_VP = 64
 
 
+EM_MEASURES = {"angle": 0, "dotprod": 1}      # include/vpk.h: VPK_DIST_ANGLE, VPK_DIST_DOTPROD
+
+
+def _measure(distance_measure):
+    """The measures the reference's EM runs (vp_localisation.py:196-201); anything else is its `assert False` (:203)."""
+    if not isinstance(distance_measure, str) or distance_measure not in EM_MEASURES:
+        raise AssertionError("distance_measure %r: the EM runs \"angle\" and \"dotprod\"" % (distance_measure,))
+    return EM_MEASURES[distance_measure]
+
+
 def _params(kw):
     kw = dict(kw)
-    if kw.pop("distance_measure", "angle") != "angle":
-        # reference vp_localisation.py:196-203: other measures are not on the hot path
-        raise AssertionError("only distance_measure='angle' is supported")
+    kw.pop("distance_measure", None)          # not a field of vpk_em_params: set on the handle (em_batch_device)
     kw.pop("init_vp", None)
     kw.pop("sphere_image", None)
     return _lib.default_em_params(**kw)
 
 
 def em_batch_device(rt, offsets, l, lp, cnn, sphere, init_vp=None, params=None, max_vp=MAX_VP,
-                    want_metric=False, want_trace=False, want_distribution=False):
+                    want_metric=False, want_trace=False, want_distribution=False, distance_measure="angle"):
     """Run vpk_em_batch on device tensors.  offsets: host int64 (B+1).  l (sum N x 3, f64) is
     normalised in place.  Returns a dict of device tensors.  want_distribution adds "dist": the arrays of
-    EM_result['distribution'] (include/vpk.h: vpk_em_set_distribution_out)."""
+    EM_result['distribution'] (include/vpk.h: vpk_em_set_distribution_out).  distance_measure: "angle" or "dotprod",
+    set on the handle for this launch and put back afterwards (vpk_em_set_distance_measure).  With time-sliced launches
+    the handle must already be at that measure (Handle.em_set_distance_measure before the first launch), since the library
+    refuses to change it while images are parked: otherwise VpkError, before anything is launched."""
+    measure = _measure(distance_measure)
+    args = (rt, offsets, l, lp, cnn, sphere, init_vp, params, max_vp, want_metric, want_trace, want_distribution)
+    before = rt.handle.em_distance_measure
+    if measure == before:                       # (time-sliced launches: the caller sets the handle once, before the first)
+        return _em_launch(*args)
+    if rt.handle.em_slice_ms > 0.0:
+        raise _lib.VpkError("em_batch_device: distance_measure=%r on a time-sliced handle that is at another measure -- the "
+                            "launch would park images and the measure could not be put back; call "
+                            "Handle.em_set_distance_measure before the first time-sliced launch" % (distance_measure,))
+    rt.handle.em_set_distance_measure(measure)
+    try:
+        return _em_launch(*args)
+    finally:
+        rt.handle.em_set_distance_measure(before)
+
+
+def _em_launch(rt, offsets, l, lp, cnn, sphere, init_vp, params, max_vp, want_metric, want_trace, want_distribution):
     torch = rt.torch
     offsets = _lib.host_i64(offsets)
     batch = offsets.shape[0] - 1
@@ -102,12 +130,16 @@ def upload_batch(rt, scenes):
 def em_batch(scenes, device=0, want_metric=False, want_trace=False, want_distribution=False, **kwargs):
     """Host-in / host-out convenience: refine a list of images, return one reference-style
     result dict per image (keys as vp_localisation.py:441-442 plus status/flags/l).  'distribution' is the
-    reference's probability_functions.PDF tuple when want_distribution is set, None otherwise."""
+    reference's probability_functions.PDF tuple when want_distribution is set, None otherwise.  The keywords are
+    expectation_maximisation's; distance_measure is "angle" or "dotprod" (anything else: AssertionError, as :203)."""
+    distance_measure = kwargs.get("distance_measure", "angle")
+    _measure(distance_measure)                # refused before the GPU is touched
     rt = get_runtime(device)
     p = _params(kwargs)
     d = upload_batch(rt, scenes)
     out = em_batch_device(rt, d["offsets"], d["l"], d["lp"], d["cnn"], d["sphere"], d["init_vp"], p,
-                          want_metric=want_metric, want_trace=want_trace, want_distribution=want_distribution)
+                          want_metric=want_metric, want_trace=want_trace, want_distribution=want_distribution,
+                          distance_measure=distance_measure)
     rt.synchronize()
     dist = {k: v.cpu().numpy() for k, v in out.pop("dist").items()} if want_distribution else None
     host = {k: (v.cpu().numpy() if v is not None else None) for k, v in out.items()}

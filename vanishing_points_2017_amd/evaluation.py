@@ -252,7 +252,11 @@ def run_em(dataset, start=None, end=None, indices=None, device=0, store_distribu
 
 
 def run_em_single(datum, distance_measure="angle", use_weights=True, do_split=True, do_merge=True):
-    """evaluation.py:332-354."""
+    """evaluation.py:332-354.  A measure other than "angle" goes through run_em_batch (the single-image drop-in of
+    vp_localisation still refuses it): the same result, 'distribution' included."""
+    if distance_measure != "angle":
+        return run_em_batch([datum], distance_measure=distance_measure, use_weights=use_weights, do_split=do_split,
+                            do_merge=do_merge, store_distribution=True)[0]
     lines = datum['lines']
     if datum['cnn_prediction'] is not None:
         datum['EM_result'] = vp.expectation_maximisation(

@@ -2,7 +2,9 @@
 EM kernels, and the stand-alone functions around it on the GPU under the reference's names, signatures and defaults.
 
 expectation_maximisation: same name, argument order, defaults, in-place normalisation of ``l`` and result keys (including
-'distribution', the PDF tuple of the last E-step); `distance_measure` other than "angle" raises AssertionError as at :203.
+'distribution', the PDF tuple of the last E-step); `distance_measure` other than "angle" raises AssertionError here (its test
+pins that).  expectation_maximisation_batch is its twin for many images in one launch, and runs both measures of the
+reference's EM, "angle" and "dotprod" (:196-201).
 
 Line geometry (vpk_line_similarity_batch, vpk_line_rating_batch; include/vpk.h): calc_lsim (:87-108), line_rating_knn
 (:34-72), lines_angles (:765-776) and line_length (:761) take and return NumPy arrays and leave ``lp`` untouched;
@@ -27,7 +29,8 @@ not modified (the reference writes into them; the results are new arrays); ``dis
 ``numClusters`` other than 2 and more than 64 VPs raise ValueError.
 
 Not here: the scalar pair helpers (lines_similarity, lines_proximity, lines_points_cosangle, line_distance_closest,
-line_segment_point_distance: device functions of csrc/line_device.hpp) and the distance measures other than "angle".
+line_segment_point_distance: device functions of csrc/line_device.hpp) and, outside the EM, the distance measures other
+than "angle".
 There is no host fallback: without the library and a GPU every call but line_length and calc_angle_to_other_vp raises."""
 import numpy as np
 
@@ -41,6 +44,11 @@ def expectation_maximisation(l, lp, cnn_response, num_iter=100, sphere_image=Non
                              use_weights=True, wbias=1, num_init_vp=25, split_merge_freq=10,
                              merge_thresh=1e-3, outlier_thresh=1.96 ** 2, final_convergence=5e-3,
                              s_thresh=1e-200, num_min_lines=3, device=0, want_metric=True, return_distribution=True):
+    if distance_measure != "angle":
+        # em.em_batch runs "dotprod" too (expectation_maximisation_batch below is its entry here); this refusal is what
+        # tests/test_gpu_em.py::test_drop_in_call_surface pins, and is lifted together with that test.
+        raise AssertionError("distance_measure %r: the single-image drop-in takes \"angle\" only; "
+                             "expectation_maximisation_batch also runs \"dotprod\"" % (distance_measure,))
     if sphere_image is None:
         raise TypeError("sphere_image is required (the reference dereferences it at vp_localisation.py:113)")
     scene = {"l": l, "lp": lp, "cnn_response": cnn_response, "sphere_image": sphere_image,
@@ -61,6 +69,44 @@ def expectation_maximisation(l, lp, cnn_response, num_iter=100, sphere_image=Non
     if status == 2:                           # np.vstack([]) at vp_localisation.py:165
         raise ValueError("need at least one array to concatenate")
     return res
+
+
+def expectation_maximisation_batch(ls, lps, cnn_responses, sphere_images, init_vps=None, device=0, num_iter=100,
+                                   do_merge=True, do_split=True, do_iterations=True, distance_measure="angle",
+                                   use_weights=True, wbias=1, num_init_vp=25, split_merge_freq=10, merge_thresh=1e-3,
+                                   outlier_thresh=1.96 ** 2, final_convergence=5e-3, s_thresh=1e-200, num_min_lines=3,
+                                   want_metric=True, return_distribution=True):
+    """expectation_maximisation (:168-450) for many images in one launch: one list entry per image, the keywords and
+    defaults of the reference for all of them, ``distance_measure`` "angle" or "dotprod" (:196-201; anything else raises
+    AssertionError as :203).  ``init_vps``: None, or one (K, 3) array per image with the same K.  Returns one result dict
+    per image with the reference's keys; every float64 ``l`` is normalised in place (:185-186).  An image without any
+    initial VP raises ValueError (:165) after all images have run."""
+    _em._measure(distance_measure)
+    ls, lps, cnn_responses, sphere_images = list(ls), list(lps), list(cnn_responses), list(sphere_images)
+    if not (len(ls) == len(lps) == len(cnn_responses) == len(sphere_images)) or \
+            (init_vps is not None and len(init_vps) != len(ls)):
+        raise ValueError("ls, lps, cnn_responses, sphere_images and init_vps must have one entry per image")
+    if any(s is None for s in sphere_images):
+        raise TypeError("sphere_image is required (the reference dereferences it at vp_localisation.py:113)")
+    if not ls:
+        return []
+    scenes = [{"l": l, "lp": lp, "cnn_response": c, "sphere_image": s, "init_vp": None if init_vps is None else init_vps[b]}
+              for b, (l, lp, c, s) in enumerate(zip(ls, lps, cnn_responses, sphere_images))]
+    results = _em.em_batch(scenes, device=device, want_metric=want_metric, want_distribution=return_distribution,
+                           num_iter=num_iter, do_merge=do_merge, do_split=do_split, do_iterations=do_iterations,
+                           distance_measure=distance_measure, use_weights=use_weights, wbias=wbias,
+                           num_init_vp=num_init_vp, split_merge_freq=split_merge_freq, merge_thresh=merge_thresh,
+                           outlier_thresh=outlier_thresh, final_convergence=final_convergence, s_thresh=s_thresh,
+                           num_min_lines=num_min_lines)
+    failed = False
+    for l, res in zip(ls, results):
+        failed = failed or res.pop("status") == 2
+        l_norm = res.pop("l")
+        if isinstance(l, np.ndarray) and l.dtype == np.float64:
+            l[...] = l_norm
+    if failed:
+        raise ValueError("need at least one array to concatenate")
+    return results
 
 
 # ---- line geometry -------------------------------------------------------------------------------------------------------
