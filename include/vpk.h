@@ -748,6 +748,41 @@ int vpk_horizon_batch(vpk_handle* h, int batch, int max_vp, const double* vp, co
                       const int32_t* num_vp, const int32_t* order, int maxbest, double theta_vmin, double theta_z,
                       double* out, int32_t* combo_out);
 
+/* ---- detector glue: the order of the best VPs and the conversion to pixels, batched (csrc/detect_device.hpp) -------- */
+/* replaces: np.argsort(counts)[::-1][:maxbest] -- calc_horizon.py:34-36 -- for a batch of images on the device, so that
+ * vpk_em_batch's outputs reach vpk_horizon_batch without a host round trip.
+ *   counts     B x max_vp fp64, num_vp  B int32 (clamped to 0..max_vp as vpk_horizon_batch clamps it): vpk_em_batch's outputs
+ *   order_out  B x maxbest int32: the first min(maxbest, M_b) entries are image b's VP indices by descending count, the
+ *              entries past that are 0
+ * The tie rule is part of the contract: among equal counts the HIGHER index comes first; a NaN count ranks above every
+ * number, and among NaNs the higher index comes first.  That is np.argsort(counts, kind="stable")[::-1], and what the
+ * reference's NumPy generation gives for up to 16 elements (there its argsort is an insertion sort).  Beyond that the
+ * reference's order among equal counts is a property of an unstable sort, so wherever counts tie this rule is the
+ * project's own.
+ * max_vp and maxbest are 1..64 and batch >= 0, else VPK_ERR_ARG before anything is launched; batch = 0 does nothing.
+ * One wave per image, one lane per VP: a lane's rank is the number of VPs that precede it.  Asynchronous on the handle's
+ * stream. */
+int vpk_vp_order_batch(vpk_handle* h, int batch, int max_vp, const double* counts, const int32_t* num_vp, int maxbest,
+                       int32_t* order_out);
+/* replaces: the pixel conversion of example.py:66-76 (horizon end points), the inverse of detect_lsd_lines'
+ * normalisation (evaluation.py:240-249), for the segments, the VPs and the horizon of a batch of images.  With
+ * scale = max(w, h):   x_px = x * scale / 2.0 + w / 2.0    y_px = -y * scale / 2.0 + h / 2.0
+ * evaluated left to right in fp64, each operation rounded on its own (no FMA): NumPy's bytes.
+ *   dims          [host] B x 2 int32: width, height of the detector image, as vpk_lsd_rows_to_lines takes it
+ *   line_offsets  [host] B+1 int64 prefix sums of the segment counts; lp  sum(N) x 4 fp64 normalised segments
+ *   vp / num_vp   B x max_vp x 3 fp64, B int32: vpk_em_batch's outputs (max_vp 1..64; num_vp clamped to 0..max_vp)
+ *   horizon       B x 15 fp64: vpk_horizon_batch's `out`
+ *   lp_px_out       sum(N) x 4 fp64, rows as in lp
+ *   vp_px_out       B x max_vp x 2 fp64: (v[0] / v[2], v[1] / v[2]) in pixels -- a VP at infinity gives the infinities
+ *                   and NaNs IEEE gives; rows at or past num_vp[b] are written as NaN
+ *   horizon_px_out  B x 2 x 2 fp64: hP1 and hP2 (x, y) in pixels
+ * Each output may be NULL (not written; its inputs are then not read and may be NULL).  A side below 1, decreasing
+ * offsets, batch < 0 and a missing input of a requested output: VPK_ERR_ARG, nothing is launched.  batch = 0 does
+ * nothing.  One thread per output row.  Asynchronous on the handle's stream. */
+int vpk_to_pixels_batch(vpk_handle* h, int batch, const int32_t* dims, const int64_t* line_offsets, const double* lp,
+                        int max_vp, const double* vp, const int32_t* num_vp, const double* horizon, double* lp_px_out,
+                        double* vp_px_out, double* horizon_px_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -75,6 +75,7 @@ EXPORTS = [
     "vpk_vp_line_counts_batch", "vpk_vp_split_batch", "vpk_vp_merge_batch",
     "vpk_estep_batch",
     "vpk_weight_matrix_batch", "vpk_mstep_batch", "vpk_init_vps_batch",
+    "vpk_vp_order_batch", "vpk_to_pixels_batch",
 ]
 
 _lib = None
@@ -176,6 +177,8 @@ def load():
     lib.vpk_weight_matrix_batch.argtypes = [c_void, ctypes.c_int] + [c_void] * 6 + [ctypes.c_double, c_void]
     lib.vpk_mstep_batch.argtypes = [c_void, ctypes.c_int] + [c_void] * 8 + [ctypes.c_double] * 2 + [c_void] * 6
     lib.vpk_init_vps_batch.argtypes = [c_void, ctypes.c_int, c_void, c_void, ctypes.c_int, ctypes.c_int] + [c_void] * 3
+    lib.vpk_vp_order_batch.argtypes = [c_void, ctypes.c_int, ctypes.c_int, c_void, c_void, ctypes.c_int, c_void]
+    lib.vpk_to_pixels_batch.argtypes = [c_void, ctypes.c_int, c_void, c_void, c_void, ctypes.c_int] + [c_void] * 6
     _lib = lib
     return lib
 

@@ -157,3 +157,41 @@ def calculate_horizon_batch(em_results, maxbest=10, theta_vmin=np.pi / 10., thet
         res.append((o[0:3].copy(), o[3:6].copy(), o[6:9].copy(), o[9:12].copy(), o[12:15].copy(),
                     c.astype(np.int64) if c[2] >= 0 else c[:2].astype(np.int64)))
     return res
+
+
+def vp_order_batch_device(rt, counts, num_vp, maxbest):
+    """np.argsort(counts)[::-1][:maxbest] (calc_horizon.py:34-36) for a batch on the device (vpk_vp_order_batch).
+    counts: B x max_vp fp64, num_vp: B int32 (device tensors, e.g. em.em_batch_device's).  Returns the device order,
+    B x maxbest int32, zero past min(maxbest, M_b).  Ties follow np.argsort(counts, kind="stable")[::-1]: among equal
+    counts the higher index first, NaN above every number (include/vpk.h).  Asynchronous on rt's stream."""
+    torch = rt.torch
+    batch, max_vp = int(counts.shape[0]), int(counts.shape[1])
+    if max_vp > 64 or maxbest > 64 or max_vp < 1 or maxbest < 1:
+        raise ValueError("vpk_vp_order_batch handles 1..64 VPs per image and a maxbest of 1..64")
+    with rt.on_stream():
+        order = torch.empty((batch, int(maxbest)), dtype=torch.int32, device=rt.tdev)
+        rt.check(rt.lib.vpk_vp_order_batch(rt.h, batch, max_vp, rt.ptr(counts), rt.ptr(num_vp), int(maxbest), rt.ptr(order)))
+    return order
+
+
+def horizon_batch_device(rt, vp, counts, num_vp, maxbest=10, theta_vmin=np.pi / 10., theta_z=np.pi / 4., order=None):
+    """calculate_horizon_and_ortho_vp for a batch that is already on the device: vp (B x max_vp x 3), counts (B x max_vp),
+    num_vp (B int32) as em.em_batch_device returns them.  ``order``: B x maxbest int32 device tensor, or None to compute it
+    on the device (vp_order_batch_device: the stable tie rule).  Then vpk_horizon_batch as calculate_horizon_batch calls it.
+    Returns {"out": B x 15 fp64 (hP1 | hP2 | zVP | hVP1 | hVP2), "combo": B x 3 int32, "order"} -- device tensors;
+    asynchronous on rt's stream."""
+    import ctypes
+    torch = rt.torch
+    batch, max_vp = int(vp.shape[0]), int(vp.shape[1])
+    if max_vp > 64 or maxbest > 64 or max_vp < 1 or maxbest < 1:
+        raise ValueError("vpk_horizon_batch handles 1..64 VPs per image and a maxbest of 1..64")
+    if order is None:
+        order = vp_order_batch_device(rt, counts, num_vp, maxbest)
+    with rt.on_stream():
+        out = torch.empty((batch, 15), dtype=torch.float64, device=rt.tdev)
+        combo = torch.empty((batch, 3), dtype=torch.int32, device=rt.tdev)
+        if batch:
+            rt.check(rt.lib.vpk_horizon_batch(rt.h, batch, max_vp, rt.ptr(vp), rt.ptr(counts), rt.ptr(num_vp), rt.ptr(order),
+                                              int(maxbest), ctypes.c_double(theta_vmin), ctypes.c_double(theta_z), rt.ptr(out),
+                                              rt.ptr(combo)))
+    return {"out": out, "combo": combo, "order": order}

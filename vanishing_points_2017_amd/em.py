@@ -127,6 +127,26 @@ def upload_batch(rt, scenes):
     return dev
 
 
+def host_result(host, l_norm, lo, hi, b):
+    """The reference-style result dict (vp_localisation.py:441-442 plus status / flags / l) of image b, whose lines are rows
+    lo..hi, from em_batch_device's outputs copied to the host (``host``: numpy arrays under the same keys, "metric" may be
+    None) and the normalised lines ``l_norm``."""
+    m, status = int(host["num_vp"][b]), int(host["status"][b])
+    res = {"status": status, "flags": int(host["flags"][b]) & 0xffffffff, "l": l_norm[lo:hi]}
+    if status == 0:
+        res.update({
+            "vp_assoc": host["vp_assoc"][lo:hi].copy(), "vp": host["vp"][b, :m].copy(),
+            "counts": host["counts"][b, :m].copy(),
+            "counts_weighted": host["counts_weighted"][b, :m].copy(), "count_id": None,
+            "decision_metric": None if host["metric"] is None else host["metric"][lo:hi, :m].T.copy(),
+            "iterations": int(host["iterations"][b]), "distribution": None,
+            "sigma": host["sigma"][b, :m].copy()})
+    else:   # vp_localisation.py:205-206
+        res.update({"vp_assoc": None, "vp": None, "counts": None, "count_id": None,
+                    "decision_metric": None, "iterations": 0})
+    return res
+
+
 def em_batch(scenes, device=0, want_metric=False, want_trace=False, want_distribution=False, **kwargs):
     """Host-in / host-out convenience: refine a list of images, return one reference-style
     result dict per image (keys as vp_localisation.py:441-442 plus status/flags/l).  'distribution' is the
@@ -152,23 +172,13 @@ def em_batch(scenes, device=0, want_metric=False, want_trace=False, want_distrib
         status = int(host["status"][b])
         if status == 3:         # VPK_EM_NO_SLOT (include/vpk.h): the image was not refined -- an error, not a result
             raise _lib.VpkError("vpk_em_batch: image %d found no working-set slot (time-sliced launch)" % b)
-        res = {"status": status, "flags": int(host["flags"][b]) & 0xffffffff, "l": l_norm[lo:hi]}
+        res = host_result(host, l_norm, lo, hi, b)
         if status == 0:
-            res.update({
-                "vp_assoc": host["vp_assoc"][lo:hi].copy(), "vp": host["vp"][b, :m].copy(),
-                "counts": host["counts"][b, :m].copy(),
-                "counts_weighted": host["counts_weighted"][b, :m].copy(), "count_id": None,
-                "decision_metric": None if host["metric"] is None else host["metric"][lo:hi, :m].T.copy(),
-                "iterations": int(host["iterations"][b]), "distribution": None,
-                "sigma": host["sigma"][b, :m].copy()})
             if dist is not None:                        # probability_functions.py:120, shapes as the reference's
                 from .probability_functions import PDF
                 res["distribution"] = PDF(v=dist["p_v"][b, :m].copy(), lv=dist["p_lv"][lo:hi, :m].copy(),
                                           vl=dist["p_vl"][lo:hi, :m].T.copy(), l=dist["p_l"][lo:hi].copy(),
                                           lvsq=dist["lvsq"][lo:hi, :m].copy(), angles=dist["angles"][b, :m].copy())
-        else:   # vp_localisation.py:205-206
-            res.update({"vp_assoc": None, "vp": None, "counts": None, "count_id": None,
-                        "decision_metric": None, "iterations": 0})
         if host["trace"] is not None:
             res["trace"] = host["trace"][b]
         results.append(res)

@@ -5,7 +5,8 @@ With --source_folder DIR (the reference uses assets/examples, example.py:26) the
 reference's three calls -- create_data_pickles(cnn_input_size=500, target_size=640), run_cnn, run_em (example.py:36-39)
 -- with this package's front end (frontend.py), a random-init CNN unless trained weights are configured (config.py),
 and the horizon end points are printed in pixel coordinates like example.py:66-76.  Without it one seeded synthetic
-scene (configs[0]: N = 800) goes through raster, CNN and EM."""
+scene (configs[0]: N = 800) goes through raster, CNN and EM.  --detector sends the images of --source_folder through
+detector.Detector instead: one GPU batch, the same printed lines, no pickles."""
 import argparse
 
 import numpy as np
@@ -75,6 +76,42 @@ def run_folder(args):
     return dataset
 
 
+def run_folder_detector(args):
+    """--detector: the images of --source_folder through detector.Detector.detect -- one batch on the GPU, no pickles --
+    with run_folder's settings (cnn_input_size 500, target_size 640, maxbest 20) and its printed lines.  Returns detect's
+    list, one result per image file."""
+    import glob
+    import os
+    from . import config, frontend
+    from .detector import Detector
+    image_files = sorted(sum((glob.glob("%s/*.%s" % (args.source_folder, ext)) for ext in ("jpg", "png", "pgm")), []))
+    if all(os.path.isfile(f) for f in (config.cnn_weights_path, config.cnn_mean_path)):
+        net = evaluation.init_caffe(config.cnn_config_path, config.cnn_weights_path, args.gpu,
+                                    mean_file=config.cnn_mean_path)._net
+    else:
+        print("no trained weights at %s: random-init AlexNet-500" % config.cnn_weights_path)
+        net = cnn.Net(cnn.synthetic_weights(0), cnn.synthetic_mean(0), device=args.gpu)
+    det = Detector(net, device=args.gpu, target_size=640, cnn_input_size=500, maxbest=20, theta_vmin=np.pi / 10.,
+                   range_policy=args.cnn_range, distance_measure='angle', use_weights=True, do_split=True, do_merge=True)
+    results = det.detect([frontend.imread(f) for f in image_files])
+    for image_file, r in zip(image_files, results):
+        height, width = r['lines']['image_shape'][:2]
+        print(image_file, "%d x %d, %d line segments" % (width, height, r['lines']['line_segments'].shape[0]))
+        res = r['EM_result']
+        datum = {'lines': r['lines'], 'EM_result': res}
+        if res is None:
+            print("  no vanishing points")
+            if args.save_overlays:
+                save_file_overlay(args.save_overlays, image_file, datum, None, args.gpu)
+            continue
+        hp1, hp2 = r['horizon_px']
+        print("  VPs: %d, iterations: %d, horizon: (%.1f, %.1f) - (%.1f, %.1f)" % (
+            res['vp'].shape[0], res['iterations'], hp1[0], hp1[1], hp2[0], hp2[1]))
+        if args.save_overlays:
+            save_file_overlay(args.save_overlays, image_file, datum, (hp1, hp2), args.gpu)
+    return results
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description='')
     p.add_argument('--gpu', default=0, type=int, help='GPU ID to use')
@@ -90,9 +127,13 @@ def main(argv=None):
     p.add_argument('--lsd', choices=['host', 'gpu', 'gpu-frontend'], default='host',
                    help='line segment detector of --source_folder: per image on the host, all images in one GPU batch, '
                         'or the whole front end after decoding (resize, grey, detector, lines, raster) on the GPU')
+    p.add_argument('--detector', dest='detector', action='store_true',
+                   help='with --source_folder: all images through detector.Detector in one GPU batch, without pickles')
     args = p.parse_args(argv)
+    if args.detector and not args.source_folder:
+        p.error("--detector needs --source_folder")
     if args.source_folder:
-        return run_folder(args)
+        return run_folder_detector(args) if args.detector else run_folder(args)
     sc = synth.make_scene(args.seed, args.lines, 3, aspect_h=0.667, raster=None)
     datum = {'lines': {'lines': sc["l"], 'line_segments': sc["lp"], 'image_shape': sc["image_shape"]},
              'sphere_image': evaluation.get_sphere_image(sc["l"], size=500, alpha=0.1)}
