@@ -783,6 +783,35 @@ int vpk_to_pixels_batch(vpk_handle* h, int batch, const int32_t* dims, const int
                         int max_vp, const double* vp, const int32_t* num_vp, const double* horizon, double* lp_px_out,
                         double* vp_px_out, double* horizon_px_out);
 
+/* ---- scoring: horizon errors against ground truth and their AUC, batched (csrc/score_device.hpp) -------------------- */
+/* replaces: the error of one image -- benchmark.py:245-253 -- for a batch:
+ *   thP1 = np.cross(trueHorizon, [1, 0, 1]);  thP2 = np.cross(trueHorizon, [-1, 0, 1]);  thP /= thP[2]       (:248-251)
+ *   max_error = np.maximum(|hP1[1] - thP1[1]|, |hP2[1] - thP2[1]|) / 2 * scale * 1.0 / imageHeight            (:253)
+ * with scale = max(w, h) (:137).  The value is NumPy's byte for byte: the cross products are written out as NumPy
+ * evaluates a 3-vector cross product (each product and each difference rounds on its own, no FMA), the rest runs left to
+ * right in fp64, and maximum hands a NaN on.
+ *   horizon       B x 15 fp64: vpk_horizon_batch's `out` (hP1 at 0..2, hP2 at 3..5)
+ *   true_horizon  B x 3 fp64: the ground-truth horizon line in the normalised frame
+ *   dims          [host] B x 2 int32: width, height of the image file, as vpk_to_pixels_batch takes it
+ *   err_out       B fp64
+ * batch < 0, a null buffer and a side below 1: VPK_ERR_ARG, nothing is launched.  batch = 0 does nothing.  One thread per
+ * image.  Asynchronous on the handle's stream. */
+int vpk_horizon_error_batch(vpk_handle* h, int batch, const double* horizon, const double* true_horizon, const int32_t* dims,
+                            double* err_out);
+/* replaces: auc.calc_auc -- auc.py:5-37, called at benchmark.py:264 -- on a device vector of n errors.
+ *   sorted_out  n fp64: the errors in np.sort's order, ascending with NaN last (must not be `err`)
+ *   auc_out     1 fp64 (device): the area under (err[i], (i + 1) / n) up to `cutoff`, divided by the cutoff
+ * A NaN error counts in the fractions and never falls under the cutoff.  `mid` is auc.py:20-28's: strict < on both sides
+ * of the cutoff, the last crossing wins.  The tail point (cutoff, 1 or mid) follows np.argsort(kind="stable"): a data
+ * point whose error equals the cutoff comes before it.  (Beyond 16 points the reference's own argsort is unstable, so
+ * there this rule is the project's.)  The order comes from a rank by counting -- thread i counts the errors that precede
+ * error i, equal errors told apart by index -- and the trapezoid sum from ONE workgroup in a fixed order, without
+ * floating-point atomics: the same input gives the same bits on every run.  The sum's order is not np.trapz's pairwise one:
+ * the two agree within 2 (n + 4) 2^-53.
+ * n < 1: VPK_ERR_ARG (the reference indexes plot_points[-1]); n > 65536: VPK_ERR_LIMIT; a null buffer: VPK_ERR_ARG;
+ * nothing is launched.  Asynchronous on the handle's stream. */
+int vpk_auc(vpk_handle* h, int n, const double* err, double cutoff, double* sorted_out, double* auc_out);
+
 #ifdef __cplusplus
 }
 #endif

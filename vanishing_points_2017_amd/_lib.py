@@ -76,6 +76,7 @@ EXPORTS = [
     "vpk_estep_batch",
     "vpk_weight_matrix_batch", "vpk_mstep_batch", "vpk_init_vps_batch",
     "vpk_vp_order_batch", "vpk_to_pixels_batch",
+    "vpk_horizon_error_batch", "vpk_auc",
 ]
 
 _lib = None
@@ -179,6 +180,8 @@ def load():
     lib.vpk_init_vps_batch.argtypes = [c_void, ctypes.c_int, c_void, c_void, ctypes.c_int, ctypes.c_int] + [c_void] * 3
     lib.vpk_vp_order_batch.argtypes = [c_void, ctypes.c_int, ctypes.c_int, c_void, c_void, ctypes.c_int, c_void]
     lib.vpk_to_pixels_batch.argtypes = [c_void, ctypes.c_int, c_void, c_void, c_void, ctypes.c_int] + [c_void] * 6
+    lib.vpk_horizon_error_batch.argtypes = [c_void, ctypes.c_int] + [c_void] * 4
+    lib.vpk_auc.argtypes = [c_void, ctypes.c_int, c_void, ctypes.c_double, c_void, c_void]
     _lib = lib
     return lib
 

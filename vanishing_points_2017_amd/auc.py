@@ -21,3 +21,20 @@ def calc_auc(error_array, cutoff=0.25):
     sel = pts[:, 0] <= cutoff
     auc = _trapezoid(pts[sel, 1], pts[sel, 0])    # sklearn.metrics.auc == trapezoid rule (auc.py:33)
     return auc / cutoff, pts
+
+
+def calc_auc_device(rt, err, cutoff=0.25):
+    """calc_auc on a device vector of errors (vpk_auc): returns (auc, sorted_errors) -- the AUC as a Python float, the
+    errors in np.sort's order (NaN last) as a device tensor.  Ties follow np.argsort(kind="stable") (include/vpk.h).
+    1 <= n <= 65536.  The call waits for the stream only to hand back the one number."""
+    torch = rt.torch
+    if err.dtype != torch.float64 or err.dim() != 1:
+        raise ValueError("calc_auc_device expects a one-dimensional float64 device tensor")
+    n = int(err.shape[0])
+    with rt.on_stream():
+        err = err.contiguous()
+        srt = torch.empty((max(n, 1),), dtype=torch.float64, device=rt.tdev)[:n]
+        out = torch.empty((1,), dtype=torch.float64, device=rt.tdev)
+        rt.check(rt.lib.vpk_auc(rt.h, n, rt.ptr(err), float(cutoff), rt.ptr(srt), rt.ptr(out)))
+        auc = float(out.cpu()[0])
+    return auc, srt

@@ -30,6 +30,7 @@ UNITS = {
     "vpk_raster.hip": ["-ffp-contract=off"],   # the curve samples must round like NumPy's separate ufunc calls
     "vpk_horizon.hip": ["-ffp-contract=off"],
     "vpk_detect.hip": ["-ffp-contract=off"],   # the pixel conversion rounds like NumPy's separate ufunc calls (detect_device.hpp)
+    "vpk_score.hip": ["-ffp-contract=off"],    # the horizon error and the AUC round like NumPy's separate ufunc calls (score_device.hpp)
     "vpk_pipeline.hip": [],
     "vpk_lsd.cpp": ["-ffp-contract=off"],      # host code: the front end's line segment detector
     "vpk_lsd_gpu.hip": ["-ffp-contract=off"],  # the same detector batched on the GPU: the host's roundings (lsd_device.hpp)

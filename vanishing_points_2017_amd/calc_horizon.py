@@ -195,3 +195,23 @@ def horizon_batch_device(rt, vp, counts, num_vp, maxbest=10, theta_vmin=np.pi / 
                                               int(maxbest), ctypes.c_double(theta_vmin), ctypes.c_double(theta_z), rt.ptr(out),
                                               rt.ptr(combo)))
     return {"out": out, "combo": combo, "order": order}
+
+
+def horizon_error_batch_device(rt, horizon, true_horizon, dims):
+    """horizon_error (benchmark.py:245-253) for a batch on the device (vpk_horizon_error_batch): NumPy's bytes.
+    horizon: B x 15 fp64 device tensor (horizon_batch_device's "out": hP1 at 0..2, hP2 at 3..5); true_horizon: B x 3 fp64
+    device tensor; dims: B x 2 (width, height) of the image files, on the host.  Returns the B errors as a device tensor;
+    asynchronous on rt's stream."""
+    import ctypes
+    torch = rt.torch
+    batch = int(horizon.shape[0])
+    dims = np.ascontiguousarray(dims, dtype=np.int32).reshape(batch, 2)
+    if tuple(horizon.shape) != (batch, 15) or tuple(true_horizon.shape) != (batch, 3) or \
+            horizon.dtype != torch.float64 or true_horizon.dtype != torch.float64:
+        raise ValueError("horizon_error_batch_device expects horizon B x 15 and true_horizon B x 3, both float64")
+    with rt.on_stream():
+        horizon, true_horizon = horizon.contiguous(), true_horizon.contiguous()
+        err = torch.empty((batch,), dtype=torch.float64, device=rt.tdev)
+        rt.check(rt.lib.vpk_horizon_error_batch(rt.h, batch, rt.ptr(horizon), rt.ptr(true_horizon),
+                                                dims.ctypes.data_as(ctypes.c_void_p), rt.ptr(err)))
+    return err

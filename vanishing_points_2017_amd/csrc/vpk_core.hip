@@ -110,7 +110,7 @@ int vpk_destroy(vpk_handle* h) {
     if (h->vpset_ws) (void)hipFree(h->vpset_ws);
     if (h->emstep_ws) (void)hipFree(h->emstep_ws);
     for (vpk_staged* s : {&h->fe_prep, &h->fe_rows, &h->lines_hdr, &h->overlay_hdr, &h->vpset_hdr, &h->estep_hdr, &h->emstep_hdr,
-                          &h->detect_hdr}) {
+                          &h->detect_hdr, &h->score_hdr}) {
         if (s->dev) (void)hipFree(s->dev);
         if (s->host) (void)hipHostFree(s->host);
         if (s->ev) (void)hipEventDestroy(s->ev);

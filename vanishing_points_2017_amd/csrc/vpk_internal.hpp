@@ -110,6 +110,7 @@ struct vpk_handle {
     size_t emstep_ws_bytes = 0;
     bool emstep_ready = false;       // dynamic-LDS attribute set on the kernel
     vpk_staged detect_hdr;           // vpk_to_pixels_batch (vpk_detect.hip): line offsets + image sizes
+    vpk_staged score_hdr;            // vpk_horizon_error_batch (vpk_score.hip): image sizes
 };
 
 // the LDS budget vpk_em_batch launches with under the handle's vpk_em_set_lds_panel setting (vpk_em.hip: em_mode): the

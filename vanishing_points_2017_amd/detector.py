@@ -163,7 +163,11 @@ class Detector(object):
           lines             create_data_dict_single's `lines` datum without the image: image_shape, line_segments, lines
         Unlike evaluation.run_em_batch no exception is raised mid-batch for an image without an initial VP: the image gets
         EM_result None and its status says why."""
-        d = self.detect_device(images)
+        return self.host_results(self.detect_device(images))
+
+    @staticmethod
+    def host_results(d):
+        """detect's list from detect_device's dict."""
         offs = d["offsets"]
         keys = ("l", "lp", "vp", "sigma", "counts", "counts_weighted", "num_vp", "vp_assoc", "iterations", "status", "flags",
                 "l_norm", "horizon", "combo", "lp_px", "vp_px", "horizon_px")
