@@ -288,7 +288,13 @@ int vpk_cnn_mean_layer_ms(vpk_handle* h, float ms[13], int* passes);
  * batch has no line, l may be NULL.  Workspace (kept on the handle, grown on demand), per line of the largest chunk of
  * <= 49 152 lines: ~38 KB of outline scratch + 64 x size bytes of row table + 16 KB of coverage pool (~86 KB per line at
  * size 500: 4.2 GB for a full chunk; the pool is never smaller than 8 x size x (size + 2) bytes and must stay below
- * 4 GiB -- an image of more than ~262 000 lines is refused with VPK_ERR_LIMIT). */
+ * 4 GiB).  An image is never split over chunks, so that bound limits the lines of ONE image: (N + 4) x 16 KB < 4 GiB, i.e.
+ * at most 262 139 lines; in `alternative` mode (below) the pool is size x (size + 2) bytes per line and chunks hold at most
+ * min(49 152, 3 GiB / (size x (size + 2))) lines, so an image has at most floor((2^32 - 1) / (size x (size + 2))) - 4
+ * lines (17 107 at size 500, 4 084 at size 1024).  One line more: VPK_ERR_LIMIT before anything is allocated or launched,
+ * the message names the largest count.
+ * VPK_ERR_ARG, likewise before anything is done: a null handle / offsets / out, batch < 1, size outside 8..1024, alpha
+ * outside 0..1 (NaN included), offsets that decrease, l == NULL although the batch has lines. */
 int vpk_sphere_raster(vpk_handle* h, const double* l, const int64_t* offsets, int batch, int size,
                       double alpha, uint8_t* out);
 /* replaces: the `alternative` keyword of sphere_line_plot (sphere_mapping.py:58-59; no caller in the reference passes it):

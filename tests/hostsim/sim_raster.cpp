@@ -51,46 +51,54 @@ void draw_polygon(const V2* v, int n, unsigned grey, unsigned a8, int size, std:
     }
 }
 
+// the samples of one line through the simplifier, as outline_kernel's sequential machine feeds them: `sub(n)` is called at the
+// end of every sub-path that kept n >= 2 points (in simp[0 .. n)); returns the simplifier's overflow flag
+template <class F>
+unsigned line_subpaths(const double* l, int size, int alt, std::vector<V2>& simp, F sub) {
+    const int ns = 10000;
+    const double lo_a = -PI_D / 2, hi_a = PI_D / 2, step = (hi_a - lo_a) / (ns - 1);
+    const double la = l[0], lb = l[1], lc = l[2];
+    Simplifier sm;
+    sm.init(simp.data(), MAXS);
+    auto flush = [&]() {
+        sm.end();
+        if (sm.n >= 2) sub(sm.n);
+        sm.n = 0;
+    };
+    constexpr int OG = 8;                                     // groups, as outline_kernel feeds them
+    for (int i0 = 0; i0 < ns; i0 += OG) {
+        double xs[OG], ys[OG];
+        for (int u = 0; u < OG; ++u) {
+            const int i = i0 + u < ns ? i0 + u : ns - 1;
+            const double al = (i == ns - 1) ? hi_a : lo_a + i * step;
+            double be = alt ? -atan(-lc / (cos(al) * la + sin(al) * lb))      // sphere_mapping.py:59
+                            : -atan((-la * sin(al) - lc * cos(al)) / lb);     // :61
+            be *= -1;
+            xs[u] = (al - lo_a) / (hi_a - lo_a) * size;
+            ys[u] = size - (be - lo_a) / (hi_a - lo_a) * size;
+        }
+        feed_group<OG>(sm, xs, ys, ns - i0, flush);
+    }
+    if (sm.have) flush();
+    return sm.overflow;
+}
+
 }  // namespace
 
 extern "C" int sim_raster(const double* l, int nlines, int size, double alpha, int alt, unsigned char* out) {
-    const int ns = 10000;
-    const double lo_a = -PI_D / 2, hi_a = PI_D / 2, step = (hi_a - lo_a) / (ns - 1);
     std::vector<V2> simp(MAXS), verts(MAXV);
     std::vector<int> cover((size_t)size * (size + 2), 0), area((size_t)size * (size + 2), 0), rowmin(size, 0x7fffffff), rowmax(size, -1);
     memset(out, 0, (size_t)size * size);
     unsigned flags = 0;
     const unsigned a8 = (unsigned)(alpha * 255.0 + 0.5);
     for (int g = 0; g < nlines; ++g) {
-        const double la = l[3 * g], lb = l[3 * g + 1], lc = l[3 * g + 2];
-        Simplifier sm;
-        sm.init(simp.data(), MAXS);
-        auto flush = [&]() {
-            sm.end();
-            if (sm.n >= 2) {
-                Outline o;
-                o.v = verts.data(); o.n = 0; o.cap = MAXV; o.flags = &flags;
-                stroke_outline(simp.data(), sm.n, 100.0 / 72.0, o);
-                if (o.n >= 3) draw_polygon(verts.data(), o.n, 255u, a8, size, cover, area, rowmin, rowmax, out);
-            }
-            sm.n = 0;
-        };
-        constexpr int OG = 8;                                     // groups, as outline_kernel feeds them
-        for (int i0 = 0; i0 < ns; i0 += OG) {
-            double xs[OG], ys[OG];
-            for (int u = 0; u < OG; ++u) {
-                const int i = i0 + u < ns ? i0 + u : ns - 1;
-                const double al = (i == ns - 1) ? hi_a : lo_a + i * step;
-                double be = alt ? -atan(-lc / (cos(al) * la + sin(al) * lb))      // sphere_mapping.py:59
-                                : -atan((-la * sin(al) - lc * cos(al)) / lb);     // :61
-                be *= -1;
-                xs[u] = (al - lo_a) / (hi_a - lo_a) * size;
-                ys[u] = size - (be - lo_a) / (hi_a - lo_a) * size;
-            }
-            feed_group<OG>(sm, xs, ys, ns - i0, flush);
-        }
-        if (sm.have) flush();
-        flags |= sm.overflow;
+        const unsigned overflow = line_subpaths(l + 3 * g, size, alt, simp, [&](int n) {
+            Outline o;
+            o.v = verts.data(); o.n = 0; o.cap = MAXV; o.flags = &flags;
+            stroke_outline(simp.data(), n, 100.0 / 72.0, o);
+            if (o.n >= 3) draw_polygon(verts.data(), o.n, 255u, a8, size, cover, area, rowmin, rowmax, out);
+        });
+        flags |= overflow;
     }
     const double s = (double)size, w_spine = 0.8 * 100.0 / 72.0;
     for (int side = 0; side < 4; ++side) {
@@ -126,4 +134,20 @@ extern "C" int sim_edge_shares(double x1, double y1, double x2, double y2, int s
     int bad = 0;
     for (size_t i = 0; i < c1.size(); ++i) bad += (c1[i] != c2[i]) || (a1[i] != a2[i]);
     return bad;
+}
+
+// the outline polygons the product's simplifier and stroker make of ONE line: the vertex count of every sub-path that is
+// drawn (>= 3 vertices), in path order, into counts[0 .. max); returns how many there are (the kernels keep up to MAXSUB and
+// hold a polygon's vertices in LDS up to a limit: the tests look for lines on both sides of it)
+extern "C" int sim_outline_counts(const double* l, int size, int alt, int* counts, int max) {
+    std::vector<V2> simp(MAXS), verts(MAXV);
+    unsigned flags = 0;
+    int np = 0;
+    line_subpaths(l, size, alt, simp, [&](int n) {
+        Outline o;
+        o.v = verts.data(); o.n = 0; o.cap = MAXV; o.flags = &flags;
+        stroke_outline(simp.data(), n, 100.0 / 72.0, o);
+        if (o.n >= 3) { if (np < max) counts[np] = o.n; ++np; }
+    });
+    return np;
 }

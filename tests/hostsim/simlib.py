@@ -218,6 +218,8 @@ def raster_lib():
     _raster_lib.sim_raster.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                        ctypes.c_int, ctypes.POINTER(ctypes.c_uint8)]
     _raster_lib.sim_edge_shares.argtypes = [ctypes.c_double] * 4 + [ctypes.c_int, ctypes.c_int]
+    _raster_lib.sim_outline_counts.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int,
+                                               ctypes.POINTER(ctypes.c_int), ctypes.c_int]
     return _raster_lib
 
 
@@ -228,6 +230,14 @@ def sim_raster(lines, size=250, alpha=0.1, alternative=False):
     flags = raster_lib().sim_raster(_p(l, ctypes.c_double), l.shape[0], size, float(alpha), int(bool(alternative)),
                                     _p(out, ctypes.c_uint8))
     return out, flags
+
+
+def sim_outline_counts(line, size=500, alternative=False):
+    """Vertices of the outline polygon of every drawn sub-path of one line, as the product's simplifier and stroker make them."""
+    l = np.ascontiguousarray(line, dtype=np.float64).reshape(3)
+    counts = np.zeros(16, dtype=np.int32)
+    n = raster_lib().sim_outline_counts(_p(l, ctypes.c_double), size, int(bool(alternative)), _p(counts, ctypes.c_int), 16)
+    return counts[:n].tolist()
 
 
 def sim_edge_shares(x1, y1, x2, y2, size, k):

@@ -2,6 +2,11 @@
 against the REFERENCE's own rasters stored in tests/golden/*.npz (sphere_mapping.sphere_line_plot run in the build
 container by oracle/make_golden.py) and against the CPU restatement oracle/agg_raster.py.
 
+This file: the PRODUCT PATHS against the reference (goldens, the `alternative` goldens, what the raster feeds, the two
+simplifiers against each other).  The kernels' orchestration at its edges -- batches of more than one chunk, the mode switch,
+cached offsets, broken paths, outlines around the LDS vertex copy, canvas sizes off the granules, the blender's table
+switch, the C entry's refusals -- is tests/test_gpu_raster_edges.py, against the restatement.
+
 Bar: the raster is integer work -- bit-exact.  Every default golden must be reproduced pixel for pixel; downstream,
 find_initial_vps on the GPU raster must give the golden's initial VPs (1e-13) and the EM started from the lines alone
 (raster made here) the reference's assignments bit for bit."""

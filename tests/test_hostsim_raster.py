@@ -1,8 +1,9 @@
 """The rasteriser's PRODUCT arithmetic (csrc/raster_device.hpp: simplifier, stroker, cell walker with its clip box and its
 closed-form restart of AGG's row DDA, calculate_alpha, blender) compiled for the host by tests/hostsim/sim_raster.cpp and run
 serially -- the CPU suite's check of the code the GPU kernels are made of (the kernels' own orchestration: LDS pools, row
-bands, atomics, the blend order across workgroups, is what tests/test_gpu_raster.py covers).  Bit-exact against the
-reference's own rasters (tests/golden) and the restatement oracle/agg_raster.py."""
+bands, atomics, the blend order across workgroups, is what tests/test_gpu_raster.py and tests/test_gpu_raster_edges.py
+cover; the latter's inputs run through the host build at the end of this file).  Bit-exact against the reference's own
+rasters (tests/golden) and the restatement oracle/agg_raster.py."""
 import os
 import sys
 
@@ -64,3 +65,48 @@ def test_product_arithmetic_on_the_alternative_curve():
     for k in "abc":
         got, flags = simlib.sim_raster(g["l_" + k], 500, 0.1, alternative=True)
         assert flags == 0 and np.array_equal(got, g["raster_" + k]), k
+
+
+# ---- the inputs of tests/test_gpu_raster_edges.py: "product arithmetic == oracle" on record in the CPU suite, so that a GPU
+# ---- mismatch on them points at the kernels' orchestration
+@pytest.mark.parametrize("alternative", [False, True])
+@pytest.mark.parametrize("size", [500, 64])
+def test_broken_paths_against_the_restatement(size, alternative):
+    """Lines whose samples are finite / NaN in turns (two sub-paths, a NaN half before or after the finite one, nothing to
+    draw) between ordinary crossing lines."""
+    from test_gpu_raster_edges import TWO_RUNS, BROKEN, broken_mix, want
+    mix = broken_mix()
+    for k in TWO_RUNS[alternative]:
+        assert len(simlib.sim_outline_counts(BROKEN[k], size, alternative)) == 2, k      # (two polygons in the product too)
+    got, flags = simlib.sim_raster(mix, size, 0.1, alternative=alternative)
+    assert flags == 0 and np.array_equal(got, want(mix, size, 0.1, alternative))
+
+
+def test_outlines_around_256_vertices_against_the_restatement():
+    """The four 1024-px lines whose outlines have 254 ... 260 vertices: the product's stroker makes polygons of the same
+    size as the oracle's (the GPU test picks its lines by that count), and the same pixels."""
+    from test_gpu_raster_edges import LVERT_LINES, want
+    for n, line in LVERT_LINES.items():
+        line = np.array(line)
+        assert len(agg_raster.stroke_outline(agg_raster.simplify(*agg_raster.curve_pixels(line, 1024)), 100 / 72)) == n
+        assert simlib.sim_outline_counts(line, 1024) == [n]
+        got, flags = simlib.sim_raster(line, 1024, 0.1)
+        assert flags == 0 and np.array_equal(got, want(line, 1024))
+
+
+@pytest.mark.parametrize("size", [8, 9, 33])
+def test_smallest_canvases_against_the_restatement(size):
+    from test_gpu_raster_edges import scene_lines, want
+    a = scene_lines()
+    got, flags = simlib.sim_raster(a[:10], size, 0.1)
+    assert flags == 0 and np.array_equal(got, want(a[:10], size))
+
+
+@pytest.mark.parametrize("alpha,a8", [(0.0, 0), (0.002, 1), (0.247, 63), (0.25, 64), (1.0, 255)])
+def test_alphas_at_the_blenders_edges_against_the_restatement(alpha, a8):
+    from test_gpu_raster_edges import scene_lines, want
+    assert int(alpha * 255 + 0.5) == a8
+    a = scene_lines()
+    got, flags = simlib.sim_raster(a[:20], 64, alpha)
+    assert flags == 0 and np.array_equal(got, want(a[:20], 64, alpha))
+    assert got.max() == {0: 0, 1: 0, 63: 212, 64: 213, 255: 255}[a8]

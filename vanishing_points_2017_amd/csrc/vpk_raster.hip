@@ -809,10 +809,11 @@ int vpk_sphere_raster(vpk_handle* h, const double* l, const int64_t* offsets, in
     // ranges of ONE line can span most of the canvas (see polygon_coverage), and a call may consist of one line
     const size_t alpha_bytes = std::max<size_t>(nl * (alt ? (size_t)size * (size + 2) : (size_t)16384), (size_t)8 * size * (size + 2));
     if (alpha_bytes >= (1ull << 32)) {                    // RowEnt::off is 32 bits (a chunk of 49 152 lines needs 0.8 GB)
-        // one image is one chunk at least; the pool per line is 16 KB, or a whole canvas in `alternative` mode
+        // one image is one chunk at least; the pool per line is 16 KB, or a whole canvas in `alternative` mode.  The largest
+        // count that passes: (lines + 4) * per_line <= 2^32 - 1 (262 139 lines at 16 KB: 2^32 is a multiple of it)
         char msg[160];
         snprintf(msg, sizeof msg, "vpk_sphere_raster: one image has more than %lld lines (the 4 GiB coverage pool at %s per line)",
-                 (long long)((1ull << 32) / (alt ? (size_t)size * (size + 2) : (size_t)16384)) - 4,
+                 (long long)(((1ull << 32) - 1) / (alt ? (size_t)size * (size + 2) : (size_t)16384)) - 4,
                  alt ? "one canvas (alternative mode)" : "16 KB");
         return vpk_fail(h, VPK_ERR_LIMIT, msg);
     }
