@@ -105,7 +105,9 @@ int vpk_em_set_workgroups(vpk_handle* h, int max_workgroups);
  * (tests/test_gpu_em.py): the switch exists for that test and for A/B timing.  Mode 1 also selects the earlier forms of the
  * other phases that have been rebuilt with the same arithmetic since (round 6: the E-step's one thread per line, the serial
  * VP compaction, the row-by-row pair pass of calc_lsim for images of 512 lines and more, the M-step's four loads in flight
- * there; vpk_pairwise honours it too) -- the same test therefore pins those rebuilds bit for bit. */
+ * there; vpk_pairwise honours it too) -- the same test therefore pins those rebuilds bit for bit.  Likewise the E-step's line
+ * part: with the operand panel in LDS the default evaluates the exp and the division to p_vl only for the terms that do not
+ * underflow, mode 1 for every (line, VP) pair (tests/test_gpu_em_estep_zeros.py). */
 int vpk_em_set_smoother(vpk_handle* h, int mode);
 /* LDS the EM workgroup may plan with for its weight_matrix operand panel and the split's cluster matrix, in doubles;
  * 0 (default) = everything a CU has beside the workgroup's state (~18 800).  A smaller budget sends images down the

@@ -81,6 +81,141 @@ template <int MEASURE> VPK_DEV double estep_pair(const EstepLine& g, const Share
 }
 
 // ---------------------------------------------------------------------------------------------
+// the line part without the responsibilities that are zero (the panel forms: plan 1 and plan 2)
+// ---------------------------------------------------------------------------------------------
+// Four in five of the terms p_lv p_v = exp(a) k2 pv, a = -(lvsq / 2s), are +0.0 because exp underflows (em_smooth.hpp counts the
+// same zeros among the smoother's operands), and so are their responsibilities term / p_l: two divisions and an exp per pair, some 70
+// instructions, that end in a value known beforehand.  The lanes of a wave run in lockstep and nearly every VP has SOME line of the
+// wave that needs its exp, so a test inside the dense VP loop saves nothing.  The panel forms therefore run three passes:
+//   A  (dense)   lvsq for every VP of the lane's range, parked in the line's panel slot; a VP is KEPT -- a bit of a 64-bit mask
+//                (MAXM = 64) -- unless lvsq > (2 s) ESTEP_UNDERFLOW_BOUND holds, which implies a < -746.0 (below) and costs a
+//                product where a costs a division.  A NaN lvsq is kept, and so is the narrow band in which a < -746.0 holds and
+//                the cheaper test does not see it: those take the dense form's own arithmetic in pass B;
+//   B  (sparse)  the kept VPs only, in ascending order: a and the term, with exp_underflow's value and the dense form's grouping,
+//                parked in the slot and added to p_l in that order.  The loop lasts as long as the lane of the wave with most kept
+//                VPs;
+//   C            term / p_l and its product with lweight for the kept VPs; for all others 0.0 / p_l and (0.0 / p_l) * lweight,
+//                evaluated once per line.
+// SAME BITS, BY CONSTRUCTION.  The dense form's term of a VP that is not kept is (0.0 * k2[m]) * pv[m], exp_underflow returning
+// 0.0 below -746.  That is +0.0 exactly when k2[m] and pv[m] are finite and of equal sign (estep_zero_safe: one wave-uniform mask
+// per call); a VP outside that mask is kept by EVERY lane and takes the dense form's arithmetic, whatever its lvsq.  Then
+//   * p_l: the dense chain starts at +0.0 and a sum of two doubles is -0.0 only if both are, so the running sum is never -0.0, and
+//     x + (+0.0) = x for every other x, NaN and infinities included: leaving the +0.0 terms out leaves every partial sum as it was,
+//     also the sum a lane takes over from its neighbour (T > 1).
+//   * p_vl and the panel: the dense form divides the parked +0.0 by p_l and multiplies by lweight; pass C evaluates that very
+//     expression on those very operands, once.
+// The cases that would break it if handled carelessly:
+//   * a NaN column (a VP at infinity under "angle": vx, vy are inf or NaN, lvsq NaN): lvsq > bound is false, kept.
+//   * a NaN or infinite pv (a VP whose angles are NaN, an overflowing mixture): 0.0 * pv is NaN, not +0.0 -- the VP is outside
+//     the mask, all its terms are evaluated and p_l becomes the NaN the dense form makes.
+//   * s at its 1e-200 floor: k2 ~ 4e99 stays finite and the bound, 1.5e-197, is a normal number: every lvsq above it is left out,
+//     lvsq = 0 or NaN is kept; a huge s (max_stdd and beyond) keeps everything, and so does an infinite one (bound inf, k2 = +0.0).
+//   * a line all of whose terms underflow: nothing is kept, p_l stays +0.0 and is floored to 1e-12, and every entry of the line is
+//     0.0 / 1e-12 = +0.0 -- what pass C stores.  A NaN p_l (it passes the floor) makes 0.0 / p_l NaN in both forms.
+//   * -0.0: a negative pv (or k2) with the other positive makes the dense term -0.0, whose quotient is -0.0, not pass C's +0.0:
+//     hence the sign test in the mask.  A kept term that comes out as -0.0 is added and divided as before.
+// lvsq > (2 s) * this  =>  -(lvsq / (2 s)) < -746.0.  The constant is 746 (1 + 2^-40) and 2 s is exact, so the rounded product lies
+// above 746 (2 s) by more than 2^-41 of it; then the true quotient lies above 746 (1 + 2^-41) and the rounded quotient (rounding is
+// monotone, and doubles between 746 and that value exist) above 746.  s >= 1e-200: no subnormal product; an overflowing one keeps.
+constexpr double ESTEP_UNDERFLOW_BOUND = 746.0 * (1.0 + 0x1p-40);
+typedef unsigned long long vpmask_t;
+VPK_DEV int lowest_vp(vpmask_t r) { return __builtin_ctzll(r); }
+VPK_DEV bool estep_zero_safe(double k2, double pv) {
+    return fabs(k2) <= 1.7976931348623157e308 && fabs(pv) <= 1.7976931348623157e308 &&
+           (__double_as_longlong(k2) < 0) == (__double_as_longlong(pv) < 0);
+}
+// bit m: VP m's underflowed term is +0.0.  Called by every lane of the workgroup; the result is wave-uniform.
+VPK_DEV vpmask_t estep_zero_safe_mask(const Shared& sh, int M) {
+    if (WAVE == MAXM) {                                      // lane m tests VP m
+        const int m = lane() < M ? lane() : 0;
+        return wave_ballot(lane() < M && estep_zero_safe(sh.k2[m], sh.pv[m]));
+    }
+    vpmask_t r = 0;
+    for (int m = 0; m < M; ++m) r |= (vpmask_t)estep_zero_safe(sh.k2[m], sh.pv[m]) << m;
+    return r;
+}
+// exp_underflow's value for every x, without its branch (two of these run side by side)
+VPK_DEV double exp_underflow_select(double x) {
+    const double e = exp(x);
+    return x < -746.0 ? 0.0 : e;
+}
+// pass A over the VPs [m_lo, m_hi) of one line: lvsq to lvq and to the panel slot; force: the VPs every lane keeps.  Returns the kept VPs.
+template <int MEASURE>
+VPK_DEV vpmask_t estep_keep(const EstepLine& g, const Shared& sh, const double* X, int m_lo, int m_hi, vpmask_t force,
+                            gdp lvq, int ldn, double* wl) {
+    constexpr int EU = 4;                                    // four sqrt / div chains side by side, as in the dense form
+    const int cnt = m_hi - m_lo;
+    const vpmask_t range = cnt <= 0 ? 0ull : ((cnt >= 64 ? ~0ull : (1ull << cnt) - 1ull) << m_lo);
+    vpmask_t keep = force & range;
+    int m = m_lo;
+    for (; m + EU <= m_hi; m += EU) {
+        double lv[EU], bound[EU];
+#pragma unroll
+        for (int u = 0; u < EU; ++u) lv[u] = estep_pair<MEASURE>(g, sh, X, m + u);
+#pragma unroll
+        for (int u = 0; u < EU; ++u) bound[u] = (2 * sh.s[m + u]) * ESTEP_UNDERFLOW_BOUND;
+#pragma unroll
+        for (int u = 0; u < EU; ++u) {
+            lvq[(size_t)(m + u) * ldn] = lv[u];
+            wl[m + u] = lv[u];
+            keep |= (vpmask_t)(!(lv[u] > bound[u])) << (m + u);
+        }
+    }
+    for (; m < m_hi; ++m) {
+        const double lv1 = estep_pair<MEASURE>(g, sh, X, m);
+        lvq[(size_t)m * ldn] = lv1;
+        wl[m] = lv1;
+        keep |= (vpmask_t)(!(lv1 > (2 * sh.s[m]) * ESTEP_UNDERFLOW_BOUND)) << m;
+    }
+    return keep;
+}
+// pass B: the kept terms in ascending VP order, two at a time; SUM: added to pl in that order.  Returns pl.
+template <bool SUM> VPK_DEV double estep_terms(vpmask_t keep, const Shared& sh, double* wl, double pl) {
+    vpmask_t r = keep;
+    while (r != 0) {
+        const int m0 = lowest_vp(r);
+        r &= r - 1;
+        const bool two = r != 0;
+        const int m1 = two ? lowest_vp(r) : m0;
+        r &= r - 1;                                          // (0 stays 0)
+        const double a0 = -(wl[m0] / (2 * sh.s[m0])), a1 = -(wl[m1] / (2 * sh.s[m1]));   // calc_plv :137
+        const double t0 = (exp_underflow_select(a0) * sh.k2[m0]) * sh.pv[m0];   // calc_plv :137-145
+        const double t1 = (exp_underflow_select(a1) * sh.k2[m1]) * sh.pv[m1];
+        wl[m0] = t0;
+        if (SUM) pl += t0;                                   // p_l = dot(p_lv, p_v) :116, in VP order
+        if (two) {
+            wl[m1] = t1;
+            if (SUM) pl += t1;
+        }
+    }
+    return pl;
+}
+// pass C over the VPs [m_lo, m_hi) of one line, pl floored
+VPK_DEV void estep_posteriors(vpmask_t keep, int m_lo, int m_hi, double pl, double lw, gdp pvq, int ldn, double* wl) {
+    const double z = 0.0 / pl, zl = z * lw;                  // calc_pvl :128 and weight_matrix :519 of a term that is +0.0
+    for (int m = m_lo; m < m_hi; ++m)
+        if (!((keep >> m) & 1)) {
+            pvq[(size_t)m * ldn] = z;
+            wl[m] = zl;
+        }
+    vpmask_t r = keep;
+    while (r != 0) {
+        const int m0 = lowest_vp(r);
+        r &= r - 1;
+        const bool two = r != 0;
+        const int m1 = two ? lowest_vp(r) : m0;
+        r &= r - 1;
+        const double q0 = wl[m0] / pl, q1 = wl[m1] / pl;     // calc_pvl :128
+        pvq[(size_t)m0 * ldn] = q0;
+        wl[m0] = q0 * lw;                                    // weight_matrix :519
+        if (two) {
+            pvq[(size_t)m1 * ldn] = q1;
+            wl[m1] = q1 * lw;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // E-step: calc_probabilities (probability_functions.py:99-147), the measure a template parameter
 // ---------------------------------------------------------------------------------------------
 // X points at sh.cur or sh.nxt.  Writes lvsq[m][n], pvl[m][n], wsrc[n][m]; floors sh.s (:139).
@@ -140,8 +275,13 @@ VPK_DEVFN void estep(EmCtx& c, const double* X) {
     // LDS and T N <= 512, T = 2, 4 or 8 ADJACENT lanes share a line, each a contiguous run of ceil(M / T) VPs.  Every (line, VP) value
     // is the same expression as below; p_l (:116) is still ONE chain over the VPs in ascending order -- lane h takes the running sum
     // from lane h - 1 and continues it over its own terms, re-read from the line's panel row -- so every output has the same bits.
+    // THE ZERO RESPONSIBILITIES LEFT OUT.  With the panel in LDS the line part runs as three passes, the exp and the division to p_vl
+    // only for the VPs whose term does not underflow (see above); the dense loop below serves the plans without a panel and, under
+    // vpk_em_set_smoother(1), every plan: the form the three passes are held to, bit for bit.
+    const bool sparse = panel && c.smoother != 1;
+    const vpmask_t force = ~estep_zero_safe_mask(sh, M);     // the VPs every lane keeps (wave-uniform: scalar registers)
     int T = 1;
-    if (panel && WAVE == 64 && c.smoother != 1)              // (vpk_em_set_smoother(1): the forms of the earlier rounds, for the bit-equality test)
+    if (sparse && WAVE == 64)                                // (vpk_em_set_smoother(1): the forms of the earlier rounds, for the bit-equality test)
         while (T < 8 && 2 * T * N <= nthreads()) T *= 2;
     if (T > 1) {
         const int n_ = tid() / T, h = tid() - n_ * T;
@@ -153,55 +293,31 @@ VPK_DEVFN void estep(EmCtx& c, const double* X) {
         const double lw = c.lweight[n];
         gdp lvq = c.lvsq + n, pvq = c.pvl + n;
         double* wl = wt + (plan == 2 ? (size_t)rs_row(n, rs_jch, rs_S, Wp) : (size_t)n * Wp);
-        int m = m_lo;
-        for (; m + EU <= m_hi; m += EU) {
-            double lv[EU], tt[EU];
-#pragma unroll
-            for (int u = 0; u < EU; ++u) lv[u] = estep_pair<MEASURE>(g, sh, X, m + u);
-#pragma unroll
-            for (int u = 0; u < EU; ++u)
-                tt[u] = (exp_underflow(-(lv[u] / (2 * sh.s[m + u]))) * sh.k2[m + u]) * sh.pv[m + u];   // calc_plv :137-145
-#pragma unroll
-            for (int u = 0; u < EU; ++u) {
-                lvq[(size_t)(m + u) * c.ldn] = lv[u];
-                wl[m + u] = tt[u];
-            }
-        }
-        for (; m < m_hi; ++m) {
-            const double lv1 = estep_pair<MEASURE>(g, sh, X, m);
-            lvq[(size_t)m * c.ldn] = lv1;
-            wl[m] = (exp_underflow(-(lv1 / (2 * sh.s[m]))) * sh.k2[m]) * sh.pv[m];
-        }
+        const vpmask_t keep = estep_keep<MEASURE>(g, sh, X, m_lo, m_hi, force, lvq, c.ldn, wl);   // pass A
+        estep_terms<false>(keep, sh, wl, 0.0);               // pass B: the terms, parked in the line's panel row
         double pl = 0.0;                                     // p_l = dot(p_lv, p_v) :116, in VP order, handed from lane to lane
         for (int hh = 0; hh < T; ++hh) {
             const double prev = wave_bcast(pl, (lane() + WAVE - 1) & (WAVE - 1));
             if (h == hh) {
                 if (hh > 0) pl = prev;
-                for (m = m_lo; m < m_hi; ++m) pl += wl[m];
+                for (vpmask_t r = keep; r != 0; r &= r - 1) pl += wl[lowest_vp(r)];   // (the terms left out are +0.0)
             }
         }
         pl = wave_bcast(pl, lane() | (T - 1));               // the line's last lane holds the whole sum
         pl = (pl > 1e-12 || is_nan(pl)) ? pl : 1e-12;        // :117
-        m = m_lo;
-        for (; m + EU <= m_hi; m += EU) {
-            double q[EU];
-#pragma unroll
-            for (int u = 0; u < EU; ++u) q[u] = wl[m + u];
-#pragma unroll
-            for (int u = 0; u < EU; ++u) q[u] = q[u] / pl;   // calc_pvl :128
-#pragma unroll
-            for (int u = 0; u < EU; ++u) {
-                pvq[(size_t)(m + u) * c.ldn] = q[u];
-                wl[m + u] = q[u] * lw;                       // weight_matrix :519
-            }
-        }
-        for (; m < m_hi; ++m) {
-            const double q1 = wl[m] / pl;
-            pvq[(size_t)m * c.ldn] = q1;
-            wl[m] = q1 * lw;
-        }
+        estep_posteriors(keep, m_lo, m_hi, pl, lw, pvq, c.ldn, wl);   // pass C
         if (on && h == T - 1)
-            for (m = M; m < Wp; ++m) wl[m] = 0.0;            // padding of the last VP tile
+            for (int m = M; m < Wp; ++m) wl[m] = 0.0;        // padding of the last VP tile
+    } else if (sparse)
+    for (int n = tid(); n < N; n += nthreads()) {            // one thread per line, the three passes
+        const EstepLine g = estep_line<MEASURE>(c, n);
+        gdp lvq = c.lvsq + n, pvq = c.pvl + n;
+        double* wl = wt + (plan == 2 ? (size_t)rs_row(n, rs_jch, rs_S, Wp) : (size_t)n * Wp);
+        const vpmask_t keep = estep_keep<MEASURE>(g, sh, X, 0, M, force, lvq, c.ldn, wl);
+        double pl = estep_terms<true>(keep, sh, wl, 0.0);    // p_l = dot(p_lv, p_v) :116, in VP order
+        pl = (pl > 1e-12 || is_nan(pl)) ? pl : 1e-12;        // :117
+        estep_posteriors(keep, 0, M, pl, c.lweight[n], pvq, c.ldn, wl);
+        for (int m = M; m < Wp; ++m) wl[m] = 0.0;            // padding of the last VP tile
     } else
     for (int n = tid(); n < N; n += nthreads()) {
         const EstepLine g = estep_line<MEASURE>(c, n);
