@@ -44,6 +44,8 @@ VPK_DEV int wave_sum_int(int v) { return v; }
 VPK_DEV double nanmax(double a, double b) { return (a != a) ? a : ((b != b) ? b : (a > b ? a : b)); }
 VPK_DEV double wave_max(double v) { return v; }
 VPK_DEV int wave_max_int(int v) { return v; }
+VPK_DEV int wave_min_int(int v) { return v; }
+VPK_DEV int wave_scan_int(int v) { return v; }
 constexpr int VPG = 1;
 template <int G> VPK_DEV double group_sum(double v) { return v; }
 template <int G> VPK_DEV int group_sum_int(int v) { return v; }
@@ -80,6 +82,7 @@ VPK_DEV double __longlong_as_double(long long v) { double r; memcpy(&r, &v, 8); 
 VPK_DEV long long clock_ticks() { return 0; }
 constexpr double CLOCK_US = 0.01;
 VPK_DEV int atomic_add_int(int* p, int v) { int o = *p; *p += v; return o; }
+VPK_DEV unsigned long long atomic_add_u64(unsigned long long* p, unsigned long long v) { unsigned long long o = *p; *p += v; return o; }
 VPK_DEV unsigned atomic_or_u32(unsigned* p, unsigned v) { unsigned o = *p; *p |= v; return o; }
 
 }  // namespace vpk

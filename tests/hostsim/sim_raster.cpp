@@ -1,9 +1,13 @@
-// sim_raster.cpp -- TEST-ONLY host build of the rasteriser's arithmetic (csrc/raster_device.hpp, unmodified): the
-// simplifier, the stroker, the cell walker with its clip box, calculate_alpha and the blender are the product's code; only
-// the orchestration around them -- which on the GPU is three kernels, LDS pools and atomics -- is a serial loop here
-// (samples -> outline per line; cells of one polygon into image-sized accumulators; sweep per row; blend; next line).
-// It is not a product path: nothing in the package builds, loads or links it.
-#include "../../vanishing_points_2017_amd/csrc/raster_device.hpp"
+// sim_raster.cpp -- TEST-ONLY host build of the rasteriser (csrc/raster_device.hpp, raster_curve.hpp, raster_coverage.hpp,
+// unmodified; see hip_sim.hpp): the curve's samples, the simplifier, the stroker, the split column, polygon_coverage -- row
+// split, joined rows, bands, sweep, row table -- and the blender are the product's code, run by ONE thread on host arrays
+// where the GPU has a workgroup on LDS.  Only what is around them is a serial loop here: line after line, each sub-path's
+// polygon through polygon_coverage into the line's rows of the dense table, then the table's ranges blended in line and
+// sub-path order.  (simplify_kernel's wave machine and blend_kernel's fetch pipeline and tables need a real 64-lane wave: GPU
+// tests.)  It is not a product path: nothing in the package builds, loads or links it.
+#include "hip_sim.hpp"
+#include "../../vanishing_points_2017_amd/csrc/raster_coverage.hpp"
+#include "../../vanishing_points_2017_amd/csrc/raster_curve.hpp"
 
 #include <stdlib.h>
 #include <string.h>
@@ -13,51 +17,70 @@ using namespace vpk_raster;
 
 namespace {
 
-void draw_polygon(const V2* v, int n, unsigned grey, unsigned a8, int size, std::vector<int>& cover, std::vector<int>& area,
-                  std::vector<int>& rowmin, std::vector<int>& rowmax, unsigned char* img) {
+// what coverage_kernel keeps in LDS and in the call's workspace, for one line at a time
+struct Canvas {
+    int size, pool;
+    std::vector<int> rows, pcover, parea;                 // six row arrays; the cell pool
+    std::vector<unsigned char> alpha;                     // the line's alpha bytes (a canvas per sub-path: more than any line takes)
+    std::vector<RowEnt> dense;                            // [MAXSUB][size]
+    unsigned long long bump = 0;
+    CovShared S;
     CellSink sink;
-    sink.cover = cover.data(); sink.area = area.data(); sink.pcover = nullptr; sink.parea = nullptr;
-    sink.rowmin = rowmin.data(); sink.rowmax = rowmax.data(); sink.rowoff = nullptr; sink.size = size;
-    sink.rmin = sink.rmax = sink.lcov = nullptr; sink.xs = 0x7fffffff;      // one range per row here
-    sink.blo = 0; sink.bhi = size; sink.boff = 0;
-    EdgeClip ec;
-    ec.bx1 = 0.0; ec.by1 = 0.0; ec.bx2 = (double)size; ec.by2 = (double)size; ec.c = sink;
-    ec.nparts = 1; ec.part = 0;          // the cells: every edge whole, into image-sized accumulators
-    for (int k = 0; k < n; ++k) ec.edge<GLOBAL>(v[k].x, v[k].y, v[k + 1 < n ? k + 1 : 0].x, v[k + 1 < n ? k + 1 : 0].y);
-    ec.nparts = 16;                      // the bounds pass the way the GPU runs it: every share of every edge
-    for (int k = 0; k < n; ++k)
-        for (int q = 0; q < 16; ++q) {
-            ec.part = q;
-            ec.edge<BOUNDS>(v[k].x, v[k].y, v[k + 1 < n ? k + 1 : 0].x, v[k + 1 < n ? k + 1 : 0].y);
+    CovOut O;
+    long long split_rows = 0, joined_rows = 0, banded = 0;
+    Canvas(int size_, int pool_) : size(size_), pool(pool_), rows(6 * (size_t)size_), pcover(pool_, 0), parea(pool_, 0),
+                                   alpha((size_t)MAXSUB * size_ * (size_ + 2)), dense((size_t)MAXSUB * size_) {
+        int* r = rows.data();
+        sink.rowmin = r; sink.rowmax = r + size; sink.rowoff = r + 2 * size; sink.rmin = r + 3 * size; sink.rmax = r + 4 * size;
+        sink.lcov = r + 5 * size;
+        for (int y = 0; y < size; ++y) {                  // (as coverage_kernel starts; polygon_coverage leaves them so)
+            sink.rowmin[y] = 0x7fffffff; sink.rowmax[y] = -1; sink.rowoff[y] = 0; sink.rmin[y] = 0x7fffffff; sink.rmax[y] = -1;
+            sink.lcov[y] = 0;
         }
-    const int ldc = size + 2;
-    for (int y = 0; y < size; ++y) {
-        const int lo = rowmin[y], hi = rowmax[y];
-        if (hi < lo) continue;
-        int R = 0;
-        for (int xi = lo; xi <= hi; ++xi) {               // the per-pixel form of sweep_scanline (coverage_kernel)
-            int& c = cover[(size_t)y * ldc + xi];
-            int& a = area[(size_t)y * ldc + xi];
-            R += c;
-            unsigned al = 0;
-            if (a) al = calc_alpha((R << (SHIFT + 1)) - a);
-            else if (xi < hi) al = calc_alpha(R << (SHIFT + 1));
-            c = 0; a = 0;
-            const int x = xi - 1;
+        sink.pcover = pcover.data(); sink.parea = parea.data();
+        sink.size = size; sink.xs = 0; sink.blo = 0; sink.bhi = 0; sink.boff = 0;
+        O.alpha = alpha.data(); O.alpha_cap = alpha.size(); O.bump = &bump; O.pool = pool; O.probe = 0; O.laps = nullptr;
+    }
+    // sub-path q (of npoly) of the line at hand -> its rows of the dense table; false: dropped
+    bool cover(const V2* v, int n, int xsplit, int q, int npoly) {
+        const int more = q == 0 ? (npoly > 1 ? npoly - 1 : 0) << ROW_MORE_SHIFT : 0;
+        const unsigned long long before = bump;
+        RowEnt* ent = dense.data() + (size_t)q * size;
+        const bool ok = polygon_coverage(v, n, xsplit, sink, size, S, O, ent, more);
+        banded += bump - before > (unsigned long long)pool;               // more entries than the pool holds: several bands
+        for (int y = 0; y < size; ++y) {
+            const Range l = range_l(ent[y]), r = range_r(ent[y]);
+            split_rows += l.len > 0 && r.len > 0;
+            joined_rows += l.len > 0 && r.len == 0 && l.xmin + l.len > xsplit;      // one range with cells on both sides
+        }
+        return ok;
+    }
+    void blend_range(const Range& r, int y, unsigned grey, unsigned a8, unsigned char* img) const {
+        for (int q = 0; q < r.len; ++q) {
+            const int x = r.xmin + q;
+            const unsigned al = alpha[(size_t)r.off + q];
             if (al && x >= 0 && x < size) img[(size_t)y * size + x] = (unsigned char)blend(img[(size_t)y * size + x], grey, a8, al);
         }
-        rowmin[y] = 0x7fffffff;
-        rowmax[y] = -1;
     }
-}
+    // the line's rows as blend_kernel reads them: sub-path 0, then as many more as its `more` bits say
+    void blend_line(unsigned grey, unsigned a8, unsigned char* img) {
+        for (int y = 0; y < size; ++y) {
+            const int more = (dense[y].lenL >> ROW_MORE_SHIFT) & 7;
+            for (int q = 0; q <= more; ++q) {
+                const RowEnt& e = dense[(size_t)q * size + y];
+                blend_range(range_l(e), y, grey, a8, img);
+                blend_range(range_r(e), y, grey, a8, img);
+            }
+        }
+        bump = 0;
+    }
+};
 
 // the samples of one line through the simplifier, as outline_kernel's sequential machine feeds them: `sub(n)` is called at the
 // end of every sub-path that kept n >= 2 points (in simp[0 .. n)); returns the simplifier's overflow flag
 template <class F>
 unsigned line_subpaths(const double* l, int size, int alt, std::vector<V2>& simp, F sub) {
-    const int ns = 10000;
-    const double lo_a = -PI_D / 2, hi_a = PI_D / 2, step = (hi_a - lo_a) / (ns - 1);
-    const double la = l[0], lb = l[1], lc = l[2];
+    const int ns = SAMPLES;
     Simplifier sm;
     sm.init(simp.data(), MAXS);
     auto flush = [&]() {
@@ -65,17 +88,14 @@ unsigned line_subpaths(const double* l, int size, int alt, std::vector<V2>& simp
         if (sm.n >= 2) sub(sm.n);
         sm.n = 0;
     };
-    constexpr int OG = 8;                                     // groups, as outline_kernel feeds them
+    constexpr int OG = SAMPLE_GROUP;
     for (int i0 = 0; i0 < ns; i0 += OG) {
         double xs[OG], ys[OG];
         for (int u = 0; u < OG; ++u) {
-            const int i = i0 + u < ns ? i0 + u : ns - 1;
-            const double al = (i == ns - 1) ? hi_a : lo_a + i * step;
-            double be = alt ? -atan(-lc / (cos(al) * la + sin(al) * lb))      // sphere_mapping.py:59
-                            : -atan((-la * sin(al) - lc * cos(al)) / lb);     // :61
-            be *= -1;
-            xs[u] = (al - lo_a) / (hi_a - lo_a) * size;
-            ys[u] = size - (be - lo_a) / (hi_a - lo_a) * size;
+            double s[3];
+            curve_sample(i0 + u < ns ? i0 + u : ns - 1, ns, size, s);
+            xs[u] = s[0];
+            ys[u] = curve_y(curve_beta(l[0], l[1], l[2], s[1], s[2], alt), size);
         }
         feed_group<OG>(sm, xs, ys, ns - i0, flush);
     }
@@ -85,52 +105,69 @@ unsigned line_subpaths(const double* l, int size, int alt, std::vector<V2>& simp
 
 }  // namespace
 
-extern "C" int sim_raster(const double* l, int nlines, int size, double alpha, int alt, unsigned char* out) {
+// the pool size the product gives coverage_kernel for a canvas size
+extern "C" int sim_raster_pool(int size) { return coverage_pool(size); }
+
+// counters[0 .. 3), summed over the call: rows that kept two separate ranges, rows whose ranges were joined, polygons that
+// took more than one band of the pool.  Returns the overflow flags, or -1 for a pool too small to hold one joined row (the band
+// packing would overrun it).
+extern "C" int sim_raster(const double* l, int nlines, int size, double alpha, int alt, int pool, unsigned char* out,
+                          long long* counters) {
+    if (pool < size + 2) return -1;
     std::vector<V2> simp(MAXS), verts(MAXV);
-    std::vector<int> cover((size_t)size * (size + 2), 0), area((size_t)size * (size + 2), 0), rowmin(size, 0x7fffffff), rowmax(size, -1);
+    Canvas cv(size, pool);
     memset(out, 0, (size_t)size * size);
     unsigned flags = 0;
     const unsigned a8 = (unsigned)(alpha * 255.0 + 0.5);
     for (int g = 0; g < nlines; ++g) {
-        const unsigned overflow = line_subpaths(l + 3 * g, size, alt, simp, [&](int n) {
-            Outline o;
-            o.v = verts.data(); o.n = 0; o.cap = MAXV; o.flags = &flags;
-            stroke_outline(simp.data(), n, 100.0 / 72.0, o);
-            if (o.n >= 3) draw_polygon(verts.data(), o.n, 255u, a8, size, cover, area, rowmin, rowmax, out);
-        });
-        flags |= overflow;
-    }
-    const double s = (double)size, w_spine = 0.8 * 100.0 / 72.0;
-    for (int side = 0; side < 4; ++side) {
-        const double x0 = (side == 1) ? s : 0.0, y0 = (side == 3) ? 0.0 : s, x1 = (side == 0) ? 0.0 : s, y1 = (side == 2) ? s : 0.0;
-        simp[0].x = floor(x0 + 0.5) + 0.5; simp[0].y = floor(y0 + 0.5) + 0.5;
-        simp[1].x = floor(x1 + 0.5) + 0.5; simp[1].y = floor(y1 + 0.5) + 0.5;
+        // outline_kernel: the line's polygons side by side in verts, up to MAXSUB of them
         Outline o;
         o.v = verts.data(); o.n = 0; o.cap = MAXV; o.flags = &flags;
-        stroke_outline(simp.data(), 2, w_spine, o);
-        draw_polygon(verts.data(), o.n, 0u, 255u, size, cover, area, rowmin, rowmax, out);
+        int npoly = 0, first[MAXSUB], count[MAXSUB], xsplit[MAXSUB];
+        flags |= line_subpaths(l + 3 * g, size, alt, simp, [&](int n) {
+            const int at = o.n, xs = split_column(simp.data(), n, size);
+            stroke_outline(simp.data(), n, LINE_WIDTH_PX, o);
+            if (o.n - at < 3) return;
+            if (npoly < MAXSUB) { first[npoly] = at; count[npoly] = o.n - at; xsplit[npoly] = xs; ++npoly; }
+            else flags |= FLAG_OVERFLOW;
+        });
+        if (npoly == 0) continue;
+        for (int q = 0; q < npoly; ++q)
+            if (!cv.cover(verts.data() + first[q], count[q], xsplit[q], q, npoly)) flags |= FLAG_OVERFLOW;
+        cv.blend_line(255u, a8, out);
     }
+    for (int side = 0; side < 4; ++side) {
+        spine_path(side, size, simp.data());
+        Outline o;
+        o.v = verts.data(); o.n = 0; o.cap = MAXV; o.flags = &flags;
+        stroke_outline(simp.data(), 2, SPINE_WIDTH_PX, o);
+        if (!cv.cover(verts.data(), o.n, size + 2, 0, 1)) flags |= FLAG_OVERFLOW;      // (a spine: one range per row)
+        cv.blend_line(0u, 255u, out);
+    }
+    counters[0] = cv.split_rows; counters[1] = cv.joined_rows; counters[2] = cv.banded;
     return (int)flags;
 }
 
 // the cells of ONE edge walked whole (nparts = 1) and in shares (nparts = K): the closed-form restart of AGG's row DDA must give
-// the same accumulators.  Returns the number of accumulator entries that differ.
+// the same accumulators.  Returns the number of accumulator entries that differ.  The accumulators are image-sized, [size][size
+// + 2] with x shifted by one (cells at x = -1 and x = size exist), behind identity row tables.
 extern "C" int sim_edge_shares(double x1, double y1, double x2, double y2, int size, int K) {
-    std::vector<int> c1((size_t)size * (size + 2), 0), a1(c1), c2(c1), a2(c1), rmin(size, 0x7fffffff), rmax(size, -1);
+    std::vector<int> c1((size_t)size * (size + 2), 0), a1(c1), c2(c1), a2(c1), rowoff(size), rowmin(size, 0), lcov(size, -1);
+    for (int y = 0; y < size; ++y) rowoff[y] = y * (size + 2);
     CellSink s;
-    s.pcover = s.parea = nullptr; s.rowmin = rmin.data(); s.rowmax = rmax.data(); s.rowoff = nullptr; s.size = size;
-    s.rmin = s.rmax = s.lcov = nullptr; s.xs = 0x7fffffff;
+    s.rowmin = rowmin.data(); s.rowmax = nullptr; s.rowoff = rowoff.data(); s.size = size;
+    s.rmin = s.rmax = nullptr; s.lcov = lcov.data(); s.xs = 0x7fffffff;
     s.blo = 0; s.bhi = size; s.boff = 0;
     EdgeClip ec;
     ec.bx1 = 0.0; ec.by1 = 0.0; ec.bx2 = (double)size; ec.by2 = (double)size;
-    s.cover = c1.data(); s.area = a1.data();
+    s.pcover = c1.data(); s.parea = a1.data();
     ec.c = s;
     ec.nparts = 1; ec.part = 0;
-    ec.edge<GLOBAL>(x1, y1, x2, y2);
-    s.cover = c2.data(); s.area = a2.data();
+    ec.edge<POOLED>(x1, y1, x2, y2);
+    s.pcover = c2.data(); s.parea = a2.data();
     ec.c = s;
     ec.nparts = K;
-    for (int q = 0; q < K; ++q) { ec.part = q; ec.edge<GLOBAL>(x1, y1, x2, y2); }
+    for (int q = 0; q < K; ++q) { ec.part = q; ec.edge<POOLED>(x1, y1, x2, y2); }
     int bad = 0;
     for (size_t i = 0; i < c1.size(); ++i) bad += (c1[i] != c2[i]) || (a1[i] != a2[i]);
     return bad;
@@ -146,7 +183,7 @@ extern "C" int sim_outline_counts(const double* l, int size, int alt, int* count
     line_subpaths(l, size, alt, simp, [&](int n) {
         Outline o;
         o.v = verts.data(); o.n = 0; o.cap = MAXV; o.flags = &flags;
-        stroke_outline(simp.data(), n, 100.0 / 72.0, o);
+        stroke_outline(simp.data(), n, LINE_WIDTH_PX, o);
         if (o.n >= 3) { if (np < max) counts[np] = o.n; ++np; }
     });
     return np;

@@ -199,10 +199,9 @@ def line_counts(lp, v, s, w, lweight, thresh=1.96 ** 2):
     return counts, cw, assoc
 
 
-# ---- the rasteriser's arithmetic (csrc/raster_device.hpp) -----------------------------------------------------------------
+# ---- the rasteriser (csrc/raster_device.hpp, raster_curve.hpp, raster_coverage.hpp) ----------------------------------------
 RASTER_SO = os.path.join(BUILD, "libvpk_hostsim_raster.so")
-RASTER_SRC = [os.path.join(HERE, "sim_raster.cpp"),
-              os.path.join(HERE, "..", "..", "vanishing_points_2017_amd", "csrc", "raster_device.hpp")]
+RASTER_SRC = [os.path.join(HERE, "sim_raster.cpp"), os.path.join(HERE, "hip_sim.hpp")] + sorted(glob.glob(os.path.join(CSRC, "raster_*.hpp")))
 _raster_lib = None
 
 
@@ -216,19 +215,33 @@ def raster_lib():
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", RASTER_SRC[0], "-o", RASTER_SO])
     _raster_lib = ctypes.CDLL(RASTER_SO)
     _raster_lib.sim_raster.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int, ctypes.c_double,
-                                       ctypes.c_int, ctypes.POINTER(ctypes.c_uint8)]
+                                       ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_longlong)]
+    _raster_lib.sim_raster_pool.argtypes = [ctypes.c_int]
     _raster_lib.sim_edge_shares.argtypes = [ctypes.c_double] * 4 + [ctypes.c_int, ctypes.c_int]
     _raster_lib.sim_outline_counts.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int,
                                                ctypes.POINTER(ctypes.c_int), ctypes.c_int]
     return _raster_lib
 
 
-def sim_raster(lines, size=250, alpha=0.1, alternative=False):
-    """The product's stroke / cell / blend arithmetic run serially on the host: uint8 [size, size] and the overflow flags."""
+def sim_raster_pool(size):
+    """Cell-pool entries the product gives its coverage kernel for a canvas size."""
+    return raster_lib().sim_raster_pool(size)
+
+
+def sim_raster(lines, size=250, alpha=0.1, alternative=False, pool=None, counters=False):
+    """The product's curve / stroke / coverage / blend code run by one thread on the host: uint8 [size, size] and the overflow
+    flags.  pool: cell-pool entries (default: the product's for this size).  counters=True: also a dict of what the coverage
+    path met -- rows that kept two separate ranges, rows whose ranges were joined, polygons that took more than one band."""
     l = np.ascontiguousarray(lines, dtype=np.float64).reshape(-1, 3)
     out = np.zeros((size, size), dtype=np.uint8)
+    met = np.zeros(3, dtype=np.int64)
     flags = raster_lib().sim_raster(_p(l, ctypes.c_double), l.shape[0], size, float(alpha), int(bool(alternative)),
-                                    _p(out, ctypes.c_uint8))
+                                    sim_raster_pool(size) if pool is None else int(pool), _p(out, ctypes.c_uint8),
+                                    _p(met, ctypes.c_longlong))
+    if flags < 0:
+        raise ValueError("sim_raster: a pool of %s entries cannot hold one joined row of a %d px canvas" % (pool, size))
+    if counters:
+        return out, flags, dict(zip(("split_rows", "joined_rows", "banded_polygons"), met.tolist()))
     return out, flags
 
 

@@ -1,9 +1,14 @@
-"""The rasteriser's PRODUCT arithmetic (csrc/raster_device.hpp: simplifier, stroker, cell walker with its clip box and its
-closed-form restart of AGG's row DDA, calculate_alpha, blender) compiled for the host by tests/hostsim/sim_raster.cpp and run
-serially -- the CPU suite's check of the code the GPU kernels are made of (the kernels' own orchestration: LDS pools, row
-bands, atomics, the blend order across workgroups, is what tests/test_gpu_raster.py and tests/test_gpu_raster_edges.py
-cover; the latter's inputs run through the host build at the end of this file).  Bit-exact against the reference's own
+"""The rasteriser's PRODUCT code compiled for the host by tests/hostsim/sim_raster.cpp and run by one thread -- the CPU
+suite's check of the code the GPU kernels are made of: csrc/raster_curve.hpp (samples, curve, spines, split column),
+csrc/raster_device.hpp (simplifier, stroker, cell walker with its clip box and its closed-form restart of AGG's row DDA,
+calculate_alpha, blender) and csrc/raster_coverage.hpp (polygon_coverage: the rows' split in a left and a right range, the
+rule that joins them, the bands of rows a polygon beyond the cell pool is done in, the sweep's runs, the row table with its
+"more sub-paths" bits), at the pool size the product uses and at the smallest one.  What stays with
+tests/test_gpu_raster.py and tests/test_gpu_raster_edges.py is what needs the GPU: several threads and their barriers and
+atomics, simplify_kernel's wave machine, blend_kernel's fetch pipeline, tables and order across workgroups, the chunk loop
+(the latter file's inputs run through the host build at the end of this file).  Bit-exact against the reference's own
 rasters (tests/golden) and the restatement oracle/agg_raster.py."""
+import functools
 import os
 import sys
 
@@ -17,13 +22,50 @@ sys.path.insert(0, os.path.join(os.path.dirname(__file__), "hostsim"))
 import simlib  # noqa: E402
 
 
-@pytest.mark.parametrize("name", ["tiny_n12", "clean3_n60", "noweights_n100", "yud_n330", "stress_n300"])
-def test_product_arithmetic_reproduces_the_references_raster(name):
+GOLDENS = ["tiny_n12", "clean3_n60", "noweights_n100", "yud_n330", "stress_n300"]
+
+
+@functools.lru_cache(maxsize=None)
+def golden_raster(name, pool=None):
+    """(the golden, the host build's raster of its lines at 500 px, flags, what the coverage path met), computed once"""
     g = load(name)
-    got, flags = simlib.sim_raster(g["l"], 500, 0.1)
+    return (g,) + simlib.sim_raster(g["l"], 500, 0.1, pool=pool, counters=True)
+
+
+@pytest.mark.parametrize("name", GOLDENS)
+def test_product_arithmetic_reproduces_the_references_raster(name):
+    g, got, flags, _ = golden_raster(name)
     assert flags == 0
     diff = got.astype(int) - g["sphere_image"].astype(int)
     assert not diff.any(), "%d pixels differ" % (diff != 0).sum()
+
+
+def test_the_rows_split_and_join_on_the_way_to_the_references_raster():
+    """The pixel equality above could hold with every row one range: on yud_n330 rows keep two separate ranges (the gap
+    between them dropped) AND rows are joined (ranges that touch, or a gap that is drawn), both in plenty."""
+    g, got, flags, met = golden_raster("yud_n330")
+    assert flags == 0 and np.array_equal(got, g["sphere_image"])
+    assert met["split_rows"] > 0 and met["joined_rows"] > 0, met
+
+
+@pytest.mark.parametrize("name", GOLDENS)
+def test_polygons_done_in_bands_reproduce_the_references_raster(name):
+    """The cell pool at its smallest legal size -- one joined row: size + 2 entries, rounded up to 64 = 512 at 500 px --
+    so that polygons take several bands of rows: the same pixels, nothing dropped."""
+    g, got, flags, met = golden_raster(name, pool=512)
+    assert flags == 0 and met["banded_polygons"] > 0, met
+    assert np.array_equal(got, g["sphere_image"])
+
+
+def test_the_pool_size_of_the_product():
+    """A band must hold one joined row (size + 2 entries); the sizes the launch uses today, from its formula: what 53 KB of
+    LDS less 11 KB of static arrays and six row arrays (of the size rounded up to 64 ints) leave, in (cover, area) pairs,
+    rounded down to 64.  (At 8 px that is 5184 entries: 6 * 64 ints of row arrays.)"""
+    for size, pool in ((8, 5184), (500, 3840), (1023, 2304), (1024, 2304)):
+        assert pool == ((53 * 1024 - 11 * 1024 - 6 * ((size + 63) & ~63) * 4) // 8) & ~63
+        assert simlib.sim_raster_pool(size) == pool >= size + 2
+    with pytest.raises(ValueError):                                  # (the host build refuses a smaller pool)
+        simlib.sim_raster(np.zeros((0, 3)), 64, 0.1, pool=65)
 
 
 def test_odd_lines_sizes_and_alpha_against_the_restatement():
@@ -92,6 +134,9 @@ def test_outlines_around_256_vertices_against_the_restatement():
         assert simlib.sim_outline_counts(line, 1024) == [n]
         got, flags = simlib.sim_raster(line, 1024, 0.1)
         assert flags == 0 and np.array_equal(got, want(line, 1024))
+        # ... and with the smallest pool (1024 + 2 entries, rounded up to 64): bands meet the vertices read from beyond LDS
+        got, flags, met = simlib.sim_raster(line, 1024, 0.1, pool=1088, counters=True)
+        assert flags == 0 and met["banded_polygons"] > 0 and np.array_equal(got, want(line, 1024))
 
 
 @pytest.mark.parametrize("size", [8, 9, 33])

@@ -2,7 +2,8 @@
 // sources): PathSimplifier, conv_stroke, the cell walker with the clip box, calculate_alpha and the plain blender, as
 // plain structs and functions.  Compiled by hipcc into the kernels of vpk_raster.hip and -- unmodified, with RDEV empty and
 // the atomics plain -- by g++ into the test-only host build tests/hostsim/sim_raster.cpp, so that the CPU suite runs the
-// product's own code against the reference's rasters.
+// product's own code against the reference's rasters.  (The curve and the spines: raster_curve.hpp; a polygon's coverage
+// built from the walkers here: raster_coverage.hpp.)
 #ifndef VPK_RASTER_DEVICE_HPP_
 #define VPK_RASTER_DEVICE_HPP_
 
@@ -11,7 +12,6 @@
 #ifdef __HIPCC__
 #define RDEV __device__
 #define RDEV_INLINE __device__ __forceinline__
-#define RDEV_NOINLINE __device__ __noinline__
 // the per-polygon accumulators live in LDS: pointers typed with the LDS address space make the accesses ds_* instructions
 // (through generic pointers -- a sink handed to a noinline function -- they were flat_* instructions: LDS by way of the
 // vector-memory address path, a round trip several times longer, with the waves parked on it 80 % of the time)
@@ -19,21 +19,21 @@
 #define RS_ATOMIC_ADD(p, v) (void)__hip_atomic_fetch_add((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
 #define RS_ATOMIC_MIN(p, v) (void)__hip_atomic_fetch_min((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
 #define RS_ATOMIC_MAX(p, v) (void)__hip_atomic_fetch_max((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-#define RS_ATOMIC_ADD_GLOBAL(p, v) atomicAdd((p), (v))
+#define RS_COVERAGE_THREADS 256
 #else
 #define RDEV
 #define RDEV_INLINE inline
-#define RDEV_NOINLINE
 #define RS_LDS
 #define RS_ATOMIC_ADD(p, v) (*(p) += (v))
 #define RS_ATOMIC_MIN(p, v) (*(p) = *(p) < (v) ? *(p) : (v))
 #define RS_ATOMIC_MAX(p, v) (*(p) = *(p) > (v) ? *(p) : (v))
-#define RS_ATOMIC_ADD_GLOBAL(p, v) (*(p) += (v))
+#define RS_COVERAGE_THREADS 1
 #endif
 
 namespace vpk_raster {
 
-constexpr int RT = 256;                 // threads per workgroup of coverage_kernel (one polygon at a time: ~250 work items)
+constexpr int RT = RS_COVERAGE_THREADS; // threads per workgroup of coverage_kernel (one polygon at a time: ~250 work items);
+                                        // a compile-time constant on either side: 256 on the device, 1 in the host build
 constexpr int MAXS = 384;               // simplified points kept per line (typical: 30-100)
 constexpr int MAXV = 1024;              // outline vertices per line (typical: 60-200)
 constexpr int MAXSUB = 4;               // sub-paths per line (a NaN sample breaks the path)
@@ -295,12 +295,11 @@ RDEV void stroke_outline(V2* p, int n, double width, Outline& o) {
 // ---------------------------------------------------------------------------------------------------------------
 // rasterizer_cells_aa::line / render_hline: cells of one edge, added with integer atomics
 // ---------------------------------------------------------------------------------------------------------------
-// Where the cells of the line being drawn live.  Default: an LDS pool -- a stroke touches a few thousand pixels, so the
-// polygon's edges are walked twice: pass 1 (BOUNDS) only records every row's first / last cell, a prefix sum over the rows
-// packs the rows' cell ranges into the pool, pass 2 (POOL) adds the cells there with LDS atomics.  A polygon whose ranges
-// do not fit the pool (GLOBAL) uses image-sized accumulators in HBM / L2 with global atomics instead.
-constexpr int POOL = 7040;              // cells (cover, area) of one polygon in LDS: 55 KB (two workgroups per CU)
-enum SinkMode { BOUNDS = 0, POOLED = 1, GLOBAL = 2 };
+// Where the cells of the line being drawn live: an LDS pool -- a stroke touches a few thousand pixels, so the polygon's edges
+// are walked twice: pass 1 (BOUNDS) only records every row's first / last cell, a prefix sum over the rows packs the rows' cell
+// ranges into the pool, pass 2 (POOLED) adds the cells there with LDS atomics.  A polygon whose ranges do not fit the pool is
+// done in bands of rows, one pass 2 per band (raster_coverage.hpp).
+enum SinkMode { BOUNDS = 0, POOLED = 1 };
 
 typedef RS_LDS int* lds_int_ptr;
 // A row's cells come in up to TWO ranges.  The curve is the graph of a function with at most one interior extremum, so a row
@@ -312,28 +311,21 @@ typedef RS_LDS int* lds_int_ptr;
 // apex itself has cells at its two ends only and IS drawn in between).  After the row scan `lcov` holds, per row, the
 // number of L entries, or -1 if the row is one joined range [rowmin, rmax].
 struct CellSink {
-    int* cover; int* area;              // GLOBAL: [size][size + 2], x shifted by one (cells at x = -1 and x = size exist)
     lds_int_ptr pcover, parea;          // POOLED: LDS pool
     lds_int_ptr rowmin, rowmax, rowoff; // LDS, per row: L range (cell index + 1), first pool entry
     lds_int_ptr rmin, rmax, lcov;       // LDS, per row: R range; cover of the L pieces, then the split (see above)
-    int xs;                             // first cell column of the R side (host build: INT_MAX -- one range per row)
+    int xs;                             // first cell column of the R side
     int size;
     int blo, bhi, boff;                 // POOLED: the band of rows [blo, bhi) the pool holds now; pool index = rowoff - boff
 };
 RDEV_INLINE int row_len(int lo, int hi) { return hi >= lo ? hi - lo + 1 : 0; }
 // (the sink travels BY VALUE through the noinline walkers below: a pointer to it would be a pointer into the caller's
 //  private memory, and every field access a scratch load)
-template <int MODE> RDEV_INLINE void cell_add(const CellSink& s, int ex, int ey, int c, int a, int row_base) {
+RDEV_INLINE void cell_add(const CellSink& s, int ex, int c, int a, int row_base) {
     if ((c | a) == 0) return;
     if (ex < -1 || ex > s.size) return;
-    if (MODE == POOLED) {                     // row_base: the row's first pool entry minus its first cell (cell_hline)
-        if (c) RS_ATOMIC_ADD(s.pcover + row_base + ex, c);
-        if (a) RS_ATOMIC_ADD(s.parea + row_base + ex, a);
-    } else {
-        const size_t idx = (size_t)ey * (s.size + 2) + ex + 1;
-        if (c) RS_ATOMIC_ADD_GLOBAL(s.cover + idx, c);
-        if (a) RS_ATOMIC_ADD_GLOBAL(s.area + idx, a);
-    }
+    if (c) RS_ATOMIC_ADD(s.pcover + row_base + ex, c);    // row_base: the row's first pool entry minus its first cell (cell_hline)
+    if (a) RS_ATOMIC_ADD(s.parea + row_base + ex, a);
 }
 // render_hline: the cells of one row's piece of an edge.  BOUNDS: only the row's first / last cell are wanted, and a
 // superset will do (an entry of the row's range that no cell is added to sweeps to alpha 0): the piece's two end cells.
@@ -361,25 +353,22 @@ template <int MODE> RDEV_INLINE void cell_hline(const CellSink& s, int ey, int x
         }
         return;
     }
+    // POOLED.  The row's entries in the pool: looked up once per row piece, not per cell
     if (ey < 0 || ey >= s.size) return;
-    int row_base = 0;
-    if (MODE == POOLED) {                     // the row's entries in the pool: looked up once per row piece, not per cell
-        if (ey < s.blo || ey >= s.bhi) return;
-        const int split = s.lcov[ey];         // entries of the L range, or -1: one joined range
-        const int lo = ex1 < ex2 ? ex1 : ex2;
-        row_base = s.rowoff[ey] - s.boff + 1 - s.rowmin[ey];
-        if (split >= 0 && lo >= s.xs) row_base = s.rowoff[ey] - s.boff + split + 1 - s.rmin[ey];
-    }
+    if (ey < s.blo || ey >= s.bhi) return;
+    const int split = s.lcov[ey];             // entries of the L range, or -1: one joined range
+    int row_base = s.rowoff[ey] - s.boff + 1 - s.rowmin[ey];
+    if (split >= 0 && (ex1 < ex2 ? ex1 : ex2) >= s.xs) row_base = s.rowoff[ey] - s.boff + split + 1 - s.rmin[ey];
     if (ex1 == ex2) {
         const int delta = y2 - y1;
-        cell_add<MODE>(s, ex1, ey, delta, (fx1 + fx2) * delta, row_base);
+        cell_add(s, ex1, delta, (fx1 + fx2) * delta, row_base);
         return;
     }
     int p = (SUB - fx1) * (y2 - y1), first = SUB, incr = 1, dx = x2 - x1;
     if (dx < 0) { p = fx1 * (y2 - y1); first = 0; incr = -1; dx = -dx; }
     int delta = p / dx, mod = p % dx;
     if (mod < 0) { --delta; mod += dx; }
-    cell_add<MODE>(s, ex1, ey, delta, (fx1 + first) * delta, row_base);
+    cell_add(s, ex1, delta, (fx1 + first) * delta, row_base);
     ex1 += incr;
     y1 += delta;
     if (ex1 != ex2) {
@@ -391,13 +380,13 @@ template <int MODE> RDEV_INLINE void cell_hline(const CellSink& s, int ey, int x
             delta = lift;
             mod += rem;
             if (mod >= 0) { mod -= dx; ++delta; }
-            cell_add<MODE>(s, ex1, ey, delta, SUB * delta, row_base);
+            cell_add(s, ex1, delta, SUB * delta, row_base);
             y1 += delta;
             ex1 += incr;
         }
     }
     delta = y2 - y1;
-    cell_add<MODE>(s, ex1, ey, delta, (fx2 + SUB - first) * delta, row_base);
+    cell_add(s, ex1, delta, (fx2 + SUB - first) * delta, row_base);
 }
 // rasterizer_cells_aa::line for the rows [part * nrows / nparts, (part + 1) * nrows / nparts) of the edge only: a long
 // edge is shared by several threads.  AGG walks the rows with an integer DDA (x advances by lift, plus one whenever

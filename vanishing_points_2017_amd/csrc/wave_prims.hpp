@@ -94,6 +94,22 @@ VPK_DEV int wave_max_int(int v) {
     }
     return v;
 }
+VPK_DEV int wave_min_int(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        int u = __shfl_xor(v, o);
+        v = u < v ? u : v;
+    }
+    return v;
+}
+// inclusive prefix sum over the wave's lanes: lane i receives v(0) + ... + v(i)
+VPK_DEV int wave_scan_int(int v) {
+    for (int o = 1; o < WAVE; o <<= 1) {
+        const int up = __shfl_up(v, o);
+        if (lane() >= o) v += up;
+    }
+    return v;
+}
 // The same butterflies over aligned groups of G lanes (G = 16: four independent problems per wave, used
 // where a phase has more small problems than waves, e.g. one M-step per VP).  G = 64 == the wave forms.
 constexpr int VPG = 16;   // lanes per VP in the M-step
@@ -251,6 +267,7 @@ VPK_DEV long long clock_ticks() { return (long long)wall_clock64(); }
 constexpr double CLOCK_US = 0.01;
 
 VPK_DEV int atomic_add_int(int* p, int v) { return atomicAdd(p, v); }
+VPK_DEV unsigned long long atomic_add_u64(unsigned long long* p, unsigned long long v) { return atomicAdd(p, v); }
 VPK_DEV unsigned atomic_or_u32(unsigned* p, unsigned v) { return atomicOr(p, v); }
 
 }  // namespace vpk
