@@ -185,3 +185,80 @@ def test_argument_errors_need_no_gpu():
         V.merge_vps(0, v, np.ones(65), None, 1e-3, None, None, 1, None, lp, None, "angle")
     with pytest.raises(ValueError, match="at most 64"):
         V.calc_vp_line_counts(v[0], None, lp, np.ones(65), np.ones((65, 4)), np.ones(4), "angle")
+
+
+def _batch_inputs():
+    """Two images (N = 4 and 3 lines, M = 2 and 1 VPs) as lists: shapes are all these checks read."""
+    n, m = (4, 3), (2, 1)
+    z = lambda *shape: [np.zeros((k,) + shape) for k in n]
+    return {"lps": z(4), "ls": z(3), "lw": z(), "ang": z(), "lsims": [np.zeros((k, k)) for k in n],
+            "vs": [np.zeros((k, 3)) for k in m], "ss": [np.ones(k) for k in m], "w": [np.zeros((j, k)) for j, k in zip(m, n)],
+            "assoc": [np.zeros(k, np.int64) for k in n]}
+
+
+def test_counts_batch_errors_need_no_gpu():
+    from vanishing_points_2017_amd import vp_localisation as V
+    g = _batch_inputs()
+    cat = {k: np.concatenate([a.reshape(a.shape[0], -1) if k in ("lps", "vs") else a.ravel() for a in v]) for k, v in g.items()}
+    with pytest.raises(ValueError, match="decision_metrics or vp_assocs is needed"):
+        V.calc_vp_line_counts_batch(g["vs"], g["lps"], g["ss"], None, g["lw"])
+    with pytest.raises(ValueError, match="the decision metrics hold 10 elements, the images' M x N sum to 11"):
+        V.calc_vp_line_counts_batch(g["vs"], g["lps"], g["ss"], [g["w"][0], g["w"][1][:, :2]], g["lw"])
+    with pytest.raises(ValueError, match="ss holds 2 elements, expected 3"):
+        V.calc_vp_line_counts_batch(g["vs"], g["lps"], g["ss"][:1], g["w"], g["lw"])
+    with pytest.raises(ValueError, match="lweights holds 8 elements, expected 7"):
+        V.calc_vp_line_counts_batch(g["vs"], g["lps"], g["ss"], g["w"], [np.zeros(4), np.zeros(4)])
+    with pytest.raises(ValueError, match="vp_assocs holds 6 elements, expected 7"):
+        V.calc_vp_line_counts_batch(g["vs"], g["lps"], g["ss"], None, g["lw"], vp_assocs=[g["assoc"][0], g["assoc"][1][:2]])
+    with pytest.raises(ValueError, match="lps and vps describe 2 and 1 images"):
+        V.calc_vp_line_counts_batch(g["vs"][:1], g["lps"], g["ss"], g["w"], g["lw"])
+    # the concatenated form
+    off = {"line_offsets": [0, 4, 7], "vp_offsets": [0, 2, 3]}
+    with pytest.raises(ValueError, match="the decision metrics hold 10 elements, the images' M x N sum to 11"):
+        V.calc_vp_line_counts_batch(cat["vs"], cat["lps"], cat["ss"], cat["w"][:-1], cat["lw"], **off)
+    with pytest.raises(ValueError, match="lweights holds 6 elements, expected 7"):
+        V.calc_vp_line_counts_batch(cat["vs"], cat["lps"], cat["ss"], cat["w"], cat["lw"][:-1], **off)
+    with pytest.raises(ValueError, match="lps offsets must rise from 0 to 7"):
+        V.calc_vp_line_counts_batch(cat["vs"], cat["lps"], cat["ss"], cat["w"], cat["lw"], line_offsets=[0, 4, 8], vp_offsets=[0, 2, 3])
+
+
+def test_split_batch_errors_need_no_gpu():
+    from vanishing_points_2017_amd import vp_localisation as V
+    g = _batch_inputs()
+    with pytest.raises(ValueError, match="the weight matrices do not hold the images' M x N elements"):
+        V.split_best_vp_batch(g["vs"], g["ss"], g["lps"], g["ls"], g["w"][:1], g["lw"], g["ang"])
+    with pytest.raises(ValueError, match="lines holds 6 rows, expected 7"):
+        V.split_best_vp_batch(g["vs"], g["ss"], g["lps"], [g["ls"][0], g["ls"][1][:2]], g["w"], g["lw"], g["ang"])
+    with pytest.raises(ValueError, match="ss holds 2 rows, expected 3"):
+        V.split_best_vp_batch(g["vs"], g["ss"][:1], g["lps"], g["ls"], g["w"], g["lw"], g["ang"])
+    with pytest.raises(ValueError, match="lineWeights holds 4 rows, expected 7"):
+        V.split_best_vp_batch(g["vs"], g["ss"], g["lps"], g["ls"], g["w"], g["lw"][:1], g["ang"])
+    with pytest.raises(ValueError, match="lineAngles holds 8 rows, expected 7"):
+        V.split_best_vp_batch(g["vs"], g["ss"], g["lps"], g["ls"], g["w"], g["lw"], [np.zeros(4), np.zeros(4)])
+    with pytest.raises(ValueError, match="linePoints and vs describe 2 and 1 images"):
+        V.split_best_vp_batch(g["vs"][:1], g["ss"], g["lps"], g["ls"], g["w"], g["lw"], g["ang"])
+
+
+def test_merge_batch_errors_need_no_gpu():
+    from vanishing_points_2017_amd import probability_functions as P, vp_localisation as V
+    g = _batch_inputs()
+    par = P.PDFParams(means=None, weights=np.zeros((2, 400), np.float32), sigma=0.1)
+
+    def merge(ls=g["ls"], ss=g["ss"], lw=g["lw"], lsims=g["lsims"], par=par, vs=g["vs"]):
+        return V.merge_vps_batch(vs, ss, ls, 1e-3, lw, lsims, 1, par, g["lps"])
+
+    for bad in (g["lsims"][:1], [g["lsims"][0], np.zeros((3, 2))], np.zeros(24)):        # 4 x 4 and 3 x 3: 25 elements
+        with pytest.raises(ValueError, match="lsims must hold one N x N matrix per image"):
+            merge(lsims=bad)
+    with pytest.raises(ValueError, match=r"pdfpar.weights must be \(2, 400\), one row per image"):
+        merge(par=par._replace(weights=np.zeros((1, 400), np.float32)))
+    with pytest.raises(ValueError, match="ls holds 6 rows, expected 7"):
+        merge(ls=[g["ls"][0], g["ls"][1][:2]])
+    with pytest.raises(ValueError, match="ss holds 2 rows, expected 3"):
+        merge(ss=g["ss"][:1])
+    with pytest.raises(ValueError, match="lweights holds 4 rows, expected 7"):
+        merge(lw=g["lw"][:1])
+    with pytest.raises(ValueError, match="lps and vs describe 2 and 1 images"):
+        merge(vs=g["vs"][:1])
+    with pytest.raises(ValueError, match="at most 64"):
+        merge(vs=[np.zeros((65, 3)), g["vs"][1]])

@@ -16,6 +16,8 @@ class VpkError(RuntimeError):
 
 
 VPK_ERR_RANGE = -6     # include/vpk.h: the CNN's fp16-pair arithmetic left its calibrated value range
+MAX_VP = 64            # capacity of the EM workgroup's VP arrays (csrc/em_layout.hpp: MAXM)
+VPK_DIST = {"angle": 0, "dotprod": 1, "area": 2}     # include/vpk.h: VPK_DIST_ANGLE, VPK_DIST_DOTPROD, VPK_DIST_AREA
 
 
 class VpkRangeError(VpkError):

@@ -2,6 +2,7 @@
 // (see include/vpk.h).  One kernel; `op` selects the body, which is the single-image entry point's (em_hooks.hpp) inside
 // emstep_device.hpp's loop over the workgroup's images.  Compiled with -ffp-contract=off like the EM unit.
 #include "emstep_device.hpp"
+#include "batch_args.hpp"
 #include "vpk_internal.hpp"
 
 using namespace vpk;
@@ -15,30 +16,13 @@ constexpr long long EMSTEP_NMAX = 32768;
 
 __global__ __launch_bounds__(EMSTEP_THREADS) void emstep_kernel(EmstepArgs a) { emstep_run(a); }
 
-// offsets rise from a value >= 0; the largest size; false = malformed
-bool check_offsets(int batch, const int64_t* off, long long* largest) {
-    if (off[0] < 0) return false;
-    *largest = 0;
-    for (int b = 0; b < batch; ++b) {
-        const long long n = off[b + 1] - off[b];
-        if (n < 0) return false;
-        if (n > *largest) *largest = n;
-    }
-    return true;
-}
-
 // the checks the two ragged entries share; *done = nothing to launch
 int check_batch(vpk_handle* h, int batch, const int64_t* line_off, const int64_t* vp_off, const char* who, bool* done) {
-    *done = true;
-    if (batch < 0) return vpk_fail(h, VPK_ERR_ARG, who);
-    if (batch == 0) return VPK_OK;
-    if (!line_off || !vp_off) return vpk_fail(h, VPK_ERR_ARG, who);
-    long long nmax = 0, mmax = 0;
-    if (!check_offsets(batch, line_off, &nmax) || !check_offsets(batch, vp_off, &mmax)) return vpk_fail(h, VPK_ERR_ARG, who);
-    if (mmax > MAXM) return vpk_fail(h, VPK_ERR_LIMIT, "emstep: an image has more than 64 VPs");
-    if (nmax > EMSTEP_NMAX) return vpk_fail(h, VPK_ERR_LIMIT, "emstep: an image has more than 32768 lines");
-    *done = false;
-    return VPK_OK;
+    const BatchRule r = batch_pair(batch, line_off, vp_off, EMSTEP_NMAX, MAXM);
+    *done = r != BATCH_OK;
+    if (r == BATCH_OK || r == BATCH_EMPTY) return VPK_OK;
+    return vpk_fail(h, batch_code(r), r == BATCH_VPS ? "emstep: an image has more than 64 VPs"
+                                      : r == BATCH_LINES ? "emstep: an image has more than 32768 lines" : who);
 }
 
 // The grid -- min(count, cap), fewer where the slots would not fit half of the device memory --, the workspace, the records
@@ -84,11 +68,8 @@ int vpk_weight_matrix_batch(vpk_handle* h, int batch, const int64_t* line_offset
     int rc = check_batch(h, batch, line_offsets, vp_offsets, "vpk_weight_matrix_batch: bad batch or offsets", &done);
     if (rc || done) return rc;
     if (!lsim_offsets) return vpk_fail(h, VPK_ERR_ARG, "vpk_weight_matrix_batch: null lsim_offsets");
-    for (int b = 0; b < batch; ++b) {
-        const long long n = line_offsets[b + 1] - line_offsets[b];
-        if (lsim_offsets[b] < 0 || lsim_offsets[b + 1] - lsim_offsets[b] < n * n)
-            return vpk_fail(h, VPK_ERR_ARG, "vpk_weight_matrix_batch: lsim_offsets leave image b less than N_b^2 elements");
-    }
+    if (batch_slots(batch, line_offsets, lsim_offsets))
+        return vpk_fail(h, VPK_ERR_ARG, "vpk_weight_matrix_batch: lsim_offsets leave image b less than N_b^2 elements");
     std::vector<EmstepImage> img;
     const long long slot = emstep_plan(batch, (const long long*)line_offsets, (const long long*)vp_offsets,
                                        (const long long*)lsim_offsets, EMSTEP_WEIGHTS, EMSTEP_WAVES, img);

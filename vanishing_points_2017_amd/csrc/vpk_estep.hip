@@ -3,6 +3,7 @@
 // estep_device.hpp's.  Compiled with -ffp-contract=off like the EM unit, whose per-pair expression the "angle" measure
 // restates.
 #include "estep_device.hpp"
+#include "batch_args.hpp"
 #include "vpk_internal.hpp"
 
 #include <vector>
@@ -16,14 +17,6 @@ template <int MEASURE> __global__ __launch_bounds__(ESTEP_TILE) void estep_batch
     estep_block<MEASURE>(a, (long long)block_id());
 }
 
-// offsets rise from a value >= 0
-bool offsets_ok(int batch, const int64_t* off) {
-    if (off[0] < 0) return false;
-    for (int b = 0; b < batch; ++b)
-        if (off[b + 1] < off[b]) return false;
-    return true;
-}
-
 }  // namespace
 
 extern "C" {
@@ -34,10 +27,9 @@ int vpk_estep_batch(vpk_handle* h, int batch, const int64_t* line_offsets, const
     if (!h) return VPK_ERR_ARG;
     if (batch < 0 || (measure != VPK_DIST_ANGLE && measure != VPK_DIST_DOTPROD && measure != VPK_DIST_AREA))
         return vpk_fail(h, VPK_ERR_ARG, "vpk_estep_batch: bad batch or unknown measure");
-    if (batch == 0) return VPK_OK;
-    if (!line_offsets || !vp_offsets) return vpk_fail(h, VPK_ERR_ARG, "vpk_estep_batch: null offsets");
-    if (!offsets_ok(batch, line_offsets) || !offsets_ok(batch, vp_offsets))
-        return vpk_fail(h, VPK_ERR_ARG, "vpk_estep_batch: offsets must not decrease");
+    const BatchRule r = batch_pair(batch, line_offsets, vp_offsets, BATCH_NO_LIMIT, BATCH_NO_LIMIT);   // any N_b, any M_b
+    if (r == BATCH_EMPTY) return VPK_OK;
+    if (r) return vpk_fail(h, VPK_ERR_ARG, r == BATCH_NULL ? "vpk_estep_batch: null offsets" : "vpk_estep_batch: offsets must not decrease");
     const bool chain = p_l_out || p_vl_out;
     const bool split = !chain;
     // header: [line_off | vp_off | mat_off | blk_off], batch + 1 each

@@ -3,6 +3,7 @@
 // (vpk_line_rating_batch; see include/vpk.h).  The arithmetic and both kernel bodies are line_device.hpp's, which the EM
 // workgroup uses too.  Compiled with -ffp-contract=off like the EM unit.
 #include "line_device.hpp"
+#include "batch_args.hpp"
 #include "vpk_internal.hpp"
 
 #include <vector>
@@ -24,17 +25,7 @@ __global__ __launch_bounds__(LINES_THREADS) void line_rating_kernel(LineBatchArg
     line_rating_block(a, block_id() / blocks_per_image, block_id() % blocks_per_image);
 }
 
-// offsets must not decrease; returns the largest image, or -1
-long long largest_image(int batch, const int64_t* offsets) {
-    if (offsets[0] < 0) return -1;
-    long long nmax = 0;
-    for (int b = 0; b < batch; ++b) {
-        const long long n = offsets[b + 1] - offsets[b];
-        if (n < 0 || n > 0x7fffffffLL / 4) return -1;
-        if (n > nmax) nmax = n;
-    }
-    return nmax;
-}
+constexpr long long LINES_NMAX = 0x7fffffffLL / 4;      // the kernels index an image's lp with ints
 
 }  // namespace
 
@@ -46,13 +37,10 @@ int vpk_line_similarity_batch(vpk_handle* h, int batch, const int64_t* offsets, 
     if (batch < 0 || !(sigma > 0)) return vpk_fail(h, VPK_ERR_ARG, "vpk_line_similarity_batch: bad argument");
     if (batch == 0) return VPK_OK;
     if (!offsets || !mat_offsets) return vpk_fail(h, VPK_ERR_ARG, "vpk_line_similarity_batch: null offsets");
-    const long long nmax = largest_image(batch, offsets);
-    if (nmax < 0) return vpk_fail(h, VPK_ERR_ARG, "vpk_line_similarity_batch: offsets must not decrease");
-    for (int b = 0; b < batch; ++b) {
-        const long long n = offsets[b + 1] - offsets[b];
-        if (mat_offsets[b] < 0 || mat_offsets[b + 1] - mat_offsets[b] < n * n)
-            return vpk_fail(h, VPK_ERR_ARG, "vpk_line_similarity_batch: mat_offsets leave image b less than N_b^2 elements");
-    }
+    long long nmax;
+    if (batch_offsets(batch, offsets, &nmax, LINES_NMAX)) return vpk_fail(h, VPK_ERR_ARG, "vpk_line_similarity_batch: offsets must not decrease");
+    if (batch_slots(batch, offsets, mat_offsets))
+        return vpk_fail(h, VPK_ERR_ARG, "vpk_line_similarity_batch: mat_offsets leave image b less than N_b^2 elements");
     if (nmax == 0) return VPK_OK;
     if (!lp || !lsim_out) return vpk_fail(h, VPK_ERR_ARG, "vpk_line_similarity_batch: null buffer");
     const long long bpi = (nmax + LS_RB - 1) / LS_RB;
@@ -81,8 +69,8 @@ int vpk_line_rating_batch(vpk_handle* h, int batch, const int64_t* offsets, cons
         return vpk_fail(h, VPK_ERR_ARG, "vpk_line_rating_batch: bad argument (sigma > 0, 1 <= k2 <= k1 <= 16)");
     if (batch == 0) return VPK_OK;
     if (!offsets) return vpk_fail(h, VPK_ERR_ARG, "vpk_line_rating_batch: null offsets");
-    const long long nmax = largest_image(batch, offsets);
-    if (nmax < 0) return vpk_fail(h, VPK_ERR_ARG, "vpk_line_rating_batch: offsets must not decrease");
+    long long nmax;
+    if (batch_offsets(batch, offsets, &nmax, LINES_NMAX)) return vpk_fail(h, VPK_ERR_ARG, "vpk_line_rating_batch: offsets must not decrease");
     if (nmax == 0 || (!lscore_out && !langle_out && !llen_out)) return VPK_OK;
     if (!lp) return vpk_fail(h, VPK_ERR_ARG, "vpk_line_rating_batch: null buffer");
     constexpr int rpb = LINES_THREADS / ROWG;

@@ -2,6 +2,7 @@
 // vpk_vp_merge_batch (see include/vpk.h).  One workgroup per image runs one operation on the caller's VP set through the
 // EM workgroup's own device functions (vpset_device.hpp).  Compiled with -ffp-contract=off like the EM unit.
 #include "vpset_device.hpp"
+#include "batch_args.hpp"
 #include "vpk_internal.hpp"
 
 #include <algorithm>
@@ -16,18 +17,6 @@ constexpr size_t VPSET_LDS_BYTES = SH_BYTES + WT_DOUBLES * sizeof(double);   // 
 constexpr long long VPSET_NMAX = 32768;                // cluster2 indexes an n x n matrix with ints
 
 __global__ __launch_bounds__(VPSET_THREADS) void vpset_kernel(VpsetArgs a) { vpset_run(a); }
-
-// offsets rise from a value >= 0; fills sizes' maxima; false = malformed
-bool check_offsets(int batch, const int64_t* off, long long* largest) {
-    if (off[0] < 0) return false;
-    *largest = 0;
-    for (int b = 0; b < batch; ++b) {
-        const long long n = off[b + 1] - off[b];
-        if (n < 0) return false;
-        if (n > *largest) *largest = n;
-    }
-    return true;
-}
 
 // header: [line_off | vp_off | mat_off | ws_off] (batch + 1 each) and the active list; returns the number of active images
 int build_header(int batch, const int64_t* line_off, const int64_t* vp_off, int op, std::vector<int64_t>& hdr, long long* ws_doubles,
@@ -77,16 +66,11 @@ int launch(vpk_handle* h, int batch, const std::vector<int64_t>& hdr, int active
 
 // the checks the three entries share; *done = nothing to launch
 int check_batch(vpk_handle* h, int batch, const int64_t* line_off, const int64_t* vp_off, const char* who, bool* done) {
-    *done = true;
-    if (batch < 0) return vpk_fail(h, VPK_ERR_ARG, who);
-    if (batch == 0) return VPK_OK;
-    if (!line_off || !vp_off) return vpk_fail(h, VPK_ERR_ARG, who);
-    long long nmax = 0, mmax = 0;
-    if (!check_offsets(batch, line_off, &nmax) || !check_offsets(batch, vp_off, &mmax)) return vpk_fail(h, VPK_ERR_ARG, who);
-    if (mmax > MAXM) return vpk_fail(h, VPK_ERR_LIMIT, "vpset: an image has more than 64 VPs");
-    if (nmax > VPSET_NMAX) return vpk_fail(h, VPK_ERR_LIMIT, "vpset: an image has more than 32768 lines");
-    *done = false;
-    return VPK_OK;
+    const BatchRule r = batch_pair(batch, line_off, vp_off, VPSET_NMAX, MAXM);
+    *done = r != BATCH_OK;
+    if (r == BATCH_OK || r == BATCH_EMPTY) return VPK_OK;
+    return vpk_fail(h, batch_code(r), r == BATCH_VPS ? "vpset: an image has more than 64 VPs"
+                                      : r == BATCH_LINES ? "vpset: an image has more than 32768 lines" : who);
 }
 
 }  // namespace
@@ -148,11 +132,11 @@ int vpk_vp_merge_batch(vpk_handle* h, int batch, const int64_t* line_offsets, co
     int rc = check_batch(h, batch, line_offsets, vp_offsets, "vpk_vp_merge_batch: bad batch or offsets", &done);
     if (rc || done) return rc;
     if (!lsim_offsets || !(prior_sigma > 0)) return vpk_fail(h, VPK_ERR_ARG, "vpk_vp_merge_batch: null lsim_offsets or sigma not > 0");
+    if (batch_slots(batch, line_offsets, lsim_offsets))
+        return vpk_fail(h, VPK_ERR_ARG, "vpk_vp_merge_batch: lsim_offsets leave image b less than N_b^2 elements");
     long long nmax = 0, mmax = 0;
     for (int b = 0; b < batch; ++b) {
         const long long n = line_offsets[b + 1] - line_offsets[b], m = vp_offsets[b + 1] - vp_offsets[b];
-        if (lsim_offsets[b] < 0 || lsim_offsets[b + 1] - lsim_offsets[b] < n * n)
-            return vpk_fail(h, VPK_ERR_ARG, "vpk_vp_merge_batch: lsim_offsets leave image b less than N_b^2 elements");
         if (n > 0 && m > 0) { nmax = std::max(nmax, n); mmax = std::max(mmax, m); }
     }
     const EmLayout L = em_layout((int)nmax, (int)em_align((size_t)std::max(mmax, 1LL), 8), VPSET_THREADS / 64, true, false);

@@ -9,10 +9,10 @@ import numpy as np
 from . import _lib
 from .runtime import get_runtime
 
-MAX_VP = 64
+MAX_VP = _lib.MAX_VP
 
 
-EM_MEASURES = {"angle": 0, "dotprod": 1}      # include/vpk.h: VPK_DIST_ANGLE, VPK_DIST_DOTPROD
+EM_MEASURES = {k: _lib.VPK_DIST[k] for k in ("angle", "dotprod")}
 
 
 def _measure(distance_measure):

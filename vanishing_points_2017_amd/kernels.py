@@ -3,11 +3,8 @@ reference's individual functions).  Each call copies its inputs to HBM, launches
 and copies the result back -- for tests and debugging, not for throughput."""
 import numpy as np
 
+from .ragged import to_device as _up
 from .runtime import get_runtime
-
-
-def _up(rt, a, dtype):
-    return rt.torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(rt.tdev)
 
 
 def pairwise(lp, device=0):

@@ -23,15 +23,15 @@ from collections import namedtuple
 
 import numpy as np
 
+from . import ragged
+from .ragged import offsets_of as _offsets_of    # the name tests/test_gpu_estep_surface.py builds its offsets with
+from ._lib import VPK_DIST
+from .runtime import get_runtime
+
 PDFParams = namedtuple('PDFParams', 'means weights sigma')
 PDF = namedtuple('PDF', 'v lv vl l lvsq angles')
 
 GRID = 20     # the CNN's response map is GRID x GRID (cnn/deploy.prototxt:283-296)
-
-
-def _runtime(device):
-    from .runtime import get_runtime
-    return get_runtime(device)
 
 
 def _sigma(confidence):
@@ -53,14 +53,6 @@ def _grid_means():
     return means
 
 
-def _to_device(rt, a, dtype):
-    """``a`` (NumPy array or torch tensor, any device) as a contiguous tensor of ``dtype`` on the runtime's GPU."""
-    t = rt.torch
-    if not isinstance(a, t.Tensor):
-        a = t.from_numpy(np.ascontiguousarray(a))
-    return a.to(device=rt.tdev, dtype=dtype).contiguous()
-
-
 def _check_maps(maps):
     """Batch size of (B, 20, 20) response maps (one map: (20, 20)); anything else raises before the GPU is touched."""
     shape = tuple(maps.shape)
@@ -78,7 +70,7 @@ def _is_params(x):
 def _maps_to_device(rt, maps):
     """The response maps as a (B, 400) float32 device tensor.  The kernels only read it, so the caller's maps are never
     written, also where no copy is made."""
-    return _to_device(rt, maps, rt.torch.float32).reshape(_check_maps(maps), GRID * GRID)
+    return ragged.to_device(rt, maps, np.float32).reshape(_check_maps(maps), GRID * GRID)
 
 
 def _prior_weights(rt, d_maps, sigma):
@@ -112,10 +104,10 @@ def pdf_params_batch(maps, confidence=1.282, device=0):
     sigma float), the arrays on the device."""
     _check_maps(maps)
     sigma = _sigma(confidence)
-    rt = _runtime(device)
+    rt = get_runtime(device)
     with rt.on_stream():
         weights = _prior_weights(rt, _maps_to_device(rt, maps), sigma)
-        means = _to_device(rt, _grid_means(), rt.torch.float64)
+        means = ragged.to_device(rt, _grid_means(), np.float64)
     rt.synchronize()
     return PDFParams(means=means, weights=weights, sigma=sigma)
 
@@ -125,14 +117,14 @@ def _params_on_device(rt, maps_or_params):
     (ncomp,) or (B, ncomp) and whose means are (ncomp, 2) or (B, ncomp, 2)."""
     t = rt.torch
     if _is_params(maps_or_params):
-        means = _to_device(rt, maps_or_params.means, t.float64)
-        weights = _to_device(rt, maps_or_params.weights, t.float64)      # a float32 weight enters :38 as its double
+        means = ragged.to_device(rt, maps_or_params.means, np.float64)
+        weights = ragged.to_device(rt, maps_or_params.weights, np.float64)      # a float32 weight enters :38 as its double
         if weights.dim() == 1:
             weights = weights.reshape(1, -1)
         return means, weights, float(maps_or_params.sigma)
     sigma = _sigma(1.282)
     weights = _prior_weights(rt, _maps_to_device(rt, maps_or_params), sigma).double()
-    return _to_device(rt, _grid_means(), t.float64), weights, sigma
+    return ragged.to_device(rt, _grid_means(), np.float64), weights, sigma
 
 
 def calc_pdf_batch(maps_or_params, x, y, device=0):
@@ -141,11 +133,11 @@ def calc_pdf_batch(maps_or_params, x, y, device=0):
     same points for every mixture -- or (B, P).  Returns a (B, P) float64 device tensor."""
     if not _is_params(maps_or_params):
         _check_maps(maps_or_params)
-    rt = _runtime(device)
+    rt = get_runtime(device)
     t = rt.torch
     with rt.on_stream():
         means, weights, sigma = _params_on_device(rt, maps_or_params)
-        pts = t.stack((_to_device(rt, x, t.float64), _to_device(rt, y, t.float64)), dim=-1).contiguous()
+        pts = t.stack((ragged.to_device(rt, x, np.float64), ragged.to_device(rt, y, np.float64)), dim=-1).contiguous()
         _, pdf = _mixture(rt, means, weights, sigma, pts)
     rt.synchronize()
     return pdf
@@ -157,10 +149,10 @@ def vp_prior_batch(maps, vps, device=0):
     tensors."""
     if not _is_params(maps):
         _check_maps(maps)
-    rt = _runtime(device)
+    rt = get_runtime(device)
     with rt.on_stream():
         means, weights, sigma = _params_on_device(rt, maps)
-        v = _to_device(rt, vps, rt.torch.float64)
+        v = ragged.to_device(rt, vps, np.float64)
         if v.shape[-1] != 3:
             raise ValueError("vps must be (M, 3) or (B, M, 3)")
         angles, pdf = _mixture(rt, means, weights, sigma, v, want_angles=True)
@@ -169,42 +161,13 @@ def vp_prior_batch(maps, vps, device=0):
 
 
 # ---- the E-step: device tensors -------------------------------------------------------------------------------------------
-DISTANCE_MEASURES = {"angle": 0, "dotprod": 1, "area": 2}     # include/vpk.h: VPK_DIST_*
+DISTANCE_MEASURES = dict(VPK_DIST)
 
 
 def _measure(distance_measure):
     if not isinstance(distance_measure, str) or distance_measure not in DISTANCE_MEASURES:
         raise ValueError("distance_measure %r: one of \"angle\", \"dotprod\", \"area\"" % (distance_measure,))
     return DISTANCE_MEASURES[distance_measure]
-
-
-def _offsets_of(sizes):
-    return np.concatenate(([0], np.cumsum(sizes, dtype=np.int64))).astype(np.int64)
-
-
-def _cat_rows(rt, xs, width, what):
-    """A list of per-image (rows, width) arrays or tensors ((rows,) for width 0) as one contiguous float64 device tensor,
-    and the host offsets of the images' rows."""
-    t = rt.torch
-    tail = (width,) if width else ()
-    if not any(isinstance(x, t.Tensor) for x in xs):         # host arrays: one concatenation, one upload
-        parts = [np.asarray(x, dtype=np.float64) for x in xs]
-    else:
-        parts = [_to_device(rt, x, t.float64) for x in xs]
-    for d in parts:
-        if tuple(d.shape[1:]) != tail or len(d.shape) != len(tail) + 1:
-            raise ValueError("%s: every image needs shape (rows,%s), got %r" % (what, " %d" % width if width else "", tuple(d.shape)))
-    off = _offsets_of([int(p.shape[0]) for p in parts])
-    if not parts:
-        return t.zeros((0,) + tail, dtype=t.float64, device=rt.tdev), off
-    if isinstance(parts[0], t.Tensor):
-        return t.cat(parts).contiguous(), off
-    return _to_device(rt, np.concatenate(parts), t.float64), off
-
-
-def _off_ptr(a):
-    import ctypes
-    return a.ctypes.data_as(ctypes.c_void_p)
 
 
 def _estep(rt, lo, vo, d_lp, d_l, d_v, d_s, d_pv, measure, want):
@@ -216,36 +179,29 @@ def _estep(rt, lo, vo, d_lp, d_l, d_v, d_s, d_pv, measure, want):
     # image that gets no workgroup stay 0
     out = {k: ((t.zeros if k in ('s', 'p_l') else t.empty)((shapes[k],), dtype=t.float64, device=rt.tdev) if k in want else None)
            for k in shapes}
-    rt.check(rt.lib.vpk_estep_batch(rt.h, lo.shape[0] - 1, _off_ptr(lo), _off_ptr(vo), rt.ptr(d_lp), rt.ptr(d_l), rt.ptr(d_v),
-                                    rt.ptr(d_s), rt.ptr(d_pv), measure, rt.ptr(out['s']), rt.ptr(out['lvsq']),
+    rt.check(rt.lib.vpk_estep_batch(rt.h, lo.shape[0] - 1, ragged.off_ptr(lo), ragged.off_ptr(vo), rt.ptr(d_lp), rt.ptr(d_l),
+                                    rt.ptr(d_v), rt.ptr(d_s), rt.ptr(d_pv), measure, rt.ptr(out['s']), rt.ptr(out['lvsq']),
                                     rt.ptr(out['p_lv']), rt.ptr(out['p_l']), rt.ptr(out['p_vl'])))
     return out
 
 
-def _estep_inputs(rt, vs, ls, lps, measure):
-    d_lp, lo = _cat_rows(rt, lps, 4, "lps")
-    d_v, vo = _cat_rows(rt, vs, 3, "vs")
+def _estep_offsets(vs, ls, lps, measure):
+    """(line offsets, VP offsets) of the E-step's lists, every image held to its row shape; host only."""
+    lo = ragged.strict_offsets(lps, (4,), "lps")
+    vo = ragged.strict_offsets(vs, (3,), "vs")
     if lo.shape != vo.shape:
         raise ValueError("lps and vs describe %d and %d images" % (lo.shape[0] - 1, vo.shape[0] - 1))
-    d_l = None
     if measure == DISTANCE_MEASURES["dotprod"]:
         if ls is None or any(x is None for x in ls):
             raise ValueError("the \"dotprod\" measure reads the homogeneous lines: ls is needed")
-        d_l, llo = _cat_rows(rt, ls, 3, "ls")
-        if not np.array_equal(llo, lo):
+        if not np.array_equal(ragged.strict_offsets(ls, (3,), "ls"), lo):
             raise ValueError("ls and lps differ in their images' line counts")
-    return d_lp, d_l, d_v, lo, vo
+    return lo, vo
 
 
-def _split_mats(flat, lo, vo, transposed):
-    """Per image the (M, N) matrix of a flat [m][n] buffer, or its (N, M) transposed view."""
-    out, at = [], 0
-    for b in range(lo.shape[0] - 1):
-        n, m = int(lo[b + 1] - lo[b]), int(vo[b + 1] - vo[b])
-        mat = flat[at:at + m * n].reshape(m, n)
-        out.append(mat.t() if transposed else mat)
-        at += m * n
-    return out
+def _estep_inputs(rt, vs, ls, lps, measure):
+    d_lp, d_v = ragged.upload(rt, lps, np.float64, (4,)), ragged.upload(rt, vs, np.float64, (3,))
+    return d_lp, ragged.upload(rt, ls, np.float64, (3,)) if measure == DISTANCE_MEASURES["dotprod"] else None, d_v
 
 
 def calc_lvsq_batch(vs, ls, lps, distance_measure="angle", device=0):
@@ -256,13 +212,14 @@ def calc_lvsq_batch(vs, ls, lps, distance_measure="angle", device=0):
     chain crosses the VPs here, so the launch also splits the VP range: a few lines against thousands of hypotheses still
     fill the machine."""
     measure = _measure(distance_measure)
-    rt = _runtime(device)
+    lo, vo = _estep_offsets(vs, ls, lps, measure)
+    rt = get_runtime(device)
     with rt.on_stream():
-        d_lp, d_l, d_v, lo, vo = _estep_inputs(rt, vs, ls, lps, measure)
+        d_lp, d_l, d_v = _estep_inputs(rt, vs, ls, lps, measure)
         d_s = rt.torch.ones((int(vo[-1]),), dtype=rt.torch.float64, device=rt.tdev)
         out = _estep(rt, lo, vo, d_lp, d_l, d_v, d_s, None, measure, ('lvsq',))
     rt.synchronize()
-    return _split_mats(out['lvsq'], lo, vo, True)
+    return ragged.split_mats(out['lvsq'], lo, vo, True)
 
 
 def _prior_ragged(rt, pdfpars_or_maps, d_v, vo):
@@ -299,16 +256,17 @@ def calc_probabilities_batch(pdfpars_or_maps, vs, ls, lps, ss, distance_measure=
     measure = _measure(distance_measure)
     if not _is_params(pdfpars_or_maps):
         _check_maps(pdfpars_or_maps)
-    rt = _runtime(device)
+    lo, vo = _estep_offsets(vs, ls, lps, measure)
+    if not np.array_equal(ragged.strict_offsets(ss, (), "ss"), vo):
+        raise ValueError("ss and vs differ in their images' VP counts")
+    rt = get_runtime(device)
     with rt.on_stream():
-        d_lp, d_l, d_v, lo, vo = _estep_inputs(rt, vs, ls, lps, measure)
-        d_s, so = _cat_rows(rt, ss, 0, "ss")
-        if not np.array_equal(so, vo):
-            raise ValueError("ss and vs differ in their images' VP counts")
+        d_lp, d_l, d_v = _estep_inputs(rt, vs, ls, lps, measure)
+        d_s = ragged.upload(rt, ss, np.float64)
         angles, p_v = _prior_ragged(rt, pdfpars_or_maps, d_v, vo)
         out = _estep(rt, lo, vo, d_lp, d_l, d_v, d_s, p_v, measure, ('s', 'lvsq', 'p_lv', 'p_l', 'p_vl'))
     rt.synchronize()
-    lvsq, p_lv, p_vl = (_split_mats(out[k], lo, vo, k != 'p_vl') for k in ('lvsq', 'p_lv', 'p_vl'))
+    lvsq, p_lv, p_vl = (ragged.split_mats(out[k], lo, vo, k != 'p_vl') for k in ('lvsq', 'p_lv', 'p_vl'))
     pdfs, s_out = [], []
     for b in range(lo.shape[0] - 1):
         n0, n1, m0, m1 = int(lo[b]), int(lo[b + 1]), int(vo[b]), int(vo[b + 1])

@@ -13,6 +13,7 @@ import numpy as np
 
 from . import coordinate_conversion as coconv
 from . import probability_functions as prob
+from .ragged import offsets_of
 
 CYAN_LINE = (0, 255, 255)                                        # c='c' on the image (:107)
 MARK_RGB = {'y': (191, 191, 0), 'g': (0, 128, 0), 'c': (0, 191, 191)}   # matplotlib's single-letter colours 'y', 'g', 'c'
@@ -163,8 +164,8 @@ def overlay_batch(panels, prims, discs, device=0):
     for p in panels:
         if p.ndim != 3 or p.shape[2] != 3 or (discs and p.shape[0] != p.shape[1]):
             raise ValueError("a panel is H x W x 3%s (got %s)" % (", square for markers" if discs else "", p.shape,))
-    pix = np.concatenate(([0], np.cumsum([p.size for p in panels]))).astype(np.int64)
-    off = np.concatenate(([0], np.cumsum([pr[2].size for pr in prims]))).astype(np.int64)
+    pix = offsets_of([p.size for p in panels])
+    off = offsets_of([pr[2].size for pr in prims])
     cols = 2 if discs else 4
     geom = np.concatenate([pr[0].reshape(-1, cols) for pr in prims])
     rgba = np.concatenate([pr[1].reshape(-1, 4) for pr in prims])

@@ -36,7 +36,9 @@ import numpy as np
 
 from . import em as _em
 from . import kernels as _kernels
-from ._lib import host_i64
+from . import ragged
+from .probability_functions import PDFParams, _grid_means
+from .runtime import get_runtime
 
 
 def expectation_maximisation(l, lp, cnn_response, num_iter=100, sphere_image=None, init_vp=None,
@@ -114,11 +116,6 @@ K1_MAX = 16      # capacity of the rating kernel's neighbour lists (csrc/line_de
 MAT_ALIGN = 16   # matrices of calc_lsim_batch start at multiples of 16 elements: whole 128-byte lines where N allows
 
 
-def _runtime(device):
-    from .runtime import get_runtime
-    return get_runtime(device)
-
-
 def _check_sigma(sigma):
     sigma = float(sigma)
     if not sigma > 0:
@@ -147,38 +144,13 @@ def _check_lp(lp):
     return lp
 
 
-def _is_device_pair(lps):
-    return isinstance(lps, tuple) and len(lps) == 2 and hasattr(lps[0], "data_ptr")
-
-
 def _check_batch(lps):
     """The image sizes' offsets (host int64) of ``lps``; raises before the GPU is touched."""
-    if _is_device_pair(lps):
-        d_lp, offsets = lps
-        offsets = host_i64(offsets)
-        if d_lp.dim() != 2 or d_lp.shape[1] != 4:
+    if ragged.is_device_pair(lps):
+        if lps[0].dim() != 2 or lps[0].shape[1] != 4:
             raise ValueError("the device form of lps is a (sum N, 4) tensor and its offsets")
-        if offsets.ndim != 1 or offsets.shape[0] < 1 or offsets[0] != 0 or (np.diff(offsets) < 0).any() or \
-                offsets[-1] != d_lp.shape[0]:
-            raise ValueError("offsets must rise from 0 to the number of lines (%d)" % d_lp.shape[0])
-        return offsets
-    sizes = [_check_lp(a).shape[0] for a in lps]
-    return np.concatenate(([0], np.cumsum(sizes, dtype=np.int64))).astype(np.int64)
-
-
-def _lines_on_device(rt, lps):
-    """(sum N, 4) float64 device tensor of a batch; the caller's arrays are only read."""
-    t = rt.torch
-    if _is_device_pair(lps):
-        return lps[0].to(device=rt.tdev, dtype=t.float64).contiguous()
-    arrs = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 4) for a in lps]
-    cat = np.concatenate(arrs) if arrs else np.zeros((0, 4))
-    return t.from_numpy(cat).to(rt.tdev)
-
-
-def _off_ptr(a):
-    import ctypes
-    return a.ctypes.data_as(ctypes.c_void_p)
+        return ragged.check_offsets(lps[1], lps[0].shape[0], "offsets", "the number of lines (%d)" % lps[0].shape[0])
+    return ragged.offsets_of([_check_lp(a).shape[0] for a in lps])
 
 
 def _rating(lps, k1, k2, sigma, want, device):
@@ -186,13 +158,12 @@ def _rating(lps, k1, k2, sigma, want, device):
     k1, k2 = _check_knn(k1, k2)
     sigma = _check_sigma(sigma)
     offsets = _check_batch(lps)
-    rt = _runtime(device)
+    rt = get_runtime(device)
     t = rt.torch
-    total = int(offsets[-1])
     with rt.on_stream():
-        d_lp = _lines_on_device(rt, lps)
-        outs = [t.empty((total,), dtype=t.float64, device=rt.tdev) if w else None for w in want]
-        rt.check(rt.lib.vpk_line_rating_batch(rt.h, offsets.shape[0] - 1, _off_ptr(offsets), rt.ptr(d_lp), k1, k2, sigma,
+        d_lp = ragged.upload(rt, lps, np.float64, (4,), pair=True)
+        outs = [t.empty((int(offsets[-1]),), dtype=t.float64, device=rt.tdev) if w else None for w in want]
+        rt.check(rt.lib.vpk_line_rating_batch(rt.h, offsets.shape[0] - 1, ragged.off_ptr(offsets), rt.ptr(d_lp), k1, k2, sigma,
                                               rt.ptr(outs[0]), rt.ptr(outs[1]), rt.ptr(outs[2])))
     rt.synchronize()
     return outs, offsets
@@ -204,15 +175,14 @@ def calc_lsim_batch(lps, sigma=0.1, device=0):
     sigma = _check_sigma(sigma)
     offsets = _check_batch(lps)
     sizes = np.diff(offsets)
-    mat = np.zeros(offsets.shape[0], dtype=np.int64)
-    np.cumsum((sizes * sizes + MAT_ALIGN - 1) // MAT_ALIGN * MAT_ALIGN, out=mat[1:])
-    rt = _runtime(device)
+    mat = ragged.offsets_of((sizes * sizes + MAT_ALIGN - 1) // MAT_ALIGN * MAT_ALIGN)
+    rt = get_runtime(device)
     t = rt.torch
     with rt.on_stream():
-        d_lp = _lines_on_device(rt, lps)
+        d_lp = ragged.upload(rt, lps, np.float64, (4,), pair=True)
         buf = t.empty((int(mat[-1]),), dtype=t.float64, device=rt.tdev)
-        rt.check(rt.lib.vpk_line_similarity_batch(rt.h, sizes.shape[0], _off_ptr(offsets), rt.ptr(d_lp), sigma, _off_ptr(mat),
-                                                  rt.ptr(buf)))
+        rt.check(rt.lib.vpk_line_similarity_batch(rt.h, sizes.shape[0], ragged.off_ptr(offsets), rt.ptr(d_lp), sigma,
+                                                  ragged.off_ptr(mat), rt.ptr(buf)))
     rt.synchronize()
     return [buf[int(m):int(m) + int(n) * int(n)].view(int(n), int(n)) for m, n in zip(mat[:-1], sizes)]
 
@@ -288,48 +258,6 @@ def _check_measure(distance_measure):
         raise ValueError("distance_measure %r is not supported: only \"angle\" runs on the GPU" % (distance_measure,))
 
 
-def _offsets_of(sizes):
-    return np.concatenate(([0], np.cumsum(sizes, dtype=np.int64))).astype(np.int64)
-
-
-def _check_offsets(off, total, what):
-    off = host_i64(off)
-    if off.ndim != 1 or off.shape[0] < 1 or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != total:
-        raise ValueError("%s offsets must rise from 0 to %d" % (what, total))
-    return off
-
-
-def _cat(rt, x, dtype, tail=()):
-    """A list of per-image arrays or tensors, or one concatenated array or tensor, as one contiguous device tensor of
-    shape (-1,) + tail.  The caller's data is only read."""
-    t = rt.torch
-    if isinstance(x, (list, tuple)):
-        if len(x) and isinstance(x[0], t.Tensor):
-            x = t.cat([a.to(device=rt.tdev, dtype=dtype).reshape((-1,) + tail) for a in x])
-        else:
-            npd = {t.float64: np.float64, t.float32: np.float32, t.int64: np.int64, t.uint8: np.uint8}[dtype]
-            arrs = [np.ascontiguousarray(a, dtype=npd).reshape((-1,) + tail) for a in x]
-            x = np.concatenate(arrs) if arrs else np.zeros((0,) + tail, dtype=npd)
-    if not isinstance(x, t.Tensor):
-        x = t.from_numpy(np.ascontiguousarray(x))
-    return x.to(device=rt.tdev, dtype=dtype).contiguous().reshape((-1,) + tail)
-
-
-def _sizes(x, offsets, what):
-    """Host int64 offsets of a batch given as a list (sizes from the list) or concatenated (offsets from the caller)."""
-    if isinstance(x, (list, tuple)):
-        return _offsets_of([int(a.shape[0]) if hasattr(a, 'shape') else len(a) for a in x])
-    if offsets is None:
-        raise ValueError("%s is one concatenated array: its offsets are needed" % what)
-    return _check_offsets(offsets, int(x.shape[0]), what)
-
-
-def _check_vp_limit(vp_off):
-    m = np.diff(vp_off)
-    if m.size and m.max() > MAX_VP:
-        raise ValueError("%d VPs: at most %d are supported" % (m.max(), MAX_VP))
-
-
 def calc_vp_line_counts_batch(vps, lps, ss, decision_metrics, lweights, distance_measure="angle", thresh=2.57,
                               vp_assocs=None, line_offsets=None, vp_offsets=None, device=0):
     """calc_vp_line_counts for many images in one launch.  Every argument is a list with one array per image -- vp (M_b, 3),
@@ -338,33 +266,31 @@ def calc_vp_line_counts_batch(vps, lps, ss, decision_metrics, lweights, distance
     flat, image after image.  Returns (counts, counts_weighted, vp_assoc, line_offsets, vp_offsets): device tensors of
     sum M, sum M and sum N (int64) elements.  An image without lines counts nothing; one without VPs associates nothing."""
     _check_measure(distance_measure)
-    lo = _sizes(lps, line_offsets, "lps")
-    vo = _sizes(vps, vp_offsets, "vps")
-    if lo.shape != vo.shape:
-        raise ValueError("lps and vps describe %d and %d images" % (lo.shape[0] - 1, vo.shape[0] - 1))
-    _check_vp_limit(vo)
-    rt = _runtime(device)
+    lo = ragged.batch_offsets(lps, line_offsets, "lps")
+    vo = ragged.batch_offsets(vps, vp_offsets, "vps")
+    ragged.check_images(lo, vo, "lps", "vps")
+    if decision_metrics is None and vp_assocs is None:
+        raise ValueError("decision_metrics or vp_assocs is needed")
+    if decision_metrics is not None and ragged.total(decision_metrics) != ragged.mats_total(lo, vo):
+        raise ValueError("the decision metrics hold %d elements, the images' M x N sum to %d"
+                         % (ragged.total(decision_metrics), ragged.mats_total(lo, vo)))
+    for x, n, what in ((ss, vo[-1], "ss"), (lweights, lo[-1], "lweights"), (vp_assocs, lo[-1], "vp_assocs")):
+        if x is not None:
+            ragged.check_total(x, n, what)
+    rt = get_runtime(device)
     t = rt.torch
     with rt.on_stream():
-        d_lp = _cat(rt, lps, t.float64, (4,))
-        d_v = _cat(rt, vps, t.float64, (3,))
-        d_s = _cat(rt, ss, t.float64)
-        d_lw = _cat(rt, lweights, t.float64)
-        d_w = _cat(rt, decision_metrics, t.float64) if decision_metrics is not None else None
-        d_ain = _cat(rt, vp_assocs, t.int64) if vp_assocs is not None else None
-        if d_w is None and d_ain is None:
-            raise ValueError("decision_metrics or vp_assocs is needed")
-        need = int((np.diff(lo) * np.diff(vo)).sum())
-        if d_w is not None and d_w.shape[0] != need:
-            raise ValueError("the decision metrics hold %d elements, the images' M x N sum to %d" % (d_w.shape[0], need))
-        for a, n, what in ((d_s, vo[-1], "ss"), (d_lw, lo[-1], "lweights"), (d_ain, lo[-1], "vp_assocs")):
-            if a is not None and a.shape[0] != n:
-                raise ValueError("%s holds %d elements, expected %d" % (what, a.shape[0], n))
+        d_lp = ragged.upload(rt, lps, np.float64, (4,))
+        d_v = ragged.upload(rt, vps, np.float64, (3,))
+        d_s = ragged.upload(rt, ss, np.float64)
+        d_lw = ragged.upload(rt, lweights, np.float64)
+        d_w = ragged.upload(rt, decision_metrics, np.float64) if decision_metrics is not None else None
+        d_ain = ragged.upload(rt, vp_assocs, np.int64) if vp_assocs is not None else None
         counts = t.zeros((int(vo[-1]),), dtype=t.float64, device=rt.tdev)
         counts_w = t.zeros_like(counts)
         assoc = d_ain.clone() if d_ain is not None else t.full((int(lo[-1]),), -1, dtype=t.int64, device=rt.tdev)
-        rt.check(rt.lib.vpk_vp_line_counts_batch(rt.h, lo.shape[0] - 1, _off_ptr(lo), _off_ptr(vo), rt.ptr(d_lp), rt.ptr(d_v),
-                                                 rt.ptr(d_s), rt.ptr(d_w), rt.ptr(d_lw), float(thresh), rt.ptr(d_ain),
+        rt.check(rt.lib.vpk_vp_line_counts_batch(rt.h, lo.shape[0] - 1, ragged.off_ptr(lo), ragged.off_ptr(vo), rt.ptr(d_lp),
+                                                 rt.ptr(d_v), rt.ptr(d_s), rt.ptr(d_w), rt.ptr(d_lw), float(thresh), rt.ptr(d_ain),
                                                  rt.ptr(counts), rt.ptr(counts_w), rt.ptr(assoc)))
     rt.synchronize()
     return counts, counts_w, assoc, lo, vo
@@ -406,27 +332,25 @@ def split_best_vp_batch(vs, ss, linePoints, lines, weightMatrices, lineWeights, 
     every line of the worst VP, -1 elsewhere; and the host offsets 'line_offsets', 'vp_offsets', 'out_offsets'."""
     if numClusters != 2:
         raise ValueError("numClusters = %r: only 2 is supported" % (numClusters,))
-    lo = _sizes(linePoints, line_offsets, "linePoints")
-    vo = _sizes(vs, vp_offsets, "vs")
-    if lo.shape != vo.shape:
-        raise ValueError("linePoints and vs describe %d and %d images" % (lo.shape[0] - 1, vo.shape[0] - 1))
-    _check_vp_limit(vo)
+    lo = ragged.batch_offsets(linePoints, line_offsets, "linePoints")
+    vo = ragged.batch_offsets(vs, vp_offsets, "vs")
+    ragged.check_images(lo, vo, "linePoints", "vs")
+    if ragged.total(weightMatrices) != ragged.mats_total(lo, vo):
+        raise ValueError("the weight matrices do not hold the images' M x N elements")
+    ragged.check_total(lines, lo[-1], "lines", 3, "rows")
+    for x, n, what in ((ss, vo[-1], "ss"), (lineWeights, lo[-1], "lineWeights"), (lineAngles, lo[-1], "lineAngles")):
+        ragged.check_total(x, n, what, unit="rows")
     B = lo.shape[0] - 1
-    rt = _runtime(device)
+    rt = get_runtime(device)
     t = rt.torch
     with rt.on_stream():
-        d_lp = _cat(rt, linePoints, t.float64, (4,))
-        d_l = _cat(rt, lines, t.float64, (3,))
-        d_v = _cat(rt, vs, t.float64, (3,))
-        d_s = _cat(rt, ss, t.float64)
-        d_w = _cat(rt, weightMatrices, t.float64)
-        d_lw = _cat(rt, lineWeights, t.float64)
-        d_la = _cat(rt, lineAngles, t.float64)
-        if d_w.shape[0] != int((np.diff(lo) * np.diff(vo)).sum()):
-            raise ValueError("the weight matrices do not hold the images' M x N elements")
-        for a, n, what in ((d_l, lo[-1], "lines"), (d_s, vo[-1], "ss"), (d_lw, lo[-1], "lineWeights"), (d_la, lo[-1], "lineAngles")):
-            if a.shape[0] != n:
-                raise ValueError("%s holds %d rows, expected %d" % (what, a.shape[0], n))
+        d_lp = ragged.upload(rt, linePoints, np.float64, (4,))
+        d_l = ragged.upload(rt, lines, np.float64, (3,))
+        d_v = ragged.upload(rt, vs, np.float64, (3,))
+        d_s = ragged.upload(rt, ss, np.float64)
+        d_w = ragged.upload(rt, weightMatrices, np.float64)
+        d_lw = ragged.upload(rt, lineWeights, np.float64)
+        d_la = ragged.upload(rt, lineAngles, np.float64)
         oo = vo + np.arange(B + 1, dtype=np.int64)
         v_out = t.zeros((int(oo[-1]), 3), dtype=t.float64, device=rt.tdev)
         s_out = t.zeros((int(oo[-1]),), dtype=t.float64, device=rt.tdev)
@@ -437,7 +361,7 @@ def split_best_vp_batch(vs, ss, linePoints, lines, weightMatrices, lineWeights, 
         split = t.full((B,), -1, dtype=t.int32, device=rt.tdev)
         flags = t.zeros((B,), dtype=t.int32, device=rt.tdev)
         labels = t.full((int(lo[-1]),), -1, dtype=t.int32, device=rt.tdev)
-        rt.check(rt.lib.vpk_vp_split_batch(rt.h, B, _off_ptr(lo), _off_ptr(vo), rt.ptr(d_lp), rt.ptr(d_l), rt.ptr(d_v),
+        rt.check(rt.lib.vpk_vp_split_batch(rt.h, B, ragged.off_ptr(lo), ragged.off_ptr(vo), rt.ptr(d_lp), rt.ptr(d_l), rt.ptr(d_v),
                                            rt.ptr(d_s), rt.ptr(d_w), rt.ptr(d_lw), rt.ptr(d_la), float(min_diff), rt.ptr(v_out),
                                            rt.ptr(s_out), rt.ptr(num), rt.ptr(split), rt.ptr(flags), rt.ptr(labels)))
     rt.synchronize()
@@ -478,26 +402,6 @@ def split_best_vp(i, v, s, linePoints, lines, weightMatrix, lineWeights, lineAng
     return {'v': v2, 's': r['s'].cpu().numpy()[:M + 1]}
 
 
-def _lsim_layout(rt, lsims, sizes):
-    """(device tensor, host element offsets) of the images' N x N matrices.  A list of views into one allocation in rising
-    order -- what calc_lsim_batch returns -- is used where it lies; anything else is concatenated on the device."""
-    t = rt.torch
-    if isinstance(lsims, (list, tuple)) and len(lsims) and all(isinstance(a, t.Tensor) and a.is_cuda and a.dtype == t.float64
-                                                                 and a.is_contiguous() for a in lsims):
-        full = [a for a in lsims if a.numel()]                   # (an empty view has no address)
-        if full:
-            base, off, pos, ok = full[0].data_ptr(), [], 0, True
-            for a, n in zip(lsims, sizes):
-                o = (a.data_ptr() - base) // 8 if a.numel() else pos
-                ok = ok and o >= pos and (not a.numel() or a.untyped_storage().data_ptr() == full[0].untyped_storage().data_ptr())
-                off.append(o)
-                pos = o + int(n) * int(n)
-            if ok:
-                return (base, full[0]), host_i64(off + [pos])
-    d = _cat(rt, lsims, t.float64)
-    return (d.data_ptr(), d), _offsets_of(sizes * sizes)
-
-
 def merge_vps_batch(vs, ss, ls, thresh, lweights, lsims, wbias, pdfpar, lps, llens=None, distance_measure="angle",
                     max_stdd=0.01, outlier_stdd=1e-6, line_offsets=None, vp_offsets=None, device=0):
     """merge_vps on slice i of many images' history arrays in one launch; arguments as in calc_vp_line_counts_batch (vs:
@@ -515,38 +419,34 @@ def merge_vps_batch(vs, ss, ls, thresh, lweights, lsims, wbias, pdfpar, lps, lle
         r = merge_vps_batch(d_v, d_s, d_l, 1e-3, llen * lscore.clamp(0.2, 1), lsims, 1, par, d_lp,
                             line_offsets=off, vp_offsets=vp_off)"""
     _check_measure(distance_measure)
-    lo = _sizes(lps, line_offsets, "lps")
-    vo = _sizes(vs, vp_offsets, "vs")
-    if lo.shape != vo.shape:
-        raise ValueError("lps and vs describe %d and %d images" % (lo.shape[0] - 1, vo.shape[0] - 1))
-    _check_vp_limit(vo)
+    lo = ragged.batch_offsets(lps, line_offsets, "lps")
+    vo = ragged.batch_offsets(vs, vp_offsets, "vs")
+    ragged.check_images(lo, vo, "lps", "vs")
     B = lo.shape[0] - 1
-    rt = _runtime(device)
+    ragged.check_lsims(lsims, lo)
+    if ragged.total(pdfpar.weights) != 400 * B:
+        raise ValueError("pdfpar.weights must be (%d, 400), one row per image" % B)
+    ragged.check_total(ls, lo[-1], "ls", 3, "rows")
+    for x, n, what in ((ss, vo[-1], "ss"), (lweights, lo[-1], "lweights")):
+        ragged.check_total(x, n, what, unit="rows")
+    rt = get_runtime(device)
     t = rt.torch
     with rt.on_stream():
-        d_lp = _cat(rt, lps, t.float64, (4,))
-        d_l = _cat(rt, ls, t.float64, (3,))
-        d_v = _cat(rt, vs, t.float64, (3,))
-        d_s = _cat(rt, ss, t.float64)
-        d_lw = _cat(rt, lweights, t.float64)
-        (lsim_ptr, lsim_keep), lsim_off = _lsim_layout(rt, lsims, np.diff(lo))
-        if lsim_off.shape[0] != B + 1 or (np.diff(lsim_off) < np.diff(lo) ** 2).any():
-            raise ValueError("lsims must hold one N x N matrix per image")
-        d_pw = _cat(rt, pdfpar.weights, t.float32, (400,))
-        if d_pw.shape[0] != B:
-            raise ValueError("pdfpar.weights must be (%d, 400), one row per image" % B)
-        for a, n, what in ((d_l, lo[-1], "ls"), (d_s, vo[-1], "ss"), (d_lw, lo[-1], "lweights")):
-            if a.shape[0] != n:
-                raise ValueError("%s holds %d rows, expected %d" % (what, a.shape[0], n))
+        d_lp = ragged.upload(rt, lps, np.float64, (4,))
+        d_l = ragged.upload(rt, ls, np.float64, (3,))
+        d_v = ragged.upload(rt, vs, np.float64, (3,))
+        d_s = ragged.upload(rt, ss, np.float64)
+        d_lw = ragged.upload(rt, lweights, np.float64)
+        (lsim_ptr, lsim_keep), lsim_off = ragged.lsim_layout(rt, lsims, np.diff(lo))
+        d_pw = ragged.upload(rt, pdfpar.weights, np.float32, (400,))
         v_out = d_v.clone()
         s_out = d_s.clone()
         num = t.from_numpy(np.diff(vo).astype(np.int32)).to(rt.tdev)
         kept = t.cat([t.arange(int(m), dtype=t.int32, device=rt.tdev) for m in np.diff(vo)]) if B else \
             t.zeros((0,), dtype=t.int32, device=rt.tdev)
         flags = t.zeros((B,), dtype=t.int32, device=rt.tdev)
-        import ctypes
-        rt.check(rt.lib.vpk_vp_merge_batch(rt.h, B, _off_ptr(lo), _off_ptr(vo), rt.ptr(d_lp), rt.ptr(d_l), rt.ptr(d_v),
-                                           rt.ptr(d_s), rt.ptr(d_lw), _off_ptr(lsim_off), ctypes.c_void_p(lsim_ptr), float(wbias),
+        rt.check(rt.lib.vpk_vp_merge_batch(rt.h, B, ragged.off_ptr(lo), ragged.off_ptr(vo), rt.ptr(d_lp), rt.ptr(d_l), rt.ptr(d_v),
+                                           rt.ptr(d_s), rt.ptr(d_lw), ragged.off_ptr(lsim_off), lsim_ptr, float(wbias),
                                            rt.ptr(d_pw), float(pdfpar.sigma), float(thresh), float(max_stdd), rt.ptr(v_out),
                                            rt.ptr(s_out), rt.ptr(num), rt.ptr(kept), rt.ptr(flags)))
     rt.synchronize()
@@ -566,7 +466,6 @@ def merge_vps(i, v, s, l, thresh, lweight, lsim, wbias, pdfpar, lp, llen, distan
     lp = _check_lp(lp)
     if M <= 1 or lp.shape[0] == 0:
         return {'v': v.copy(), 's': s.copy()}
-    from .probability_functions import PDFParams, _grid_means
     if not np.array_equal(np.asarray(pdfpar.means), _grid_means()):
         raise ValueError("pdfpar.means must be the 20 x 20 grid of pdf_params")
     w = np.asarray(pdfpar.weights, dtype=np.float32).reshape(1, -1)
@@ -584,78 +483,7 @@ def merge_vps(i, v, s, l, thresh, lweight, lsim, wbias, pdfpar, lp, llen, distan
 
 
 # ---- the EM update outside the EM: weights, M-step and initial VPs for a batch ----------------------------------------------
-MAX_LINES = 32768                       # per image (csrc/vpk_emstep.hip)
-
-
-def _numel(a):
-    return int(a.numel()) if hasattr(a, "numel") else int(np.asarray(a).size)
-
-
-def _shape(a):
-    return tuple(a.shape) if hasattr(a, "shape") else np.asarray(a).shape
-
-
-def _check_counts(lo, vo, what_l, what_v):
-    if lo.shape != vo.shape:
-        raise ValueError("%s and %s describe %d and %d images" % (what_l, what_v, lo.shape[0] - 1, vo.shape[0] - 1))
-    _check_vp_limit(vo)
-    n = np.diff(lo)
-    if n.size and n.max() > MAX_LINES:
-        raise ValueError("%d lines in one image: at most %d are supported" % (n.max(), MAX_LINES))
-
-
-def _check_rows(x, off, width, what):
-    """``x`` holds off[-1] rows of ``width`` elements (lists: image b off[b + 1] - off[b] of them); host only."""
-    if isinstance(x, (list, tuple)):
-        if len(x) != off.shape[0] - 1:
-            raise ValueError("%s holds %d images, expected %d" % (what, len(x), off.shape[0] - 1))
-        for b, a in enumerate(x):
-            if _numel(a) != int(off[b + 1] - off[b]) * width:
-                raise ValueError("%s[%d] holds %d elements, expected %d" % (what, b, _numel(a), int(off[b + 1] - off[b]) * width))
-    elif _numel(x) != int(off[-1]) * width:
-        raise ValueError("%s holds %d elements, expected %d" % (what, _numel(x), int(off[-1]) * width))
-
-
-def _check_mats(x, lo, vo, what, transposed=False):
-    """``x`` holds the images' M_b x N_b matrices: a list of (M_b, N_b) -- ``transposed``: (N_b, M_b) -- arrays or tensors,
-    or the [m][n] matrices concatenated flat, image after image; host only."""
-    n, m = np.diff(lo), np.diff(vo)
-    if isinstance(x, (list, tuple)):
-        if len(x) != n.shape[0]:
-            raise ValueError("%s holds %d images, expected %d" % (what, len(x), n.shape[0]))
-        for b, a in enumerate(x):
-            want = (int(n[b]), int(m[b])) if transposed else (int(m[b]), int(n[b]))
-            if _shape(a) != want and not (_numel(a) == 0 and want[0] * want[1] == 0):
-                raise ValueError("%s[%d] has shape %r, expected %r" % (what, b, _shape(a), want))
-    elif _numel(x) != int((n * m).sum()):
-        raise ValueError("%s holds %d elements, the images' M x N sum to %d" % (what, _numel(x), int((n * m).sum())))
-
-
-def _cat_mats(rt, x, transposed=False):
-    if transposed and isinstance(x, (list, tuple)):
-        x = [a.T if hasattr(a, "data_ptr") else np.asarray(a).T for a in x]      # back to [m][n]: free for a transposed view
-    return _cat(rt, x, rt.torch.float64)
-
-
-def _vp_sizes_of_mats(mats, vp_offsets, what):
-    """VP offsets from a list of (M_b, N_b) matrices, or the caller's for the flat form."""
-    if isinstance(mats, (list, tuple)):
-        for a in mats:
-            if len(_shape(a)) != 2:
-                raise ValueError("%s: every image's matrix must be two-dimensional (M_b, N_b)" % what)
-        return _offsets_of([_shape(a)[0] for a in mats])
-    if vp_offsets is None:
-        raise ValueError("%s is one concatenated array: vp_offsets is needed" % what)
-    vo = host_i64(vp_offsets)
-    if vo.ndim != 1 or vo.shape[0] < 1 or vo[0] != 0 or (np.diff(vo) < 0).any():
-        raise ValueError("vp_offsets must rise from 0")
-    return vo
-
-
-def _split_mn(buf, lo, vo):
-    n, m = np.diff(lo), np.diff(vo)
-    at = np.concatenate(([0], np.cumsum(n * m)))
-    return [buf[int(at[b]):int(at[b + 1])].view(int(m[b]), int(n[b])) for b in range(n.shape[0])]
+MAX_LINES = ragged.MAX_LINES           # per image (csrc/vpk_emstep.hip)
 
 
 def find_initial_vps_batch(sphere_images, cnn_responses, num_max, device=0, want_weights=False):
@@ -667,31 +495,31 @@ def find_initial_vps_batch(sphere_images, cnn_responses, num_max, device=0, want
     num_max = int(num_max)
     if num_max < 1 or num_max > MAX_VP:
         raise ValueError("num_max = %d: 1 to %d initial VPs are supported" % (num_max, MAX_VP))
-    if isinstance(sphere_images, (list, tuple)):
-        sph = [_shape(a) for a in sphere_images]
+    if ragged.is_list(sphere_images):
+        sph = [ragged.shape(a) for a in sphere_images]
     else:
-        if len(_shape(sphere_images)) != 3:
+        if len(ragged.shape(sphere_images)) != 3:
             raise ValueError("sphere_images must be (B, S, S) or a list of (S, S) images")
-        sph = [_shape(sphere_images)[1:]] * _shape(sphere_images)[0]
+        sph = [ragged.shape(sphere_images)[1:]] * ragged.shape(sphere_images)[0]
     B = len(sph)
     if any(len(s) != 2 or s[0] != s[1] or s != sph[0] for s in sph):
         raise ValueError("the sphere images must be square and of one size")
     if B and sph[0][0] < 20:
         raise ValueError("sphere images of %d pixels: at least 20 are needed" % sph[0][0])
-    nc = len(cnn_responses) if isinstance(cnn_responses, (list, tuple)) else (_shape(cnn_responses)[0] if len(_shape(cnn_responses)) else -1)
+    nc = len(cnn_responses) if ragged.is_list(cnn_responses) else (ragged.shape(cnn_responses)[0] if len(ragged.shape(cnn_responses)) else -1)
     if nc != B:
         raise ValueError("sphere_images and cnn_responses describe %d and %d images" % (B, nc))
-    if isinstance(cnn_responses, (list, tuple)):
-        if any(_numel(a) != 400 for a in cnn_responses):
+    if ragged.is_list(cnn_responses):
+        if any(ragged.numel(a) != 400 for a in cnn_responses):
             raise ValueError("every response map must hold 20 x 20 values")
-    elif _numel(cnn_responses) != 400 * B:
+    elif ragged.numel(cnn_responses) != 400 * B:
         raise ValueError("cnn_responses must hold 20 x 20 values per image")
     S = sph[0][0] if B else 20
-    rt = _runtime(device)
+    rt = get_runtime(device)
     t = rt.torch
     with rt.on_stream():
-        d_cnn = _cat(rt, cnn_responses, t.float32, (400,))
-        d_sp = _cat(rt, sphere_images, t.uint8, (S, S))
+        d_cnn = ragged.upload(rt, cnn_responses, np.float32, (400,))
+        d_sp = ragged.upload(rt, sphere_images, np.uint8, (S, S))
         v0 = t.zeros((B, num_max, 3), dtype=t.float64, device=rt.tdev)
         m0 = t.zeros((B,), dtype=t.int32, device=rt.tdev)
         wts = t.zeros((B, 400), dtype=t.float32, device=rt.tdev) if want_weights else None
@@ -706,49 +534,43 @@ def weight_matrix_batch(p_vls, lweights, lsims, bias=0.001, line_offsets=None, v
     concatenated; ``lsims`` as in merge_vps_batch -- the list calc_lsim_batch returns is used where it lies.  ``bias``
     defaults to the reference's own 0.001; the EM calls weight_matrix with wbias (1).  Returns a list of (M_b, N_b) float64
     device tensors, views of one buffer in which the matrices follow each other without gaps."""
-    lo = _sizes(lweights, line_offsets, "lweights")
-    vo = _vp_sizes_of_mats(p_vls, vp_offsets, "p_vls")
-    _check_counts(lo, vo, "lweights", "p_vls")
-    _check_mats(p_vls, lo, vo, "p_vls")
-    n = np.diff(lo)
-    if isinstance(lsims, (list, tuple)):
-        if len(lsims) != n.shape[0] or any(_numel(a) != int(k) * int(k) for a, k in zip(lsims, n)):
-            raise ValueError("lsims must hold one N x N matrix per image")
-    elif _numel(lsims) != int((n * n).sum()):
-        raise ValueError("lsims must hold one N x N matrix per image")
+    lo = ragged.batch_offsets(lweights, line_offsets, "lweights")
+    vo = ragged.vp_sizes_of_mats(p_vls, vp_offsets, "p_vls")
+    ragged.check_counts(lo, vo, "lweights", "p_vls")
+    ragged.check_mats(p_vls, lo, vo, "p_vls")
+    ragged.check_lsims(lsims, lo)
     B = lo.shape[0] - 1
-    rt = _runtime(device)
+    rt = get_runtime(device)
     t = rt.torch
     with rt.on_stream():
-        d_p = _cat_mats(rt, p_vls)
-        d_lw = _cat(rt, lweights, t.float64)
-        (lsim_ptr, lsim_keep), lsim_off = _lsim_layout(rt, lsims, n)
-        w = t.zeros((int((n * np.diff(vo)).sum()),), dtype=t.float64, device=rt.tdev)
-        import ctypes
-        rt.check(rt.lib.vpk_weight_matrix_batch(rt.h, B, _off_ptr(lo), _off_ptr(vo), rt.ptr(d_p), rt.ptr(d_lw), _off_ptr(lsim_off),
-                                                ctypes.c_void_p(lsim_ptr), float(bias), rt.ptr(w)))
+        d_p = ragged.upload_mats(rt, p_vls)
+        d_lw = ragged.upload(rt, lweights, np.float64)
+        (lsim_ptr, lsim_keep), lsim_off = ragged.lsim_layout(rt, lsims, np.diff(lo))
+        w = t.zeros((ragged.mats_total(lo, vo),), dtype=t.float64, device=rt.tdev)
+        rt.check(rt.lib.vpk_weight_matrix_batch(rt.h, B, ragged.off_ptr(lo), ragged.off_ptr(vo), rt.ptr(d_p), rt.ptr(d_lw),
+                                                ragged.off_ptr(lsim_off), lsim_ptr, float(bias), rt.ptr(w)))
     rt.synchronize()
     del lsim_keep
-    return _split_mn(w, lo, vo)
+    return ragged.split_mats(w, lo, vo)
 
 
 def calc_new_vanishing_point_batch(ls, ws, line_offsets=None, vp_offsets=None, device=0):
     """calc_new_vanishing_point for every row of many images' weight matrices in one launch (vpk_mstep_batch without
     state).  ``ls``: (N_b, 3) normalised lines each, ``ws``: (M_b, N_b) each -- or concatenated with the offsets.  Returns
     (vp (sum M, 3) float64, valid (sum M,) int32) as device tensors: vp is zero and valid 0 where the reference returns None."""
-    lo = _sizes(ls, line_offsets, "ls")
-    vo = _vp_sizes_of_mats(ws, vp_offsets, "ws")
-    _check_counts(lo, vo, "ls", "ws")
-    _check_rows(ls, lo, 3, "ls")
-    _check_mats(ws, lo, vo, "ws")
-    rt = _runtime(device)
+    lo = ragged.batch_offsets(ls, line_offsets, "ls")
+    vo = ragged.vp_sizes_of_mats(ws, vp_offsets, "ws")
+    ragged.check_counts(lo, vo, "ls", "ws")
+    ragged.check_rows(ls, lo, 3, "ls")
+    ragged.check_mats(ws, lo, vo, "ws")
+    rt = get_runtime(device)
     t = rt.torch
     with rt.on_stream():
-        d_l = _cat(rt, ls, t.float64, (3,))
-        d_w = _cat_mats(rt, ws)
+        d_l = ragged.upload(rt, ls, np.float64, (3,))
+        d_w = ragged.upload_mats(rt, ws)
         vp = t.zeros((int(vo[-1]), 3), dtype=t.float64, device=rt.tdev)
         valid = t.zeros((int(vo[-1]),), dtype=t.int32, device=rt.tdev)
-        rt.check(rt.lib.vpk_mstep_batch(rt.h, lo.shape[0] - 1, _off_ptr(lo), _off_ptr(vo), rt.ptr(d_l), rt.ptr(d_w), None, None,
+        rt.check(rt.lib.vpk_mstep_batch(rt.h, lo.shape[0] - 1, ragged.off_ptr(lo), ragged.off_ptr(vo), rt.ptr(d_l), rt.ptr(d_w), None, None,
                                         None, None, 1e-6, 1e-200, rt.ptr(vp), None, None, None, rt.ptr(valid), None))
     rt.synchronize()
     return vp, valid
@@ -782,24 +604,24 @@ def mstep_batch(ls, ws, lvsqs, p_vls, curs, assocs=None, max_stdd=1e-6, s_thresh
         raise ValueError("lvsqs and p_vls are given together (calc_new_vanishing_point_batch takes neither)")
     if lvsqs is None:
         raise ValueError("mstep_batch needs lvsqs and p_vls: calc_new_vanishing_point_batch gives the positions alone")
-    lo = _sizes(ls, line_offsets, "ls")
-    vo = _sizes(curs, vp_offsets, "curs")
-    _check_counts(lo, vo, "ls", "curs")
-    _check_rows(ls, lo, 3, "ls")
-    _check_rows(curs, vo, 3, "curs")
-    _check_mats(ws, lo, vo, "ws")
-    _check_mats(lvsqs, lo, vo, "lvsqs", transposed=True)
-    _check_mats(p_vls, lo, vo, "p_vls")
+    lo = ragged.batch_offsets(ls, line_offsets, "ls")
+    vo = ragged.batch_offsets(curs, vp_offsets, "curs")
+    ragged.check_counts(lo, vo, "ls", "curs")
+    ragged.check_rows(ls, lo, 3, "ls")
+    ragged.check_rows(curs, vo, 3, "curs")
+    ragged.check_mats(ws, lo, vo, "ws")
+    ragged.check_mats(lvsqs, lo, vo, "lvsqs", transposed=True)
+    ragged.check_mats(p_vls, lo, vo, "p_vls")
     if assocs is not None:
-        _check_rows(assocs, lo, 1, "assocs")
+        ragged.check_rows(assocs, lo, 1, "assocs")
     B = lo.shape[0] - 1
-    rt = _runtime(device)
+    rt = get_runtime(device)
     t = rt.torch
     with rt.on_stream():
-        d_l = _cat(rt, ls, t.float64, (3,))
-        d_cur = _cat(rt, curs, t.float64, (3,))
-        d_w, d_lv, d_p = _cat_mats(rt, ws), _cat_mats(rt, lvsqs, transposed=True), _cat_mats(rt, p_vls)
-        d_a = _cat(rt, assocs, t.int64) if assocs is not None else None
+        d_l = ragged.upload(rt, ls, np.float64, (3,))
+        d_cur = ragged.upload(rt, curs, np.float64, (3,))
+        d_w, d_lv, d_p = ragged.upload_mats(rt, ws), ragged.upload_mats(rt, lvsqs, transposed=True), ragged.upload_mats(rt, p_vls)
+        d_a = ragged.upload(rt, assocs, np.int64) if assocs is not None else None
         M = int(vo[-1])
         vp = t.zeros((M, 3), dtype=t.float64, device=rt.tdev)
         s = t.full((M,), -1.0, dtype=t.float64, device=rt.tdev)
@@ -807,7 +629,7 @@ def mstep_batch(ls, ws, lvsqs, p_vls, curs, assocs=None, max_stdd=1e-6, s_thresh
         removed = t.zeros((M,), dtype=t.int32, device=rt.tdev)
         valid = t.zeros((M,), dtype=t.int32, device=rt.tdev)
         max_err = t.zeros((B,), dtype=t.float64, device=rt.tdev)
-        rt.check(rt.lib.vpk_mstep_batch(rt.h, B, _off_ptr(lo), _off_ptr(vo), rt.ptr(d_l), rt.ptr(d_w), rt.ptr(d_lv), rt.ptr(d_p),
+        rt.check(rt.lib.vpk_mstep_batch(rt.h, B, ragged.off_ptr(lo), ragged.off_ptr(vo), rt.ptr(d_l), rt.ptr(d_w), rt.ptr(d_lv), rt.ptr(d_p),
                                         rt.ptr(d_a), rt.ptr(d_cur), float(max_stdd), float(s_thresh), rt.ptr(vp), rt.ptr(s),
                                         rt.ptr(err), rt.ptr(removed), rt.ptr(valid), rt.ptr(max_err)))
     rt.synchronize()
