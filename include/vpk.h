@@ -311,18 +311,20 @@ int vpk_sphere_raster_flags(vpk_handle* h, int batch, uint32_t* flags_out);
 /* ---- front end: line segment detection (vpk_lsd_detect: HOST code, host pointers) -------------------------------- */
 /* replaces: lsdpython.lsd.detect_line_segments(image) as called by detect_lsd_lines (evaluation.py:227-251; the
  * detector itself is an un-vendored submodule of the reference, .gitmodules:1-3 -- parity unpinned, see
- * csrc/vpk_lsd.cpp).  image [host]: height x width fp64 grey levels 0..255, row-major; scale: Gaussian sub-sampling
+ * csrc/lsd_device.hpp, the detector's one source; csrc/lsd_host.hpp runs it for one image).  A null image or n_out,
+ * width or height < 8, max_segments < 0, rows without a buffer, a scale that is not > 0: VPK_ERR_ARG.  image [host]: height x width fp64 grey levels 0..255, row-major; scale: Gaussian sub-sampling
  * factor (0.8 = LSD's default).  out [host]: up to max_segments rows of 7 doubles (x1, y1, x2, y2, width, p,
  * -log10(NFA)) in pixel coordinates of the input image; *n_out = number of segments found (if it exceeds
  * max_segments only the first max_segments were written: call again with a larger buffer).  No GPU involved. */
 int vpk_lsd_detect(const double* image, int width, int height, double scale, double* out, int max_segments, int* n_out);
-/* The same detector for a batch of images on the GPU (csrc/vpk_lsd_gpu.hip).  Per image exactly what vpk_lsd_detect
- * does: the same rows in the same order, the same argument rules (width, height >= 8 and scale > 0, else VPK_ERR_ARG)
+/* The same detector, compiled from the same source, for a batch of images on the GPU (csrc/vpk_lsd_gpu.hip; the rules,
+ * the workspace layout and the chunks below: csrc/lsd_plan.hpp).  Per image exactly what vpk_lsd_detect does: the same
+ * rows in the same order, the same argument rules (width, height >= 8 and scale > 0, else VPK_ERR_ARG)
  * and the same overflow rule; coordinates and -log10(NFA) may differ from the host's in the last bits only, where the
  * device's atan2 / sin / cos / exp / log differ from the host libm's.  Everything else -- the
  * grid-wide passes, the seed order, the wave-split region stage, the chunking -- is pinned bit for bit: under the
- * portable math policy (vpk_lsd_set_math) the rows equal the host build of the same source byte for byte
- * (tests/test_gpu_lsd_exact.py).
+ * portable math policy (vpk_lsd_set_math) the rows equal the host's under that policy byte for byte
+ * (tests/test_gpu_lsd_exact.py), and both equal recorded rows (tests/golden/lsd/lsd_portable.npz).
  *   dims         [host] B x 2 int32: width, height of each image
  *   pix_offsets  [host] B+1 int64 prefix sums of width * height (offsets of the images in `images`)
  *   images       concatenated row-major fp64 grey levels 0..255

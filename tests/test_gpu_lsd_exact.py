@@ -12,7 +12,7 @@ import pytest
 
 from test_frontend import _render
 from test_gpu_lsd import IMAGES, _Dev, _strokes
-from test_hostsim_lsd import build_sim
+from test_hostsim_lsd import GOLDEN_IMAGES, GOLDEN_SCALES, build_sim, golden_lsd
 
 pytestmark = pytest.mark.gpu
 
@@ -77,6 +77,14 @@ def host_rows_08(port):
 def test_batch_equals_the_portable_host_build(dev, port, host_rows_08, scale):
     want = _check(dev, port, IMAGES, scale, want=host_rows_08 if scale == 0.8 else None)
     assert sum(w.shape[0] for w in want) > 1000
+
+
+@pytest.mark.parametrize("scale", GOLDEN_SCALES)
+def test_batch_equals_the_recorded_rows(dev, scale):
+    """One call over the stored images of tests/golden/lsd/lsd_portable.npz: the rows recorded from the host, byte for byte."""
+    gold = golden_lsd()
+    _check(dev, None, [gold[name][0] for name in GOLDEN_IMAGES], scale, names=list(GOLDEN_IMAGES),
+           want=[gold[name][1][scale] for name in GOLDEN_IMAGES])
 
 
 def _edge_images():

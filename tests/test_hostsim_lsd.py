@@ -1,11 +1,12 @@
-"""The GPU line segment detector's PRODUCT arithmetic (csrc/lsd_device.hpp: Gaussian samples with host-made weights,
-gradient, seed bins, region growing, rectangles, refinement, NFA) compiled for the host by tests/hostsim/sim_lsd.cpp and
-run serially with a one-lane wave -- bit for bit the rows of the host detector vpk_lsd_detect (csrc/vpk_lsd.cpp).  The
-kernels' own orchestration (grid-wide passes, the LDS counting sort, the wave-split loops) is what tests/test_gpu_lsd.py
-covers.  The same source with the portable math policy (sim_lsd_portable, lsd_portable_math.hpp) is what
-tests/test_gpu_lsd_exact.py pins the GPU to byte for byte; here it must stay a faithful LSD: the detector contract of
-test_frontend.py, and the host detector's rows within the rule the ocml path is held to.  Also: the argument checks of
-lsd.detect_line_segments_batch that need no GPU."""
+"""The line segment detector's one source (csrc/lsd_device.hpp: Gaussian samples with host-made weights, gradient, seed
+bins, region growing, rectangles, refinement, NFA; csrc/lsd_host.hpp: its serial loop with a one-lane wave) compiled by g++
+through tests/hostsim/sim_lsd.cpp -- bit for bit the rows of the product's clang build of the same source, vpk_lsd_detect
+(csrc/vpk_lsd.cpp), and, under the portable math policy, the rows recorded in tests/golden/lsd/lsd_portable.npz from the tree in
+which the host detector was still written out on its own.  The kernels' own orchestration (grid-wide passes, the LDS
+counting sort, the wave-split loops) is what tests/test_gpu_lsd.py covers.  The same source with the portable math policy
+(sim_lsd_portable, lsd_portable_math.hpp) is what tests/test_gpu_lsd_exact.py pins the GPU to byte for byte; here it must
+stay a faithful LSD: the detector contract of test_frontend.py, and the host detector's rows within the rule the ocml path
+is held to.  Also: the argument checks of lsd.detect_line_segments_batch that need no GPU."""
 import ctypes
 import os
 import subprocess
@@ -99,6 +100,40 @@ def test_device_source_on_the_host_equals_the_host_detector(sim, name, scale):
         assert want.shape[0] == 0
     if name.startswith("strokes"):
         assert want.shape[0] > 20
+
+
+GOLDEN = os.path.join(HERE, "golden", "lsd", "lsd_portable.npz")
+GOLDEN_IMAGES = ("noise_8x8", "stroke_9x13", "strokes6_48x40", "strokes12_96x80", "strokes20_160x120")
+GOLDEN_SCALES = (0.8, 1.0, 0.5)
+
+
+def golden_lsd():
+    """tests/golden/lsd/lsd_portable.npz (oracle/make_lsd_golden.py): name -> (image as float64, {scale: recorded rows})."""
+    with np.load(GOLDEN) as z:
+        return {name: (z["image_" + name].astype(np.float64), {s: z["rows_%s_%g" % (name, s)] for s in GOLDEN_SCALES})
+                for name in GOLDEN_IMAGES}
+
+
+@pytest.mark.parametrize("scale", GOLDEN_SCALES)
+@pytest.mark.parametrize("name", GOLDEN_IMAGES)
+def test_portable_build_equals_the_recorded_rows(sim_portable, name, scale):
+    image, rows = golden_lsd()[name]
+    want = rows[scale]
+    got = sim_portable(image, scale)
+    assert got.shape == want.shape
+    assert got.tobytes() == want.tobytes(), "rows differ: %s" % np.argwhere(got != want)[:5]
+    assert want.shape[0] >= 5 if name.startswith("strokes") else want.shape[0] == (2 if name == "stroke_9x13" else 0)
+
+
+def test_a_nan_pixel_is_binned_in_range(sim):
+    """grad_bin clamps the bin of a NaN magnitude, on the host as in lsd_order's LDS histogram: the call returns VPK_OK
+    (detect_line_segments raises otherwise) with finite rows, the g++ build's."""
+    image = golden_lsd()["strokes6_48x40"][0]
+    image[20, 24] = np.nan
+    for scale in GOLDEN_SCALES:
+        got = lsd.detect_line_segments(image, scale=scale)
+        assert got.shape[0] >= 1 and np.isfinite(got).all()
+        assert got.tobytes() == sim(image, scale).tobytes()
 
 
 def test_batch_rejects_a_non_2d_image_before_device_work(monkeypatch):

@@ -1,17 +1,36 @@
-// lsd_device.hpp -- the arithmetic of the GPU line segment detector (vpk_lsd_gpu.hip): the same steps, formulas and
-// evaluation order as the host detector csrc/vpk_lsd.cpp, cut into per-pixel functions for the image-sized passes and
-// one per-image driver for the sequential region stage.  Compiled by hipcc into the kernels of vpk_lsd_gpu.hip and --
-// unmodified, with LSD_HD empty and a one-lane wave -- by g++ into the test-only host build of the tests, which checks
-// that these functions reproduce vpk_lsd_detect bit for bit when they run on glibc's libm.
+// lsd_device.hpp -- the line segment detector of the front end: the one source of its arithmetic, for the host
+// (vpk_lsd_detect: lsd_host.hpp, vpk_lsd.cpp) and for the GPU batch (vpk_lsd_detect_batch: vpk_lsd_gpu.hip).
+//
+// replaces: lsdpython.lsd.detect_line_segments(image) as called from detect_lsd_lines (evaluation.py:227-251).
+// The reference's detector lives in an un-vendored submodule (.gitmodules:1-3 -> github.com/fkluger/lsd-python, a
+// Cython wrapper around R. Grompone von Gioi's LSD 1.6; the directory is empty in the reference), so there is no
+// source to follow and no output to pin against: PARITY UNPINNED.  This file restates the PUBLISHED algorithm --
+// Grompone von Gioi, Jakubowicz, Morel, Randall, "LSD: a Line Segment Detector", Image Processing On Line 2 (2012),
+// with that paper's default parameters (scale 0.8, sigma_scale 0.6, quant 2.0, ang_th 22.5 deg, log_eps 0,
+// density_th 0.7, n_bins 1024) -- step by step:
+//   1. Gaussian sub-sampling to 80 %,                      2. gradient with a 2 x 2 mask, level-line angle, magnitude,
+//   3. pixels pseudo-ordered by magnitude (1024 bins),     4. region growing with the region's running angle,
+//   5. rectangle from the region's weighted inertia,       6. density check / refinement (angle tolerance, radius),
+//   7. a-contrario validation: NFA = N_tests * binomial tail, kept if -log10(NFA) > 0, with the rectangle variations
+//      of the paper's "rect_improve".
+// Output rows: x1, y1, x2, y2, width, p, -log10(NFA) in pixel coordinates of the input image (7 doubles), the layout
+// detect_lsd_lines consumes (columns 0..3 and 6).
+//
+// The steps are cut into per-pixel functions for the image-sized passes and one per-image driver (Region) for the
+// sequential region stage.  hipcc compiles them into the kernels of vpk_lsd_gpu.hip and, with a one-lane wave, into
+// vpk_lsd_detect; g++ compiles them, with LSD_HD empty, into the host build of the tests (tests/hostsim/sim_lsd.cpp).
+// tests/golden/lsd/lsd_portable.npz holds rows recorded when the host detector was still written out on its own and equal
+// to these functions bit for bit.
 //
 // What the GPU computes differently from the host is only the device libm (ocml): atan2 / sin / cos in the gradient and
 // the region's running angle, exp / log / log10 / pow / sinh in the NFA.  Everything else -- the Gaussian weights (made
 // on the host by gaussian_weights below), sqrt, division, floor / ceil, the integer pixel counts of the NFA, min / max --
 // is exact and identical.  The elementary functions of the per-pixel and region-stage code go through a math policy M:
 // Libm (the product's, above) or Portable (lsd_portable_math.hpp, test-only), under which device and host give the
-// same bits and the kernels' orchestration is pinned exactly (tests/test_gpu_lsd_exact.py).  The fp64 sums of the region stage keep the host's order: one wave runs the region stage of
-// one image with every lane executing the same sequential code; only order-free work (the per-column pixel counts of
-// rect_nfa and the min / max of region2rect) is split across the lanes.
+// same bits and the kernels' orchestration is pinned exactly (tests/test_gpu_lsd_exact.py).  The fp64 sums of the region
+// stage keep one order everywhere: on the GPU one wave runs the region stage of one image with every lane executing the
+// same sequential code; only order-free work (the per-column pixel counts of rect_nfa and the min / max of region2rect)
+// is split across the lanes.
 #ifndef VPK_LSD_DEVICE_HPP_
 #define VPK_LSD_DEVICE_HPP_
 
@@ -35,7 +54,7 @@ constexpr double M_3_2_PI_L = 4.71238898038;
 constexpr double M_2__PI_L = 6.28318530718;
 constexpr double LN10_L = 2.30258509299404568402;
 constexpr int N_BINS = 1024;
-// LSD's default parameters (vpk_lsd.cpp)
+// LSD's default parameters
 constexpr double SIGMA_SCALE = 0.6, QUANT = 2.0, ANG_TH = 22.5, LOG_EPS = 0.0, DENSITY_TH = 0.7;
 
 struct Pt { int x, y; };
@@ -65,13 +84,13 @@ struct Portable {                              // test-only: the same bits on bo
     LSD_HD static double sinh(double x) { return vpk_pmath::sinh(x); }
 };
 
-// per-call constants, all made on the host (vpk_lsd.cpp computes them the same way)
+// per-call constants, all made on the host
 struct Params {
     double scale, prec, p, rho;
     int taps, half;            // Gaussian kernel: n = 1 + 2 h taps
 };
 
-// host-only: the constants of vpk_lsd_detect for `scale`, and the per-image ones
+// host-only: the constants of a call at `scale`, and the per-image ones
 inline Params make_params(double scale) {
     Params q;
     q.scale = scale;
@@ -95,7 +114,7 @@ inline void scaled_size(int width, int height, double scale, int& xs, int& ys) {
 inline double log_nt(int xs, int ys) { return 5.0 * (log10((double)xs) + log10((double)ys)) / 2.0 + log10(11.0); }
 inline int min_reg_size(double logNT, double p) { return (int)(-logNT / log10(p)); }
 
-// host-only: gaussian_kernel of vpk_lsd.cpp for every output coordinate 0..count-1 of both passes (the kernel of output
+// host-only: the normalised Gaussian kernel of every output coordinate 0..count-1 of both passes (the kernel of output
 // coordinate i depends on i and the scale only): table[i * taps + k]
 inline void gaussian_weights(double* table, int count, const Params& q) {
     const double sigma = q.scale < 1.0 ? SIGMA_SCALE / q.scale : SIGMA_SCALE;
@@ -265,8 +284,9 @@ struct Region {
     LSD_HD double grad(int x, int y) const { return modgrad[(long long)y * xs + x]; }
     LSD_HD unsigned char& use(int x, int y) const { return used[(long long)y * xs + x]; }
 
-    // rect_nfa: the rectangle iterator of vpk_lsd.cpp visits, column by column, x = ceil(vx[0]) .. (x <= vx[2]) and in
-    // each column y = ceil(ys) .. (y <= ye); the columns are independent, so the lanes take them in turn [split]
+    // rect_nfa: LSD's rectangle iterator visits, column by column, x = ceil(vx[0]) .. (x <= vx[2]) and in each column
+    // y = ceil(ys) .. (y <= ye), and counts the pixels inside the image; the columns are independent, so the lanes
+    // take them in turn [split]
     LSD_HD double rect_nfa(const Rect& r) const {
         double vxr[4], vyr[4], vx[4], vy[4];
         vxr[0] = r.x1 - r.dy * r.width / 2.0; vyr[0] = r.y1 + r.dx * r.width / 2.0;
@@ -471,8 +491,9 @@ struct Region {
         return log_nfa;
     }
 
-    // the seed loop of vpk_lsd_detect over `n_order` seeds (packed y * xs + x, pseudo-ordered; seeds whose angle is NOTDEF
-    // may be left out: the host skips them).  Rows go to out (max_segments of 7 doubles; lane 0 writes); returns the count.
+    // the seed loop over `n_order` seeds (packed y * xs + x, pseudo-ordered; seeds whose angle is NOTDEF may be left out:
+    // the loop skips them).  Rows go to out (max_segments of 7 doubles; lane 0 writes); returns the full count, which may
+    // exceed max_segments.
     LSD_HD int detect(const int* order, int n_order, const Params& q, int min_reg, double* out, int max_segments) const {
         int count = 0;
         for (int k = 0; k < n_order; ++k) {

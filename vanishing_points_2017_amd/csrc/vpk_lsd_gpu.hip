@@ -1,7 +1,9 @@
 // vpk_lsd_gpu.hip -- batched line segment detection on the GPU (C-ABI entry vpk_lsd_detect_batch).
 //
-// Per image the same detector as vpk_lsd_detect (csrc/vpk_lsd.cpp), in the same order; the arithmetic is in
-// lsd_device.hpp.  Five launches per chunk of images, every image-sized pass grid-wide over the chunk:
+// Per image the same detector as vpk_lsd_detect, from the same source and in the same order: the arithmetic is in
+// lsd_device.hpp (lsd_host.hpp is its serial loop on the host); what is decided on the host before a launch -- the rules,
+// the workspace layout, the chunks -- is in lsd_plan.hpp.  Five launches per chunk of images, every image-sized pass
+// grid-wide over the chunk:
 //   lsd_sample_x    Gaussian sub-sampling along x (input -> aux), weights made on the host by the host's formula
 //   lsd_sample_y    ... along y (aux -> scaled)
 //   lsd_gradient    gradient, level-line angle, magnitude, per-image max of the magnitudes (exact: a max), `used` cleared
@@ -18,6 +20,7 @@
 #include <string.h>
 
 #include "lsd_device.hpp"
+#include "lsd_plan.hpp"
 
 using namespace vpk_lsd;
 
@@ -26,27 +29,6 @@ namespace {
 constexpr int PASS_THREADS = 256;
 constexpr int ORDER_THREADS = 1024;
 constexpr int ORDER_WAVES = ORDER_THREADS / 64;
-constexpr int MAX_CHUNK_IMAGES = 4096;
-constexpr size_t DEFAULT_WS_LIMIT = (size_t)4 << 30;
-constexpr long long MAX_DIM = 1 << 20;          // input or scaled side
-constexpr long long MAX_SCALED_PIXELS = 1 << 30; // seeds are packed as y * xs + x into an int
-
-struct ImgDesc {
-    long long in_off;                             // first pixel in `images`
-    long long aux, scaled, ang, grad, order, reg, used;   // byte offsets into the chunk's workspace
-    int w, h, xs, ys;
-    int b;                                        // index in the batch
-    int min_reg;
-    double logNT;
-};
-
-struct Meta {                                     // per image of a chunk, zeroed before it
-    unsigned long long max_grad;                  // bits of a non-negative double: integer max = double max
-    int n_seeds;
-    int pad;
-};
-
-inline long long align256(long long v) { return (v + 255) & ~255LL; }
 
 template <class T> __device__ __forceinline__ T* at(unsigned char* ws, long long off) { return (T*)(ws + off); }
 
@@ -101,8 +83,8 @@ __global__ void __launch_bounds__(PASS_THREADS) lsd_gradient(const ImgDesc* __re
         atomicMax(&meta[blockIdx.y].max_grad, (unsigned long long)__double_as_longlong(mx));
 }
 
-// seeds: pixels x < xs - 1, y < ys - 1 whose angle is defined (the host also pushes the others; its seed loop skips them),
-// walked in the host's push order c = x * (ys - 1) + y.  Wave w owns a contiguous range of c, so a bin's seeds of wave w
+// seeds: pixels x < xs - 1, y < ys - 1 whose angle is defined, walked in the host's push order c = x * (ys - 1) + y
+// (lsd_host.hpp).  Wave w owns a contiguous range of c, so a bin's seeds of wave w
 // come after those of the waves before it: cursor[w][bin] starts at the bin's start plus their counts.
 __global__ void __launch_bounds__(ORDER_THREADS) lsd_order(const ImgDesc* __restrict__ desc, unsigned char* ws, Meta* meta) {
     __shared__ int hist[ORDER_WAVES][N_BINS];
@@ -212,6 +194,23 @@ __global__ void __launch_bounds__(64) lsd_region(const ImgDesc* __restrict__ des
     if (threadIdx.x == 0) n_out[d.b] = n;
 }
 
+// the launches of one chunk of n images (desc: its descriptors on the device); max_aux, max_px: its largest xs * h, xs * ys
+template <class M>
+void launch_chunk(hipStream_t stream, const ImgDesc* desc, int n, long long max_aux, long long max_px, const double* images,
+                  const double* wts, const Params& q, unsigned char* ws, Meta* meta, double* out, int max_segments, int* n_out) {
+    auto blocks = [](long long total) {
+        const long long g = (total + PASS_THREADS - 1) / PASS_THREADS;
+        return (unsigned)(g < 1024 ? g : 1024);
+    };
+    if (q.scale != 1.0) {
+        hipLaunchKernelGGL(lsd_sample_x, dim3(blocks(max_aux), n), dim3(PASS_THREADS), 0, stream, desc, images, wts, q, ws);
+        hipLaunchKernelGGL(lsd_sample_y, dim3(blocks(max_px), n), dim3(PASS_THREADS), 0, stream, desc, wts, q, ws);
+    }
+    hipLaunchKernelGGL(lsd_gradient<M>, dim3(blocks(max_px), n), dim3(PASS_THREADS), 0, stream, desc, images, q, ws, meta);
+    hipLaunchKernelGGL(lsd_order, dim3(n), dim3(ORDER_THREADS), 0, stream, desc, ws, meta);
+    hipLaunchKernelGGL(lsd_region<M>, dim3(n), dim3(64), 0, stream, desc, q, ws, (const Meta*)meta, out, max_segments, n_out);
+}
+
 }  // namespace
 
 extern "C" {
@@ -237,74 +236,19 @@ int vpk_lsd_detect_batch(vpk_handle* h, int batch, const int32_t* dims, const in
         return vpk_fail(h, VPK_ERR_ARG, "vpk_lsd_detect_batch: bad argument");
     if (batch == 0) return VPK_OK;
     const Params q = make_params(scale);
-    std::vector<ImgDesc> desc((size_t)batch);
-    std::vector<long long> bytes((size_t)batch);
-    int max_c = 0;
-    for (int b = 0; b < batch; ++b) {
-        const int w = dims[2 * b], ht = dims[2 * b + 1];
-        if (w < 8 || ht < 8) return vpk_fail(h, VPK_ERR_ARG, "vpk_lsd_detect_batch: width and height must be >= 8");
-        if (pix_offsets[b + 1] - pix_offsets[b] != (int64_t)w * ht || pix_offsets[b] < 0)
-            return vpk_fail(h, VPK_ERR_ARG, "vpk_lsd_detect_batch: pix_offsets do not match width * height");
-        if (w > MAX_DIM || ht > MAX_DIM || !((double)w * scale <= (double)MAX_DIM) || !((double)ht * scale <= (double)MAX_DIM))
-            return vpk_fail(h, VPK_ERR_LIMIT, "vpk_lsd_detect_batch: image side beyond 2^20 pixels");
-        int xs, ys;
-        scaled_size(w, ht, scale, xs, ys);
-        const long long P = (long long)xs * ys;
-        if (P > MAX_SCALED_PIXELS || xs < 1 || ys < 1)
-            return vpk_fail(h, VPK_ERR_LIMIT, "vpk_lsd_detect_batch: sub-sampled image beyond 2^30 pixels");
-        ImgDesc& d = desc[(size_t)b];
-        memset(&d, 0, sizeof(d));
-        d.in_off = pix_offsets[b];
-        d.w = w; d.h = ht; d.xs = xs; d.ys = ys; d.b = b;
-        d.logNT = log_nt(xs, ys);
-        d.min_reg = min_reg_size(d.logNT, q.p);
-        long long o = 0;
-        if (scale != 1.0) {
-            d.aux = o; o += align256((long long)xs * ht * 8);
-            d.scaled = o; o += align256(P * 8);
-            max_c = xs > max_c ? xs : max_c;
-            max_c = ys > max_c ? ys : max_c;
-        }
-        d.ang = o; o += align256(P * 8);
-        d.grad = o; o += align256(P * 8);
-        d.order = o; o += align256(P * 4);
-        d.reg = o; o += align256(P * 8);
-        d.used = o; o += align256(P);
-        bytes[(size_t)b] = o;
-    }
-    // chunks: consecutive images while their workspace stays under the limit (at least one image per chunk)
-    const size_t limit = h->lsd_ws_limit ? h->lsd_ws_limit : DEFAULT_WS_LIMIT;
-    std::vector<int> starts;
-    size_t ws_need = 0;
-    {
-        int b = 0;
-        while (b < batch) {
-            const int s = b;
-            long long used = 0;
-            while (b < batch && b - s < MAX_CHUNK_IMAGES) {
-                const long long meta = align256((long long)(b - s + 1) * sizeof(Meta));
-                if (b > s && meta + used + bytes[(size_t)b] > (long long)limit) break;
-                used += bytes[(size_t)b];
-                ++b;
-            }
-            starts.push_back(s);
-            // offsets inside the chunk: the Meta array first, then the images one after the other
-            const long long meta = align256((long long)(b - s) * sizeof(Meta));
-            long long base = meta;
-            for (int k = s; k < b; ++k) {
-                ImgDesc& d = desc[(size_t)k];
-                if (scale != 1.0) { d.aux += base; d.scaled += base; }
-                d.ang += base; d.grad += base; d.order += base; d.reg += base; d.used += base;
-                base += bytes[(size_t)k];
-            }
-            if ((size_t)base > ws_need) ws_need = (size_t)base;
-        }
-        starts.push_back(batch);
+    const Plan plan = plan_batch(batch, dims, pix_offsets, scale, h->lsd_ws_limit);
+    if (plan.rule) {
+        static const char* const what[] = {nullptr,
+                                           "vpk_lsd_detect_batch: width and height must be >= 8",            // PLAN_SIDE
+                                           "vpk_lsd_detect_batch: pix_offsets do not match width * height",  // PLAN_OFFSETS
+                                           "vpk_lsd_detect_batch: image side beyond 2^20 pixels",            // PLAN_DIM
+                                           "vpk_lsd_detect_batch: sub-sampled image beyond 2^30 pixels"};    // PLAN_PIXELS
+        return vpk_fail(h, plan_code(plan.rule), what[plan.rule]);
     }
     VPK_HIP(h, hipSetDevice(h->device));
     // header: descriptors, then the Gaussian weights of every output coordinate 0..max_c-1
     const size_t desc_bytes = (size_t)align256((long long)batch * sizeof(ImgDesc));
-    const size_t hdr_bytes = desc_bytes + (size_t)max_c * q.taps * sizeof(double);
+    const size_t hdr_bytes = desc_bytes + (size_t)plan.max_c * q.taps * sizeof(double);
     if (h->lsd_ev_valid) VPK_HIP(h, hipEventSynchronize(h->lsd_ev));  // the previous call's upload has left the staging
     if (h->lsd_host_bytes < hdr_bytes) {
         if (h->lsd_host) VPK_HIP(h, hipHostFree(h->lsd_host));
@@ -315,11 +259,11 @@ int vpk_lsd_detect_batch(vpk_handle* h, int batch, const int32_t* dims, const in
     }
     if (!h->lsd_ev) VPK_HIP(h, hipEventCreateWithFlags(&h->lsd_ev, hipEventDisableTiming));
     unsigned char* stage = (unsigned char*)h->lsd_host;
-    memcpy(stage, desc.data(), (size_t)batch * sizeof(ImgDesc));
-    if (max_c) gaussian_weights((double*)(stage + desc_bytes), max_c, q);
+    memcpy(stage, plan.desc.data(), (size_t)batch * sizeof(ImgDesc));
+    if (plan.max_c) gaussian_weights((double*)(stage + desc_bytes), plan.max_c, q);
     int rc = vpk_reserve(h, &h->lsd_hdr, &h->lsd_hdr_bytes, hdr_bytes, "vpk_lsd_detect_batch: header");
     if (rc) return rc;
-    rc = vpk_reserve(h, &h->lsd_ws, &h->lsd_ws_bytes, ws_need, "vpk_lsd_detect_batch: workspace");
+    rc = vpk_reserve(h, &h->lsd_ws, &h->lsd_ws_bytes, plan.ws_bytes, "vpk_lsd_detect_batch: workspace");
     if (rc) return rc;
     VPK_HIP(h, hipMemcpyAsync(h->lsd_hdr, stage, hdr_bytes, hipMemcpyHostToDevice, h->stream));
     VPK_HIP(h, hipEventRecord(h->lsd_ev, h->stream));
@@ -328,37 +272,24 @@ int vpk_lsd_detect_batch(vpk_handle* h, int batch, const int32_t* dims, const in
     const double* wts = (const double*)((unsigned char*)h->lsd_hdr + desc_bytes);
     unsigned char* ws = (unsigned char*)h->lsd_ws;
     Meta* meta = (Meta*)ws;
-    for (size_t c = 0; c + 1 < starts.size(); ++c) {
-        const int s = starts[c], n = starts[c + 1] - s;
+    for (size_t c = 0; c + 1 < plan.starts.size(); ++c) {
+        const int s = plan.starts[c], n = plan.starts[c + 1] - s;
         long long max_aux = 0, max_px = 0;
-        for (int k = s; k < starts[c + 1]; ++k) {
-            const ImgDesc& d = desc[(size_t)k];
+        for (int k = s; k < s + n; ++k) {
+            const ImgDesc& d = plan.desc[(size_t)k];
             max_aux = (long long)d.xs * d.h > max_aux ? (long long)d.xs * d.h : max_aux;
             max_px = (long long)d.xs * d.ys > max_px ? (long long)d.xs * d.ys : max_px;
         }
-        auto blocks = [](long long total) {
-            const long long g = (total + PASS_THREADS - 1) / PASS_THREADS;
-            return (unsigned)(g < 1024 ? g : 1024);
-        };
         VPK_HIP(h, hipMemsetAsync(meta, 0, (size_t)n * sizeof(Meta), h->stream));
-        if (scale != 1.0) {
-            hipLaunchKernelGGL(lsd_sample_x, dim3(blocks(max_aux), n), dim3(PASS_THREADS), 0, h->stream, ddesc + s, images, wts,
-                               q, ws);
-            hipLaunchKernelGGL(lsd_sample_y, dim3(blocks(max_px), n), dim3(PASS_THREADS), 0, h->stream, ddesc + s, wts, q, ws);
+        switch (h->lsd_math) {
+            case 1:
+                launch_chunk<Portable>(h->stream, ddesc + s, n, max_aux, max_px, images, wts, q, ws, meta, out, max_segments,
+                                       (int*)n_out);
+                break;
+            default:
+                launch_chunk<Libm>(h->stream, ddesc + s, n, max_aux, max_px, images, wts, q, ws, meta, out, max_segments,
+                                   (int*)n_out);
         }
-        if (h->lsd_math == 1)
-            hipLaunchKernelGGL(lsd_gradient<Portable>, dim3(blocks(max_px), n), dim3(PASS_THREADS), 0, h->stream, ddesc + s,
-                               images, q, ws, meta);
-        else
-            hipLaunchKernelGGL(lsd_gradient<Libm>, dim3(blocks(max_px), n), dim3(PASS_THREADS), 0, h->stream, ddesc + s,
-                               images, q, ws, meta);
-        hipLaunchKernelGGL(lsd_order, dim3(n), dim3(ORDER_THREADS), 0, h->stream, ddesc + s, ws, meta);
-        if (h->lsd_math == 1)
-            hipLaunchKernelGGL(lsd_region<Portable>, dim3(n), dim3(64), 0, h->stream, ddesc + s, q, ws, (const Meta*)meta, out,
-                               max_segments, (int*)n_out);
-        else
-            hipLaunchKernelGGL(lsd_region<Libm>, dim3(n), dim3(64), 0, h->stream, ddesc + s, q, ws, (const Meta*)meta, out,
-                               max_segments, (int*)n_out);
         VPK_HIP(h, hipGetLastError());
     }
     return VPK_OK;

@@ -1,13 +1,14 @@
 """`lsd.detect_line_segments(image)` -- the call the reference makes into its un-vendored `lsdpython` submodule
-(evaluation.py:7,238; .gitmodules:1-3).  Backed by the host-side detector in libvpk.so (csrc/vpk_lsd.cpp: the
-published LSD algorithm with its default parameters; parity with the absent original is unpinned).
-`detect_line_segments_batch(images)` runs the same detector for a list of images in one GPU call
-(vpk_lsd_detect_batch, csrc/vpk_lsd_gpu.hip); the host detector stays the default everywhere."""
+(evaluation.py:7,238; .gitmodules:1-3).  Backed by the detector of libvpk.so (csrc/lsd_device.hpp: the published LSD
+algorithm with its default parameters; parity with the absent original is unpinned), run on the host for one image
+(vpk_lsd_detect, csrc/vpk_lsd.cpp).  `detect_line_segments_batch(images)` runs the same source for a list of images in one
+GPU call (vpk_lsd_detect_batch, csrc/vpk_lsd_gpu.hip); the host call stays the default everywhere."""
 import ctypes
 
 import numpy as np
 
 from . import _lib
+from .ragged import offsets_of
 
 _BATCH_CAP = 4096          # rows per image of detect_line_segments_batch's first call
 
@@ -47,16 +48,14 @@ def detect_line_segments_batch(images, scale=0.8, device=0):
     h = _lib.get_handle(device)
     dev = torch.device("cuda", int(device))
     dims = np.array([[im.shape[1], im.shape[0]] for im in imgs], dtype=np.int32)
-    offsets = np.zeros(len(imgs) + 1, dtype=np.int64)
-    offsets[1:] = np.cumsum([im.size for im in imgs])
+    offsets = offsets_of([im.size for im in imgs])
     flat = torch.from_numpy(np.concatenate([im.ravel() for im in imgs])).to(dev)
     torch.cuda.synchronize(dev)               # the upload runs on torch's stream, the detector on the handle's
 
     def run(idx, cap):
         sel = np.asarray(idx)
         d = np.ascontiguousarray(dims[sel])
-        offs = np.zeros(len(idx) + 1, dtype=np.int64)
-        offs[1:] = np.cumsum(d[:, 0].astype(np.int64) * d[:, 1])
+        offs = offsets_of(d[:, 0].astype(np.int64) * d[:, 1])
         sub = flat if len(idx) == len(imgs) else torch.cat([flat[offsets[i]:offsets[i + 1]] for i in idx])
         out = torch.empty((len(idx), cap, 7), dtype=torch.float64, device=dev)
         n = torch.zeros(len(idx), dtype=torch.int32, device=dev)
