@@ -590,7 +590,8 @@ int vpk_line_rating_batch(vpk_handle* h, int batch, const int64_t* offsets, cons
  * sum_{a < b} M_a N_a.  Everything else is a device pointer.  batch = 0 does nothing; an image with N_b = 0 or M_b = 0
  * gets no workgroup and none of its outputs is written.  batch < 0, malformed offsets and null buffers: VPK_ERR_ARG, and
  * no output is touched. */
-/* replaces: calc_vp_line_counts -- vp_localisation.py:482-512, distance_measure "angle" -- for a batch.
+/* replaces: calc_vp_line_counts -- vp_localisation.py:482-512 -- for a batch, under distance_measure "angle"; the other
+ * measures: vpk_vp_line_counts_batch_measure below.
  *   lp sum(N) x 4, v sum(M) x 3, s sum(M), metric [m][n] per image, lweights sum(N)
  *   vp_assoc_in  NULL (:486-487: the argmax of the metric over the VPs, first maximum, a NaN counts as the maximum) or
  *                sum(N) int64: entries below 0 skip the line (:494) and come back unchanged; entries of M_b or more
@@ -617,8 +618,8 @@ int vpk_vp_split_batch(vpk_handle* h, int batch, const int64_t* line_offsets, co
                        const double* langles, double min_diff, double* v_out, double* s_out, int32_t* m_out,
                        int32_t* split_out, uint32_t* flags_out, int32_t* labels_out);
 
-/* replaces: merge_vps with calc_angle_to_other_vp -- vp_localisation.py:633-697, distance_measure "angle" -- for a
- * batch, on slice i of the history array.  While the smallest angle between two VPs (the first row-major minimum of the
+/* replaces: merge_vps with calc_angle_to_other_vp -- vp_localisation.py:633-697 -- for a batch, on slice i of the history
+ * array, under distance_measure "angle"; the other measures: vpk_vp_merge_batch_measure below.  While the smallest angle between two VPs (the first row-major minimum of the
  * M x M angle matrix, :647-653; the diagonal counts pi) is below thresh: calc_probabilities and weight_matrix of the whole
  * set (:658-659, the EM's E-step and smoother), the new VP k from w[j] + w[k] (:661) and its variance (:663-666), VP j
  * deleted (:674-675).  s[k] is written before the abort test (:666-668): a merge given up because the new VP is None or
@@ -629,13 +630,40 @@ int vpk_vp_split_batch(vpk_handle* h, int batch, const int64_t* line_offsets, co
  *   cells are used, as pdf_params leaves them, more raise VPK_VPSET_FLAG_PRIOR_TRUNCATED
  *   v_out sum(M) x 3, s_out sum(M), keep_out sum(M) int32: image b's rows start at vp_offsets[b]; m_out[b] rows are
  *   the merged set and the indices its VPs had in the input, rows past it zeros and -1; m_out, flags_out batch
- * llen, which the reference passes on to calc_probabilities, is not read by the "angle" measure and is not taken. */
+ * llen, which the reference passes on to calc_probabilities, is read by none of its three calc_lvsq_* and is not taken. */
 #define VPK_VPSET_FLAG_PRIOR_TRUNCATED 8u
 int vpk_vp_merge_batch(vpk_handle* h, int batch, const int64_t* line_offsets, const int64_t* vp_offsets, const double* lp,
                        const double* l, const double* v, const double* s, const double* lweight,
                        const int64_t* lsim_offsets, const double* lsim, double wbias, const float* prior_weights,
                        double prior_sigma, double thresh, double max_stdd, double* v_out, double* s_out, int32_t* m_out,
                        int32_t* keep_out, uint32_t* flags_out);
+
+/* replaces: calc_vp_line_counts -- vp_localisation.py:482-512 with its branch on distance_measure (:495-500) -- for a
+ * batch.  measure: VPK_DIST_ANGLE, VPK_DIST_DOTPROD or VPK_DIST_AREA (enum vpk_dist_measure below), one kernel each; any
+ * other value is VPK_ERR_ARG.  The arguments of vpk_vp_line_counts_batch, and l sum(N) x 3: read by VPK_DIST_DOTPROD only
+ * (else it may be NULL; NULL under VPK_DIST_DOTPROD is VPK_ERR_ARG).  The distance is evaluated on v, s and l as they
+ * stand (the reference normalises none of them here):
+ *   angle    calc_lvsq_single (probability_functions.py:212-224): the bits of vpk_vp_line_counts_batch
+ *   dotprod  |v[m] . l[n]| (:496), summed as (l0 v0 + l1 v1) + l2 v2; finite for a VP at infinity
+ *   area     calc_lvsq_area_single (probability_functions.py:227-249): vpk_estep_batch's lvsq of the pair
+ * A NaN distance makes the outlier test (:504) false and the line counts: under "angle" and "area" for a VP with
+ * v[2] == 0, under "area" also where c^2 - b^2 < 0 (:245).  Every argument error is returned before anything is launched
+ * and no output is touched. */
+int vpk_vp_line_counts_batch_measure(vpk_handle* h, int measure, int batch, const int64_t* line_offsets,
+                                     const int64_t* vp_offsets, const double* lp, const double* l, const double* v,
+                                     const double* s, const double* metric, const double* lweights, double thresh,
+                                     const int64_t* vp_assoc_in, double* counts_out, double* counts_w_out,
+                                     int64_t* vp_assoc_out);
+/* replaces: merge_vps -- vp_localisation.py:633-684, which hands its distance_measure to calc_probabilities (:658) -- for a
+ * batch.  measure as above; the arguments of vpk_vp_merge_batch after it, and its bits under VPK_DIST_ANGLE.  The E-step of
+ * every merge round runs under the measure: "dotprod" on l against v as given (calc_lvsq_dotprod,
+ * probability_functions.py:150-154), "area" as calc_lvsq_area (:179-209) has it, a NaN where its radicand is negative.
+ * max_stdd is the caller's: the EM passes 0.01 under every measure (:339, :448). */
+int vpk_vp_merge_batch_measure(vpk_handle* h, int measure, int batch, const int64_t* line_offsets, const int64_t* vp_offsets,
+                               const double* lp, const double* l, const double* v, const double* s, const double* lweight,
+                               const int64_t* lsim_offsets, const double* lsim, double wbias, const float* prior_weights,
+                               double prior_sigma, double thresh, double max_stdd, double* v_out, double* s_out,
+                               int32_t* m_out, int32_t* keep_out, uint32_t* flags_out);
 
 /* ---- the E-step outside the EM (batched; asynchronous on the handle's stream) ---------------------------- */
 /* replaces: calc_probabilities -- probability_functions.py:99-120 -- after its prior (calc_angles and calc_pdf, :104-105:

@@ -2,11 +2,14 @@
 set its own EM run ended with, through calc_vp_line_counts_batch and merge_vps_batch in one launch each, and through 102
 single-image calls.
 
-    python scripts/time_vp_set.py [--reps 5]
+    python scripts/time_vp_set.py [--reps 5] [--measure angle|dotprod|area]
 
 Prints one JSON line: wall times in ms (median of --reps after one warm-up; uploads, the launch and the final synchronise
 included; the batch forms' results stay on the device, the single calls copy theirs to the host as they always do).  The
-merge runs at thresh = 1e-2, ten times the EM's, so that some of the final VP sets do merge."""
+merge runs at thresh = 1e-2, ten times the EM's, so that some of the final VP sets do merge.
+
+--measure: the batch forms are also timed under that distance measure (counts_batch_<measure>_ms, merge_batch_<measure>_ms)
+on the same VP sets, next to the "angle" times of the same run; the single-image forms take "angle" only."""
 import argparse
 import json
 import os
@@ -33,6 +36,7 @@ def median_ms(f, reps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--measure", choices=("angle", "dotprod", "area"), default="angle")
     a = ap.parse_args()
     scenes = list(synth.config_scenes(2))
     res = em.em_batch(scenes, want_metric=True)
@@ -58,6 +62,13 @@ def main():
     out = {"images": len(lps), "lines": int(sum(x.shape[0] for x in lps)), "vps": int(sum(x.shape[0] for x in vs)),
            "counts_batch_ms": median_ms(counts_b, a.reps), "counts_single_ms": median_ms(counts_1, a.reps),
            "merge_batch_ms": median_ms(merge_b, a.reps), "merge_single_ms": median_ms(merge_1, a.reps)}
+    if a.measure != "angle":
+        counts_m = lambda: V.calc_vp_line_counts_batch(vs, lps, ss, metrics, lws, a.measure, thresh=1.96 ** 2, ls=ls)   # noqa: E731
+        merge_m = lambda: V.merge_vps_batch(vs, ss, ls, thresh, lws, lsims, 1, par, lps, distance_measure=a.measure)   # noqa: E731
+        out["counts_batch_%s_ms" % a.measure] = median_ms(counts_m, a.reps)
+        out["merge_batch_%s_ms" % a.measure] = median_ms(merge_m, a.reps)
+        out["vps_after_merge_%s" % a.measure] = int(merge_m()["num_vp"].sum())
+        out["lines_counted_%s" % a.measure] = int(counts_m()[0].sum())
     mb = merge_b()
     out["vps_after_merge"] = int(mb["num_vp"].sum())
     c = counts_b()

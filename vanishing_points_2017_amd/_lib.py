@@ -75,6 +75,7 @@ EXPORTS = [
     "vpk_line_similarity_batch", "vpk_line_rating_batch",
     "vpk_overlay_lines_batch", "vpk_overlay_markers_batch",
     "vpk_vp_line_counts_batch", "vpk_vp_split_batch", "vpk_vp_merge_batch",
+    "vpk_vp_line_counts_batch_measure", "vpk_vp_merge_batch_measure",
     "vpk_estep_batch",
     "vpk_weight_matrix_batch", "vpk_mstep_batch", "vpk_init_vps_batch",
     "vpk_vp_order_batch", "vpk_to_pixels_batch",
@@ -176,6 +177,9 @@ def load():
     lib.vpk_vp_split_batch.argtypes = [c_void, ctypes.c_int] + [c_void] * 9 + [ctypes.c_double] + [c_void] * 6
     lib.vpk_vp_merge_batch.argtypes = [c_void, ctypes.c_int] + [c_void] * 9 + [ctypes.c_double, c_void] + \
                                       [ctypes.c_double] * 3 + [c_void] * 5
+    lib.vpk_vp_line_counts_batch_measure.argtypes = [c_void, ctypes.c_int, ctypes.c_int] + [c_void] * 8 + [ctypes.c_double] + [c_void] * 4
+    lib.vpk_vp_merge_batch_measure.argtypes = [c_void, ctypes.c_int, ctypes.c_int] + [c_void] * 9 + [ctypes.c_double, c_void] + \
+                                              [ctypes.c_double] * 3 + [c_void] * 5
     lib.vpk_estep_batch.argtypes = [c_void, ctypes.c_int] + [c_void] * 7 + [ctypes.c_int] + [c_void] * 5
     lib.vpk_weight_matrix_batch.argtypes = [c_void, ctypes.c_int] + [c_void] * 6 + [ctypes.c_double, c_void]
     lib.vpk_mstep_batch.argtypes = [c_void, ctypes.c_int] + [c_void] * 8 + [ctypes.c_double] * 2 + [c_void] * 6

@@ -54,17 +54,21 @@ VPK_DEV int smooth_plan(const EmCtx& c, int M) {
 // ---------------------------------------------------------------------------------------------
 // the E-step's distance, per measure
 // ---------------------------------------------------------------------------------------------
-// The per-pair value lvsq[n][m] for the EM's two measures (vp_localisation.py:196-203) -- what differs between them; calc_plv, the p_l
-// chain with its floor, the panel layouts and the lanes per line behind it do not see the measure.  estep_device.hpp's
-// estep_lvsq<MEASURE>, restated operand for operand (that file restates this one; neither includes the other).
+// The per-pair value lvsq[n][m] per measure -- what differs between them; calc_plv, the p_l chain with its floor, the panel layouts
+// and the lanes per line behind it do not see the measure.  estep_device.hpp's estep_lvsq<MEASURE>, restated operand for operand
+// (that file restates this one; neither includes the other).  The EM runs the first two (vp_localisation.py:196-203; em_run asserts
+// it); "area" is instantiated by the stand-alone merge_vps alone (vpset_device.hpp).
 //   angle (:165-174):   the five rows line_geometry_setup<VPK_DIST_ANGLE> left in c.drow (midpoint, direction, its norm) against the
 //                       VP projected to the image plane (sh.vx, sh.vy, written by the prior part below); a VP at infinity is a NaN column.
 //   dotprod (:151-152): three rows, the normalised line c.l, against the VP as given in X (no division by v2: finite at infinity).
+//   area (:187-207):    five rows (midpoint, first end point, c = |midpoint - second end point|) against sh.vx, sh.vy; the VP's part of
+//                       vl = np.cross(v_, lmh) / |vl[0:2]| (estep_device.hpp's estep_vp<VPK_DIST_AREA>) is evaluated per pair from those
+//                       two, the same expressions on the same operands: Shared keeps its size.  A negative radicand is a NaN.
 struct EstepLine { double g0, g1, g2, g3, g4; };
 template <int MEASURE> VPK_DEV EstepLine estep_line(const EmCtx& c, int n) {
     EstepLine g;
     g.g0 = c.drow[n]; g.g1 = c.drow[(size_t)c.ldn + n]; g.g2 = c.drow[2 * (size_t)c.ldn + n];
-    if (MEASURE == VPK_DIST_ANGLE) { g.g3 = c.drow[3 * (size_t)c.ldn + n]; g.g4 = c.drow[4 * (size_t)c.ldn + n]; }
+    if (MEASURE != VPK_DIST_DOTPROD) { g.g3 = c.drow[3 * (size_t)c.ldn + n]; g.g4 = c.drow[4 * (size_t)c.ldn + n]; }
     else { g.g3 = 0.0; g.g4 = 0.0; }
     return g;
 }
@@ -74,9 +78,17 @@ template <int MEASURE> VPK_DEV double estep_pair(const EstepLine& g, const Share
         const double n1 = norm2(v1x, v1y);
         const double cc = 1 - fabs(dot2(v1x, v1y, g.g2, g.g3) / (n1 * g.g4));
         return cc * cc;                                      // :174
-    } else {
+    } else if (MEASURE == VPK_DIST_DOTPROD) {
         const double lv = (g.g0 * X[3 * m] + g.g1 * X[3 * m + 1]) + g.g2 * X[3 * m + 2];   // :151
         return lv * lv;                                      // :152
+    } else {
+        const double vx = sh.vx[m], vy = sh.vy[m];           // :187-188
+        const double nrm = norm2(vy, -vx);                   // :201
+        const double vl2 = (vx * g.g1 - vy * g.g0) / nrm;    // :200-201
+        const double b = fabs(((vy / nrm) * g.g2 + (-vx / nrm) * g.g3) + vl2);   // :203
+        const double a = sqrt(g.g4 * g.g4 - b * b);          // :205
+        const double t = (a * (b * b)) / g.g4;
+        return t * t;                                        // :207
     }
 }
 
@@ -224,7 +236,6 @@ VPK_DEV void estep_posteriors(vpmask_t keep, int m_lo, int m_hi, double pl, doub
 //  em_run's register allocation the line loop spills.  The phases stay functions of their own.)
 template <int MEASURE = VPK_DIST_ANGLE>
 VPK_DEVFN void estep(EmCtx& c, const double* X) {
-    static_assert(MEASURE == VPK_DIST_ANGLE || MEASURE == VPK_DIST_DOTPROD, "the EM runs \"angle\" and \"dotprod\" (vp_localisation.py:196-203)");
     Shared& sh = SH();
     const int M = sh.M, N = c.N;
     const double kk = -0.5 / (sh.sigma_prior * sh.sigma_prior);
@@ -246,8 +257,8 @@ VPK_DEVFN void estep(EmCtx& c, const double* X) {
             acc = group_sum<G>(acc);
             if (gl == 0) {
                 sh.pv[m] = acc;
-                if (MEASURE == VPK_DIST_ANGLE) {
-                    sh.vx[m] = x0 / x2;                      // calc_lvsq_angle :165-166
+                if (MEASURE != VPK_DIST_DOTPROD) {
+                    sh.vx[m] = x0 / x2;                      // calc_lvsq_angle :165-166, calc_lvsq_area :187-188
                     sh.vy[m] = x1 / x2;
                 }
                 double sm = sh.s[m];

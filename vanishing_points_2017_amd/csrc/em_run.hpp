@@ -148,6 +148,7 @@ VPK_DEVFN void restore_state(EmCtx& c) {
 // that suspended it (vpk_em_set_distance_measure refuses while images are parked).
 template <int MEASURE = VPK_DIST_ANGLE>
 VPK_DEVFN int em_run(EmCtx& c, EmOut& o, EmSlice& sl) {
+    static_assert(MEASURE == VPK_DIST_ANGLE || MEASURE == VPK_DIST_DOTPROD, "the EM runs \"angle\" and \"dotprod\" (vp_localisation.py:196-203)");
     Shared& sh = SH();
     const vpk_em_params& P = c.prm;
     const double max_stdd = MEASURE == VPK_DIST_DOTPROD ? 1e-3 : 1e-6;   // :196-201 (also s_init_factor)

@@ -552,6 +552,7 @@ VPK_DEVFN void initial_vps(EmCtx& c) {
 // iteration): midpoint, direction and its norm, in c.drow as [5][ldn]; the line probabilities p_l of the
 // current E-step follow at [5].
 // "dotprod" (calc_lvsq_dotprod :151): the three components of the normalised line c.l, in the first three rows.
+// "area" (calc_lvsq_area :192-204; the stand-alone merge_vps only): midpoint, first end point and c = |midpoint - second end point|.
 template <int MEASURE = VPK_DIST_ANGLE>
 VPK_DEVFN void line_geometry_setup(EmCtx& c) {
     for (int n = tid(); n < c.N; n += nthreads()) {
@@ -563,6 +564,15 @@ VPK_DEVFN void line_geometry_setup(EmCtx& c) {
             continue;
         }
         cgdp q = c.lp + 4 * (size_t)n;
+        if (MEASURE == VPK_DIST_AREA) {
+            const double mx = 0.5 * (q[0] + q[2]), my = 0.5 * (q[1] + q[3]);
+            c.drow[n] = mx;
+            c.drow[(size_t)c.ldn + n] = my;
+            c.drow[2 * (size_t)c.ldn + n] = q[0];
+            c.drow[3 * (size_t)c.ldn + n] = q[1];
+            c.drow[4 * (size_t)c.ldn + n] = norm2(mx - q[2], my - q[3]);
+            continue;
+        }
         const double v2x = q[0] - q[2], v2y = q[1] - q[3];
         c.drow[n] = 0.5 * (q[0] + q[2]);
         c.drow[(size_t)c.ldn + n] = 0.5 * (q[1] + q[3]);

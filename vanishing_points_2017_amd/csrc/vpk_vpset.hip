@@ -16,7 +16,15 @@ constexpr int VPSET_THREADS = 512;                     // the EM workgroup's sha
 constexpr size_t VPSET_LDS_BYTES = SH_BYTES + WT_DOUBLES * sizeof(double);   // [Shared | panel]: two workgroups per CU
 constexpr long long VPSET_NMAX = 32768;                // cluster2 indexes an n x n matrix with ints
 
-__global__ __launch_bounds__(VPSET_THREADS) void vpset_kernel(VpsetArgs a) { vpset_run(a); }
+// one kernel per distance measure, as vpk_em.hip and vpk_estep.hip have them: no run-time branch in a pair loop
+template <int MEASURE> __global__ __launch_bounds__(VPSET_THREADS) void vpset_kernel(VpsetArgs a) { vpset_run<MEASURE>(a); }
+
+typedef void (*vpset_kernel_t)(VpsetArgs);
+vpset_kernel_t kernel_of(int measure) {
+    return measure == VPK_DIST_DOTPROD ? vpset_kernel<VPK_DIST_DOTPROD>
+         : measure == VPK_DIST_AREA ? vpset_kernel<VPK_DIST_AREA> : vpset_kernel<VPK_DIST_ANGLE>;
+}
+bool known_measure(int measure) { return measure == VPK_DIST_ANGLE || measure == VPK_DIST_DOTPROD || measure == VPK_DIST_AREA; }
 
 // header: [line_off | vp_off | mat_off | ws_off] (batch + 1 each) and the active list; returns the number of active images
 int build_header(int batch, const int64_t* line_off, const int64_t* vp_off, int op, std::vector<int64_t>& hdr, long long* ws_doubles,
@@ -42,12 +50,14 @@ int build_header(int batch, const int64_t* line_off, const int64_t* vp_off, int 
     return active;
 }
 
-int launch(vpk_handle* h, int batch, const std::vector<int64_t>& hdr, int active, long long ws_doubles, VpsetArgs& a, const char* who) {
+int launch(vpk_handle* h, int measure, int batch, const std::vector<int64_t>& hdr, int active, long long ws_doubles, VpsetArgs& a,
+           const char* who) {
     VPK_HIP(h, hipSetDevice(h->device));
     if ((size_t)ws_doubles * 8 > h->total_mem / 2) return vpk_fail(h, VPK_ERR_LIMIT, "vpset: the batch's workspace exceeds half of the device memory");
     if (!h->vpset_ready) {
-        VPK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(vpset_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)VPSET_LDS_BYTES));
+        for (int m : {VPK_DIST_ANGLE, VPK_DIST_DOTPROD, VPK_DIST_AREA})
+            VPK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel_of(m)), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)VPSET_LDS_BYTES));
         h->vpset_ready = true;
     }
     int rc = vpk_reserve(h, &h->vpset_ws, &h->vpset_ws_bytes, (size_t)(ws_doubles > 0 ? ws_doubles : 32) * 8, "hipMalloc(vpset workspace)");
@@ -59,7 +69,7 @@ int launch(vpk_handle* h, int batch, const std::vector<int64_t>& hdr, int active
     a.line_off = d; a.vp_off = d + B1; a.mat_off = d + 2 * B1; a.ws_off = d + 3 * B1; a.active = d + 4 * B1;
     a.ws = (gdp)h->vpset_ws;
     a.wt_doubles = WT_DOUBLES;
-    hipLaunchKernelGGL(vpset_kernel, dim3((unsigned)active), dim3(VPSET_THREADS), VPSET_LDS_BYTES, h->stream, a);
+    hipLaunchKernelGGL(kernel_of(measure), dim3((unsigned)active), dim3(VPSET_THREADS), VPSET_LDS_BYTES, h->stream, a);
     VPK_HIP(h, hipGetLastError());
     return VPK_OK;
 }
@@ -77,10 +87,13 @@ int check_batch(vpk_handle* h, int batch, const int64_t* line_off, const int64_t
 
 extern "C" {
 
-int vpk_vp_line_counts_batch(vpk_handle* h, int batch, const int64_t* line_offsets, const int64_t* vp_offsets, const double* lp,
-                             const double* v, const double* s, const double* metric, const double* lweights, double thresh,
-                             const int64_t* vp_assoc_in, double* counts_out, double* counts_w_out, int64_t* vp_assoc_out) {
+int vpk_vp_line_counts_batch_measure(vpk_handle* h, int measure, int batch, const int64_t* line_offsets, const int64_t* vp_offsets,
+                                     const double* lp, const double* l, const double* v, const double* s, const double* metric,
+                                     const double* lweights, double thresh, const int64_t* vp_assoc_in, double* counts_out,
+                                     double* counts_w_out, int64_t* vp_assoc_out) {
     if (!h) return VPK_ERR_ARG;
+    if (!known_measure(measure)) return vpk_fail(h, VPK_ERR_ARG, "vpk_vp_line_counts_batch_measure: unknown measure");
+    if (measure == VPK_DIST_DOTPROD && !l) return vpk_fail(h, VPK_ERR_ARG, "vpk_vp_line_counts_batch_measure: \"dotprod\" reads l");
     bool done;
     int rc = check_batch(h, batch, line_offsets, vp_offsets, "vpk_vp_line_counts_batch: bad batch or offsets", &done);
     if (rc || done) return rc;
@@ -92,11 +105,18 @@ int vpk_vp_line_counts_batch(vpk_handle* h, int batch, const int64_t* line_offse
         return vpk_fail(h, VPK_ERR_ARG, "vpk_vp_line_counts_batch: null buffer");
     VpsetArgs a = {};
     a.op = VPSET_COUNTS;
-    a.lp = (cgdp)lp; a.v = (cgdp)v; a.s = (cgdp)s; a.w = (cgdp)metric; a.lweight = (cgdp)lweights;
+    a.lp = (cgdp)lp; a.l = (cgdp)l; a.v = (cgdp)v; a.s = (cgdp)s; a.w = (cgdp)metric; a.lweight = (cgdp)lweights;
     a.assoc_in = (cgllp)vp_assoc_in;
     a.thresh = thresh;
     a.counts = (gdp)counts_out; a.counts_w = (gdp)counts_w_out; a.assoc_out = (gllp)vp_assoc_out;
-    return launch(h, batch, hdr, active, ws, a, "vpk_vp_line_counts_batch: header");
+    return launch(h, measure, batch, hdr, active, ws, a, "vpk_vp_line_counts_batch: header");
+}
+
+int vpk_vp_line_counts_batch(vpk_handle* h, int batch, const int64_t* line_offsets, const int64_t* vp_offsets, const double* lp,
+                             const double* v, const double* s, const double* metric, const double* lweights, double thresh,
+                             const int64_t* vp_assoc_in, double* counts_out, double* counts_w_out, int64_t* vp_assoc_out) {
+    return vpk_vp_line_counts_batch_measure(h, VPK_DIST_ANGLE, batch, line_offsets, vp_offsets, lp, nullptr, v, s, metric, lweights, thresh,
+                                            vp_assoc_in, counts_out, counts_w_out, vp_assoc_out);
 }
 
 int vpk_vp_split_batch(vpk_handle* h, int batch, const int64_t* line_offsets, const int64_t* vp_offsets, const double* lp,
@@ -120,14 +140,16 @@ int vpk_vp_split_batch(vpk_handle* h, int batch, const int64_t* line_offsets, co
     a.thresh = min_diff;
     a.v_out = (gdp)v_out; a.s_out = (gdp)s_out; a.m_out = (gip)m_out; a.split_out = (gip)split_out;
     a.flags_out = (VPK_GLOBAL unsigned*)flags_out; a.labels_out = (gip)labels_out;
-    return launch(h, batch, hdr, active, ws, a, "vpk_vp_split_batch: header");
+    return launch(h, VPK_DIST_ANGLE, batch, hdr, active, ws, a, "vpk_vp_split_batch: header");
 }
 
-int vpk_vp_merge_batch(vpk_handle* h, int batch, const int64_t* line_offsets, const int64_t* vp_offsets, const double* lp,
-                       const double* l, const double* v, const double* s, const double* lweight, const int64_t* lsim_offsets,
-                       const double* lsim, double wbias, const float* prior_weights, double prior_sigma, double thresh,
-                       double max_stdd, double* v_out, double* s_out, int32_t* m_out, int32_t* keep_out, uint32_t* flags_out) {
+int vpk_vp_merge_batch_measure(vpk_handle* h, int measure, int batch, const int64_t* line_offsets, const int64_t* vp_offsets,
+                               const double* lp, const double* l, const double* v, const double* s, const double* lweight,
+                               const int64_t* lsim_offsets, const double* lsim, double wbias, const float* prior_weights,
+                               double prior_sigma, double thresh, double max_stdd, double* v_out, double* s_out, int32_t* m_out,
+                               int32_t* keep_out, uint32_t* flags_out) {
     if (!h) return VPK_ERR_ARG;
+    if (!known_measure(measure)) return vpk_fail(h, VPK_ERR_ARG, "vpk_vp_merge_batch_measure: unknown measure");
     bool done;
     int rc = check_batch(h, batch, line_offsets, vp_offsets, "vpk_vp_merge_batch: bad batch or offsets", &done);
     if (rc || done) return rc;
@@ -154,7 +176,15 @@ int vpk_vp_merge_batch(vpk_handle* h, int batch, const int64_t* line_offsets, co
     a.thresh = thresh; a.max_stdd = max_stdd;
     a.v_out = (gdp)v_out; a.s_out = (gdp)s_out; a.m_out = (gip)m_out; a.keep_out = (gip)keep_out;
     a.flags_out = (VPK_GLOBAL unsigned*)flags_out;
-    return launch(h, batch, hdr, active, ws, a, "vpk_vp_merge_batch: header");
+    return launch(h, measure, batch, hdr, active, ws, a, "vpk_vp_merge_batch: header");
+}
+
+int vpk_vp_merge_batch(vpk_handle* h, int batch, const int64_t* line_offsets, const int64_t* vp_offsets, const double* lp,
+                       const double* l, const double* v, const double* s, const double* lweight, const int64_t* lsim_offsets,
+                       const double* lsim, double wbias, const float* prior_weights, double prior_sigma, double thresh,
+                       double max_stdd, double* v_out, double* s_out, int32_t* m_out, int32_t* keep_out, uint32_t* flags_out) {
+    return vpk_vp_merge_batch_measure(h, VPK_DIST_ANGLE, batch, line_offsets, vp_offsets, lp, l, v, s, lweight, lsim_offsets, lsim, wbias,
+                                      prior_weights, prior_sigma, thresh, max_stdd, v_out, s_out, m_out, keep_out, flags_out);
 }
 
 }  // extern "C"

@@ -42,19 +42,37 @@ struct VpsetArgs {
     gip keep_out;
 };
 
-// calc_lvsq_single (probability_functions.py:212-224): the E-step's expression for one (VP, line) pair
-VPK_DEV double lvsq_single(cgdp v, cgdp q) {
+// The distance of the outlier test (:495-500) for one (VP, line) pair, on the caller's v, lp and l as they stand: the
+// reference normalises none of them here.
+//   angle    calc_lvsq_single (probability_functions.py:212-224): the E-step's lvsq of the pair
+//   dotprod  |vp[m] . l[n]| (:496), grouped as em_estep.hpp's estep_pair groups it; finite for a VP at infinity
+//   area     calc_lvsq_area_single (probability_functions.py:227-249): estep_device.hpp's estep_line / estep_vp /
+//            estep_lvsq<VPK_DIST_AREA> of the pair, restated operand for operand -- the E-step's lvsq again.  NaN where
+//            c^2 - b^2 < 0 (:245) and, as under "angle", for a VP with v[2] == 0.
+template <int MEASURE> VPK_DEV double vpset_dist(cgdp v, cgdp q, cgdp hl) {
+    if (MEASURE == VPK_DIST_DOTPROD) return fabs((hl[0] * v[0] + hl[1] * v[1]) + hl[2] * v[2]);
     const double vx = v[0] / v[2], vy = v[1] / v[2];
-    const double v1x = 0.5 * (q[0] + q[2]) - vx, v1y = 0.5 * (q[1] + q[3]) - vy;
-    const double v2x = q[0] - q[2], v2y = q[1] - q[3];
-    const double cc = 1 - fabs(dot2(v1x, v1y, v2x, v2y) / (norm2(v1x, v1y) * norm2(v2x, v2y)));
-    return cc * cc;
+    const double mx = 0.5 * (q[0] + q[2]), my = 0.5 * (q[1] + q[3]);
+    if (MEASURE == VPK_DIST_ANGLE) {
+        const double v1x = mx - vx, v1y = my - vy;
+        const double v2x = q[0] - q[2], v2y = q[1] - q[3];
+        const double cc = 1 - fabs(dot2(v1x, v1y, v2x, v2y) / (norm2(v1x, v1y) * norm2(v2x, v2y)));
+        return cc * cc;
+    }
+    const double nrm = norm2(vy, -vx);                        // :241
+    const double vl2 = (vx * my - vy * mx) / nrm;             // :240-241
+    const double b = fabs(((vy / nrm) * q[0] + (-vx / nrm) * q[1]) + vl2);   // :243
+    const double cl = norm2(mx - q[2], my - q[3]);            // :244
+    const double a = sqrt(cl * cl - b * b);                   // :245
+    const double t = (a * (b * b)) / cl;
+    return t * t;                                             // :247
 }
 
 // :486-507 up to the counting: c.assoc[n] = the line's VP or -1.  The argmax is assign_lines' (first maximum, a NaN
 // counts as the maximum); a caller's association is taken as it is, entries below 0 skip the line (:494) and entries
 // of M or more -- an IndexError in the reference -- skip it too.  The outlier test reads the CALLER's s: a NaN or
-// negative s[m] makes the comparison false and the line counts, as in the reference.
+// negative s[m] makes the comparison false and the line counts, as in the reference; so does a NaN distance.
+template <int MEASURE>
 VPK_DEVFN void vpset_assign(EmCtx& c, int M, cgdp v, cgdp s, cgllp assoc_in, double thresh) {
     const int N = c.N;
     for (int n = tid(); n < N; n += nthreads()) {
@@ -70,7 +88,8 @@ VPK_DEVFN void vpset_assign(EmCtx& c, int M, cgdp v, cgdp s, cgllp assoc_in, dou
             }
         }
         if (best >= 0) {
-            const double dist = lvsq_single(v + 3 * (size_t)best, c.lp + 4 * (size_t)n);
+            const double dist = vpset_dist<MEASURE>(v + 3 * (size_t)best, c.lp + 4 * (size_t)n,
+                                                    MEASURE == VPK_DIST_DOTPROD ? c.l + 3 * (size_t)n : c.lp);
             if (dist > thresh * sqrt(s[best])) best = -1;    // :504
             else if (c.lweight[n] == 0) best = -1;           // :506
         }
@@ -105,6 +124,7 @@ VPK_DEVFN void vpset_prior(const VPK_GLOBAL float* wts, double sigma) {
 // What the EM's set-up leaves for estep / smooth, from the caller's arrays: lsim in the slot's padded layout
 // (em_layout.hpp), its column sums in pairwise_setup's order (one wave per column, lanes over the rows in ascending
 // order), den (:522), the zero tail rows and the per-line constants.
+template <int MEASURE>
 VPK_DEVFN void vpset_merge_setup(EmCtx& c, cgdp lsim, cgdp lweight) {
     Shared& sh = SH();
     const int N = c.N;
@@ -124,9 +144,12 @@ VPK_DEVFN void vpset_merge_setup(EmCtx& c, cgdp lsim, cgdp lweight) {
     }
     block_sync();
     zero_tail_rows(c);
-    line_geometry_setup(c);
+    line_geometry_setup<MEASURE>(c);
 }
 
+// MEASURE: distance_measure, a compile-time parameter, one kernel per measure (vpk_vpset.hip).  It reaches the outlier
+// test of the counts and the E-step of a merge; split_best_vp has no measure and runs in the "angle" kernel.
+template <int MEASURE>
 VPK_DEV void vpset_run(const VpsetArgs& a) {
     Shared& sh = SH();
     const int b = (int)a.active[block_id()];
@@ -149,9 +172,9 @@ VPK_DEV void vpset_run(const VpsetArgs& a) {
         c.prm.wbias = a.wbias;
         bind_scratch(c, (double*)ws, a.L, false);
         vpset_prior(a.prior_w + (size_t)NCELL * b, a.prior_sigma);
-        vpset_merge_setup(c, a.lsim + a.mat_off[b], a.lweight + n0);
+        vpset_merge_setup<MEASURE>(c, a.lsim + a.mat_off[b], a.lweight + n0);
         // nxt is not touched by a merge of cur, and compact_vps moves it with its VP: nxt[3 k] = the index VP k came with
-        merge_vps(c, false, a.thresh, a.max_stdd);
+        merge_vps<MEASURE>(c, false, a.thresh, a.max_stdd);
         const int Mn = sh.M;
         for (int k = tid(); k < M; k += nthreads()) {
             const bool in = k < Mn;
@@ -167,8 +190,9 @@ VPK_DEV void vpset_run(const VpsetArgs& a) {
     c.lweight = (gdp)(a.lweight + n0);
     if (a.op == VPSET_COUNTS) {
         c.assoc = (gip)ws;                                    // N ints
+        if (MEASURE == VPK_DIST_DOTPROD) c.l = (gdp)(a.l + 3 * n0);
         cgllp ain = a.assoc_in ? a.assoc_in + n0 : (cgllp) nullptr;
-        vpset_assign(c, M, v, s, ain, a.thresh);
+        vpset_assign<MEASURE>(c, M, v, s, ain, a.thresh);
         count_lines(c);                                       // :509-510, the EM's summation order
         for (int k = tid(); k < M; k += nthreads()) { a.counts[m0 + k] = sh.cnt[k]; a.counts_w[m0 + k] = sh.cntw[k]; }
         for (int n = tid(); n < N; n += nthreads()) {
@@ -178,6 +202,7 @@ VPK_DEV void vpset_run(const VpsetArgs& a) {
         }
         return;
     }
+    if (MEASURE != VPK_DIST_ANGLE) return;                    // (split is launched under "angle" alone)
     // split: [cl N x N | pvl 3 N (staging of a very large set's directions) | assoc N ints | idx 3 N ints]
     c.l = (gdp)(a.l + 3 * n0);
     c.langle = (gdp)(a.langle + n0);

@@ -15,8 +15,8 @@ Deliberate differences of the E-step from the reference:
   - an unknown ``distance_measure`` raises ValueError (the reference falls through to a NameError at :114);
   - p_l is one sum over the VPs in ascending order, not np.dot's BLAS order (:116).
 The "area" measure is kept as the reference has it: np.cross of the 2-vector v_ (:200) measures from the line through the
-segment's midpoint in direction v_.  The EM itself, calc_vp_line_counts, split_best_vp and merge_vps still take "angle"
-only.
+segment's midpoint in direction v_.  vp_localisation's calc_vp_line_counts_batch and merge_vps_batch take the three
+measures too; the EM runs "angle" and "dotprod" (the reference asserts on "area" there), split_best_vp has no measure.
 
 Not here: calc_point (:261-266; dead, it overwrites its own first column) and calc_vp_line_triangles (no caller)."""
 from collections import namedtuple

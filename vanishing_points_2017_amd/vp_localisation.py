@@ -19,18 +19,19 @@ find_initial_vps_batch, weight_matrix_batch, calc_new_vanishing_point_batch and 
 error and removal step around it (:284-322 soft, :353-392 hard) -- take many images per launch, return device tensors and
 give, image by image, the bits of the single-image entry points.  With the prior, the E-step and the VP set functions a
 whole EM iteration is composed of device-resident calls (mstep_batch's docstring), under any of the E-step's distance
-measures.
+measures: prior, E-step, weights, M-step, counts and merge take all three; the split has none.
 
 VP set maintenance (vpk_vp_line_counts_batch, vpk_vp_split_batch, vpk_vp_merge_batch; include/vpk.h): calc_vp_line_counts
 (:482-512), split_best_vp (:527-630) and merge_vps (:633-684) on a VP set of the caller's, through the EM workgroup's own
 device functions; calc_angle_to_other_vp (:687-697) on the host.  The ``*_batch`` forms take many images per launch and
 return device tensors.  Deliberate differences from the reference: the caller's ``v``, ``s`` and ``vp_assoc`` arrays are
-not modified (the reference writes into them; the results are new arrays); ``distance_measure`` other than "angle",
-``numClusters`` other than 2 and more than 64 VPs raise ValueError.
+not modified (the reference writes into them; the results are new arrays); ``numClusters`` other than 2 and more than
+64 VPs raise ValueError.  calc_vp_line_counts_batch and merge_vps_batch take the reference's three measures
+(vpk_vp_line_counts_batch_measure, vpk_vp_merge_batch_measure); the single-image calc_vp_line_counts and merge_vps take
+"angle" and raise ValueError for the others.
 
 Not here: the scalar pair helpers (lines_similarity, lines_proximity, lines_points_cosangle, line_distance_closest,
-line_segment_point_distance: device functions of csrc/line_device.hpp) and, outside the EM, the distance measures other
-than "angle".
+line_segment_point_distance: device functions of csrc/line_device.hpp).
 There is no host fallback: without the library and a GPU every call but line_length and calc_angle_to_other_vp raises."""
 import numpy as np
 
@@ -254,21 +255,40 @@ VP_FLAG_SPLIT_TIE, VP_FLAG_SPLIT_DISCONNECTED, VP_FLAG_OVERFLOW, VP_FLAG_PRIOR_T
 
 
 def _check_measure(distance_measure):
+    """the single-image forms"""
     if distance_measure != "angle":
-        raise ValueError("distance_measure %r is not supported: only \"angle\" runs on the GPU" % (distance_measure,))
+        raise ValueError("distance_measure %r is not supported by the single-image form: use the *_batch form with one-image "
+                         "lists" % (distance_measure,))
+
+
+_MEASURES = {"angle": 0, "dotprod": 1, "area": 2}      # enum vpk_dist_measure (include/vpk.h)
+
+
+def _measure_code(distance_measure):
+    """the batch forms: the reference's three measures (:495-500)"""
+    if not isinstance(distance_measure, str) or distance_measure not in _MEASURES:
+        raise ValueError("distance_measure %r: one of \"angle\", \"dotprod\", \"area\"" % (distance_measure,))
+    return _MEASURES[distance_measure]
 
 
 def calc_vp_line_counts_batch(vps, lps, ss, decision_metrics, lweights, distance_measure="angle", thresh=2.57,
-                              vp_assocs=None, line_offsets=None, vp_offsets=None, device=0):
+                              vp_assocs=None, line_offsets=None, vp_offsets=None, device=0, ls=None):
     """calc_vp_line_counts for many images in one launch.  Every argument is a list with one array per image -- vp (M_b, 3),
     lp (N_b, 4), s (M_b,), decision_metric (M_b, N_b), lweights (N_b,), vp_assoc (N_b,) int64 -- or one concatenated
     array / device tensor with ``line_offsets`` / ``vp_offsets`` (host int64, B + 1); the metrics are then concatenated
     flat, image after image.  Returns (counts, counts_weighted, vp_assoc, line_offsets, vp_offsets): device tensors of
-    sum M, sum M and sum N (int64) elements.  An image without lines counts nothing; one without VPs associates nothing."""
-    _check_measure(distance_measure)
+    sum M, sum M and sum N (int64) elements.  An image without lines counts nothing; one without VPs associates nothing.
+
+    ``distance_measure``: "angle", "dotprod" or "area" (:495-500), evaluated on vps, ss and ls as they stand.  ``ls``: the
+    lines, (N_b, 3) each or concatenated; read by "dotprod" only, which needs them (|vp[m] . l[n]|, :496)."""
+    measure = _measure_code(distance_measure)
+    if distance_measure == "dotprod" and ls is None:
+        raise ValueError("distance_measure \"dotprod\" reads the lines: pass ls")
     lo = ragged.batch_offsets(lps, line_offsets, "lps")
     vo = ragged.batch_offsets(vps, vp_offsets, "vps")
     ragged.check_images(lo, vo, "lps", "vps")
+    if distance_measure == "dotprod":
+        ragged.check_total(ls, lo[-1], "ls", 3, "rows")
     if decision_metrics is None and vp_assocs is None:
         raise ValueError("decision_metrics or vp_assocs is needed")
     if decision_metrics is not None and ragged.total(decision_metrics) != ragged.mats_total(lo, vo):
@@ -281,6 +301,7 @@ def calc_vp_line_counts_batch(vps, lps, ss, decision_metrics, lweights, distance
     t = rt.torch
     with rt.on_stream():
         d_lp = ragged.upload(rt, lps, np.float64, (4,))
+        d_l = ragged.upload(rt, ls, np.float64, (3,)) if distance_measure == "dotprod" else None
         d_v = ragged.upload(rt, vps, np.float64, (3,))
         d_s = ragged.upload(rt, ss, np.float64)
         d_lw = ragged.upload(rt, lweights, np.float64)
@@ -289,9 +310,10 @@ def calc_vp_line_counts_batch(vps, lps, ss, decision_metrics, lweights, distance
         counts = t.zeros((int(vo[-1]),), dtype=t.float64, device=rt.tdev)
         counts_w = t.zeros_like(counts)
         assoc = d_ain.clone() if d_ain is not None else t.full((int(lo[-1]),), -1, dtype=t.int64, device=rt.tdev)
-        rt.check(rt.lib.vpk_vp_line_counts_batch(rt.h, lo.shape[0] - 1, ragged.off_ptr(lo), ragged.off_ptr(vo), rt.ptr(d_lp),
-                                                 rt.ptr(d_v), rt.ptr(d_s), rt.ptr(d_w), rt.ptr(d_lw), float(thresh), rt.ptr(d_ain),
-                                                 rt.ptr(counts), rt.ptr(counts_w), rt.ptr(assoc)))
+        rt.check(rt.lib.vpk_vp_line_counts_batch_measure(rt.h, measure, lo.shape[0] - 1, ragged.off_ptr(lo), ragged.off_ptr(vo),
+                                                         rt.ptr(d_lp), rt.ptr(d_l), rt.ptr(d_v), rt.ptr(d_s), rt.ptr(d_w), rt.ptr(d_lw),
+                                                         float(thresh), rt.ptr(d_ain), rt.ptr(counts), rt.ptr(counts_w),
+                                                         rt.ptr(assoc)))
     rt.synchronize()
     return counts, counts_w, assoc, lo, vo
 
@@ -301,7 +323,8 @@ def calc_vp_line_counts(vp, l, lp, s, decision_metric, lweights, distance_measur
     variances ``s``.  ``vp_assoc`` None: every line goes to the argmax of ``decision_metric`` (M, N) over the VPs (:487);
     given, entries below 0 skip their line (:494).  A line farther than thresh * sqrt(s[m]) from its VP (:504) or of
     weight 0 (:506) gets -1.  ``l`` is not read by the "angle" measure.  The result's vp_assoc is a new int64 array: the
-    caller's is not written.  It is what result_plotting.line_primitives takes as a datum's ``vp_assoc``."""
+    caller's is not written.  It is what result_plotting.line_primitives takes as a datum's ``vp_assoc``.
+    This single-image form takes "angle" only; "dotprod" and "area": calc_vp_line_counts_batch with one-image lists."""
     _check_measure(distance_measure)
     vp = np.asarray(vp, dtype=np.float64).reshape(-1, 3)
     lp = _check_lp(lp)
@@ -407,7 +430,9 @@ def merge_vps_batch(vs, ss, ls, thresh, lweights, lsims, wbias, pdfpar, lps, lle
     """merge_vps on slice i of many images' history arrays in one launch; arguments as in calc_vp_line_counts_batch (vs:
     (M_b, 3) each, ls (N_b, 3) normalised lines).  ``lsims``: the images' plain (N_b, N_b) matrices as a list -- the
     list calc_lsim_batch returns is used where it lies -- or concatenated flat.  ``pdfpar``: PDFParams with weights (B, 400),
-    as pdf_params_batch returns.  ``llens`` is not read by the "angle" measure.  Returns a dict of device tensors: 'v'
+    as pdf_params_batch returns.  ``llens`` is read by none of the reference's measures and is not used.
+    ``distance_measure``: "angle", "dotprod" or "area", the measure of every round's E-step (:658); ``max_stdd`` is the
+    caller's under each of them (the EM passes 0.01, :339, :448).  Returns a dict of device tensors: 'v'
     (sum M, 3), 's' (sum M,) and 'kept' (sum M,) int32: image b's rows start at vp_offsets[b], 'num_vp' (B,) of them are the
     merged set and the indices its VPs came with, the rest zeros and -1; 'flags' (B,) int32; and the host offsets.
 
@@ -418,7 +443,7 @@ def merge_vps_batch(vs, ss, ls, thresh, lweights, lsims, wbias, pdfpar, lps, lle
         par = pdf_params_batch(d_maps)
         r = merge_vps_batch(d_v, d_s, d_l, 1e-3, llen * lscore.clamp(0.2, 1), lsims, 1, par, d_lp,
                             line_offsets=off, vp_offsets=vp_off)"""
-    _check_measure(distance_measure)
+    measure = _measure_code(distance_measure)
     lo = ragged.batch_offsets(lps, line_offsets, "lps")
     vo = ragged.batch_offsets(vs, vp_offsets, "vs")
     ragged.check_images(lo, vo, "lps", "vs")
@@ -445,10 +470,10 @@ def merge_vps_batch(vs, ss, ls, thresh, lweights, lsims, wbias, pdfpar, lps, lle
         kept = t.cat([t.arange(int(m), dtype=t.int32, device=rt.tdev) for m in np.diff(vo)]) if B else \
             t.zeros((0,), dtype=t.int32, device=rt.tdev)
         flags = t.zeros((B,), dtype=t.int32, device=rt.tdev)
-        rt.check(rt.lib.vpk_vp_merge_batch(rt.h, B, ragged.off_ptr(lo), ragged.off_ptr(vo), rt.ptr(d_lp), rt.ptr(d_l), rt.ptr(d_v),
-                                           rt.ptr(d_s), rt.ptr(d_lw), ragged.off_ptr(lsim_off), lsim_ptr, float(wbias),
-                                           rt.ptr(d_pw), float(pdfpar.sigma), float(thresh), float(max_stdd), rt.ptr(v_out),
-                                           rt.ptr(s_out), rt.ptr(num), rt.ptr(kept), rt.ptr(flags)))
+        rt.check(rt.lib.vpk_vp_merge_batch_measure(rt.h, measure, B, ragged.off_ptr(lo), ragged.off_ptr(vo), rt.ptr(d_lp), rt.ptr(d_l),
+                                                   rt.ptr(d_v), rt.ptr(d_s), rt.ptr(d_lw), ragged.off_ptr(lsim_off), lsim_ptr,
+                                                   float(wbias), rt.ptr(d_pw), float(pdfpar.sigma), float(thresh), float(max_stdd),
+                                                   rt.ptr(v_out), rt.ptr(s_out), rt.ptr(num), rt.ptr(kept), rt.ptr(flags)))
     rt.synchronize()
     del lsim_keep
     return {'v': v_out, 's': s_out, 'num_vp': num, 'kept': kept, 'flags': flags, 'line_offsets': lo, 'vp_offsets': vo}
@@ -459,7 +484,8 @@ def merge_vps(i, v, s, l, thresh, lweight, lsim, wbias, pdfpar, lp, llen, distan
     """merge_vps (:633-684) on slice ``i`` of the (T, M, 3) history array ``v``: {'v', 's'}.  While the two closest VPs
     are closer than ``thresh``, they are merged into the second (column j is deleted from every slice, :674) until a merge
     is given up (new VP None, or s[k] > max_stdd -- s[k] is returned as changed, :666-668).  ``pdfpar`` is what this
-    package's pdf_params returns.  Returned arrays are new; the caller's v and s are not written."""
+    package's pdf_params returns.  Returned arrays are new; the caller's v and s are not written.
+    This single-image form takes "angle" only; "dotprod" and "area": merge_vps_batch with one-image lists."""
     _check_measure(distance_measure)
     v, s, vi = _history(v, s, i)
     M = v.shape[1]
