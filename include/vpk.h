@@ -850,6 +850,62 @@ int vpk_horizon_error_batch(vpk_handle* h, int batch, const double* horizon, con
  * nothing is launched.  Asynchronous on the handle's stream. */
 int vpk_auc(vpk_handle* h, int n, const double* err, double cutoff, double* sorted_out, double* auc_out);
 
+/* ---- fine-tuning the dense head: train/train_val.prototxt:289-417 under train/solver.prototxt -------------------------
+ * The trainer keeps fp32 master copies of fc6 [H6 x I], fc7 [H7 x H6] and fc8 [O x H7] with their biases, a momentum
+ * buffer for each, and the activations of one step.  It is separate from the forward's packed weights: a trained head
+ * reaches a forward through vpk_train_store and vpk_cnn_load.  The conv stack below is frozen: the input X is
+ * vpk_cnn_forward_tap's tap 7 (pool5), B x I in Caffe's C x H x W order.
+ *
+ * The solver's numbers; vpk_train_default_params sets the prototxts' values. */
+typedef struct vpk_train_params {
+    float base_lr;            /* solver.prototxt:8   1e-4 */
+    float gamma;              /* :10  0.1; lr = base_lr * gamma^floor(iteration / stepsize) (lr_policy "step", :9) */
+    int64_t stepsize;         /* :11  200000 */
+    float momentum;           /* :17  0.9 */
+    float weight_decay;       /* :18  5e-4 */
+    float lr_mult_weight;     /* train_val.prototxt:295, 335, 375   1 */
+    float decay_mult_weight;  /* :296, 336, 376   1 */
+    float lr_mult_bias;       /* :299, 339, 379   2 */
+    float decay_mult_bias;    /* :300, 340, 380   0 */
+    float dropout_ratio;      /* :326, 366   0.5 */
+} vpk_train_params;
+void vpk_train_default_params(vpk_train_params* p);
+/* dims = (I, H6, H7, O), all >= 1 (else VPK_ERR_ARG); the net's are (57600, 4096, 4096, 400).  Allocates weights, momentum,
+ * activations and the backward's workspace; one trainer per handle (a second create: VPK_ERR_STATE).  vpk_destroy frees it. */
+int vpk_train_create(vpk_handle* h, const int32_t dims[4]);
+int vpk_train_destroy(vpk_handle* h);
+/* dropout_ratio in [0, 1) and stepsize >= 1, else VPK_ERR_ARG.  Takes effect with the next step. */
+int vpk_train_set_params(vpk_handle* h, const vpk_train_params* p);
+/* blobs [host]: fp32 fc6 weight, fc6 bias, fc7 weight, fc7 bias, fc8 weight, fc8 bias -- the last six of vpk_cnn_load's.
+ * vpk_train_load zeroes the momentum and the iteration counter (a solver started from a caffemodel);
+ * vpk_train_load_momentum / vpk_train_store_momentum move the momentum in the same layout (the history of a solverstate).
+ * All four wait for the handle's stream.  Before vpk_train_load the other three return VPK_ERR_STATE. */
+int vpk_train_load(vpk_handle* h, const void* const blobs[6]);
+int vpk_train_store(vpk_handle* h, void* const blobs_out[6]);
+int vpk_train_load_momentum(vpk_handle* h, const void* const blobs[6]);
+int vpk_train_store_momentum(vpk_handle* h, void* const blobs_out[6]);
+/* the solver's iteration: it selects the learning rate (solver.prototxt:8-11) and keys the generated dropout masks */
+int vpk_train_set_iteration(vpk_handle* h, long long iteration);
+int vpk_train_get_iteration(const vpk_handle* h, long long* iteration_out);
+/* One solver iteration on a batch of 1 <= B <= 32 rows (the prototxt's batch size is 5, train_val.prototxt:14); B outside that
+ * range: VPK_ERR_LIMIT before anything is launched, the state is unchanged.  All pointers are device pointers.
+ *   forward (TRAIN phase, :289-393)  a6 = relu(X W6^T + b6), d6 = a6 m6 / (1 - p); the same for fc7; z = d7 W8^T + b8
+ *   loss (:411-417)  sum over B x O of max(z,0) - z t + log1p(exp(-|z|)), divided by B; dz = (sigmoid(z) - t) / B
+ *   backward         dW = dY^T X, db = sum_b dY, dX = dY W through dropout and ReLU; no dX below fc6
+ *   update (solver.prototxt:1, 17, 18)  V <- momentum V + lr_local (dW + decay_local W), W <- W - V
+ *   X          B x I fp32          labels  B x O fp32 in [0, 1]
+ *   mask6/7    B x H6 / B x H7 uint8 0/1 keep masks, both or neither (else VPK_ERR_ARG).  NULL: generated from
+ *              (seed, iteration, layer, b, j) by the counter-based hash documented in csrc/train_device.hpp
+ *   loss_out   1 fp32 (may be NULL)    sigout_out  B x O fp32: sigmoid(z), the prototxt's sigout (:419-424; may be NULL)
+ * Each layer's weights are read once by the forward, and read and written once, with their momentum, by a fused
+ * backward-and-update sweep; no float atomics, so the same state and inputs give the same bits.  Asynchronous on the
+ * handle's stream; increments the iteration. */
+int vpk_train_step(vpk_handle* h, const float* X, const float* labels, int B, const uint8_t* mask6, const uint8_t* mask7,
+                   unsigned long long seed, float* loss_out, float* sigout_out);
+/* The TEST phase of the same net (:289-424 without Dropout's mask and scale) on any B >= 1, in chunks of 32; changes no
+ * weight.  labels may be NULL (then loss_out is not written); with labels, loss_out is required.  The loss is divided by B. */
+int vpk_train_eval(vpk_handle* h, const float* X, const float* labels, int B, float* loss_out, float* sigout_out);
+
 #ifdef __cplusplus
 }
 #endif

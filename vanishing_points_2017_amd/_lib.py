@@ -59,6 +59,14 @@ class StepArgs(ctypes.Structure):
                 ("reuse_event", ctypes.c_void_p), ("em_prior", ctypes.c_void_p)]
 
 
+class TrainParams(ctypes.Structure):
+    """vpk_train_params (include/vpk.h): the numbers of train/solver.prototxt and of the head's layers in train_val.prototxt."""
+    _fields_ = [("base_lr", ctypes.c_float), ("gamma", ctypes.c_float), ("stepsize", ctypes.c_int64),
+                ("momentum", ctypes.c_float), ("weight_decay", ctypes.c_float), ("lr_mult_weight", ctypes.c_float),
+                ("decay_mult_weight", ctypes.c_float), ("lr_mult_bias", ctypes.c_float),
+                ("decay_mult_bias", ctypes.c_float), ("dropout_ratio", ctypes.c_float)]
+
+
 EXPORTS = [
     "vpk_create", "vpk_destroy", "vpk_set_stream", "vpk_get_stream", "vpk_synchronize", "vpk_last_error", "vpk_version",
     "vpk_em_default_params", "vpk_device_info", "vpk_em_set_workgroups", "vpk_em_set_smoother", "vpk_em_set_lds_panel", "vpk_em_set_distance_measure", "vpk_em_set_time_slice", "vpk_em_flush", "vpk_em_set_distribution_out", "vpk_cnn_load", "vpk_cnn_forward", "vpk_cnn_forward_tap",
@@ -80,6 +88,9 @@ EXPORTS = [
     "vpk_weight_matrix_batch", "vpk_mstep_batch", "vpk_init_vps_batch",
     "vpk_vp_order_batch", "vpk_to_pixels_batch",
     "vpk_horizon_error_batch", "vpk_auc",
+    "vpk_train_default_params", "vpk_train_create", "vpk_train_destroy", "vpk_train_set_params",
+    "vpk_train_load", "vpk_train_store", "vpk_train_load_momentum", "vpk_train_store_momentum",
+    "vpk_train_set_iteration", "vpk_train_get_iteration", "vpk_train_step", "vpk_train_eval",
 ]
 
 _lib = None
@@ -188,6 +199,17 @@ def load():
     lib.vpk_to_pixels_batch.argtypes = [c_void, ctypes.c_int, c_void, c_void, c_void, ctypes.c_int] + [c_void] * 6
     lib.vpk_horizon_error_batch.argtypes = [c_void, ctypes.c_int] + [c_void] * 4
     lib.vpk_auc.argtypes = [c_void, ctypes.c_int, c_void, ctypes.c_double, c_void, c_void]
+    lib.vpk_train_default_params.argtypes = [ctypes.POINTER(TrainParams)]
+    lib.vpk_train_default_params.restype = None
+    lib.vpk_train_create.argtypes = [c_void, ctypes.POINTER(ctypes.c_int32)]
+    lib.vpk_train_destroy.argtypes = [c_void]
+    lib.vpk_train_set_params.argtypes = [c_void, ctypes.POINTER(TrainParams)]
+    for fn in (lib.vpk_train_load, lib.vpk_train_store, lib.vpk_train_load_momentum, lib.vpk_train_store_momentum):
+        fn.argtypes = [c_void, ctypes.POINTER(c_void)]
+    lib.vpk_train_set_iteration.argtypes = [c_void, ctypes.c_longlong]
+    lib.vpk_train_get_iteration.argtypes = [c_void, ctypes.POINTER(ctypes.c_longlong)]
+    lib.vpk_train_step.argtypes = [c_void, c_void, c_void, ctypes.c_int, c_void, c_void, ctypes.c_ulonglong, c_void, c_void]
+    lib.vpk_train_eval.argtypes = [c_void, c_void, c_void, ctypes.c_int, c_void, c_void]
     _lib = lib
     return lib
 

@@ -93,6 +93,7 @@ int vpk_destroy(vpk_handle* h) {
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
     vpk_cnn_free(h);
+    vpk_train_free(h);
     if (h->em_ws) (void)hipFree(h->em_ws);
     if (h->em_hdr) (void)hipFree(h->em_hdr);
     if (h->em_sess) (void)hipFree(h->em_sess);

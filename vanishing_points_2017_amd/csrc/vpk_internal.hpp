@@ -11,6 +11,7 @@
 #include "em_layout.hpp"
 
 struct vpk_cnn_state;   // vpk_cnn.hip
+struct vpk_train_state; // vpk_train.hip
 
 // a device header uploaded through pinned staging: the staging is reused once the event of the previous upload has fired
 struct vpk_staged {
@@ -111,6 +112,7 @@ struct vpk_handle {
     bool emstep_ready = false;       // dynamic-LDS attribute set on the kernel
     vpk_staged detect_hdr;           // vpk_to_pixels_batch (vpk_detect.hip): line offsets + image sizes
     vpk_staged score_hdr;            // vpk_horizon_error_batch (vpk_score.hip): image sizes
+    vpk_train_state* train = nullptr; // vpk_train_create (vpk_train.hip): the dense head's master weights, momentum, activations
 };
 
 // the LDS budget vpk_em_batch launches with under the handle's vpk_em_set_lds_panel setting (vpk_em.hip: em_mode): the
@@ -122,6 +124,7 @@ int vpk_fail(vpk_handle* h, int code, const char* what);
 int vpk_fail_hip(vpk_handle* h, hipError_t e, const char* what);
 int vpk_reserve(vpk_handle* h, void** p, size_t* have, size_t want, const char* what);
 void vpk_cnn_free(vpk_handle* h);
+void vpk_train_free(vpk_handle* h);
 // copies `bytes` of `src` to s.dev through s's pinned staging, asynchronously on the handle's stream
 int vpk_stage_upload(vpk_handle* h, vpk_staged& s, const void* src, size_t bytes, const char* what);
 
