@@ -48,6 +48,8 @@ struct Shared {
 
 constexpr size_t SH_BYTES = (sizeof(Shared) + 15) / 16 * 16;
 static_assert(sizeof(Shared) % 8 == 0 && sizeof(Shared) <= EM_STATE_DOUBLES * 8, "Shared must fit the slot's state region");
+// dynamic LDS of a launch with the default panel: [Shared | smoother operand tile]; ~77 KiB -> two workgroups per CU (160 KiB)
+constexpr size_t EM_LDS_BYTES = SH_BYTES + WT_DOUBLES * sizeof(double);
 // LDS layout of every EM kernel: [Shared | smoother operand panel]
 VPK_DEV Shared& SH() { return *reinterpret_cast<Shared*>(lds_base()); }
 VPK_DEV double* WT() { return reinterpret_cast<double*>(lds_base() + SH_BYTES); }

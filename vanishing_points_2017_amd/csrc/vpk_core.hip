@@ -32,24 +32,36 @@ int vpk_reserve(vpk_handle* h, void** p, size_t* have, size_t want, const char* 
     return VPK_OK;
 }
 
-// copies `bytes` of `src` to s.dev through s's pinned staging, asynchronously on the handle's stream
-int vpk_stage_upload(vpk_handle* h, vpk_staged& s, const void* src, size_t bytes, const char* what) {
-    if (s.ev_valid) VPK_HIP(h, hipEventSynchronize(s.ev));    // the previous call's upload has left the staging
-    if (s.host_bytes < bytes) {
-        if (s.host) VPK_HIP(h, hipHostFree(s.host));
-        s.host = nullptr;
-        s.host_bytes = 0;
-        VPK_HIP(h, hipHostMalloc(&s.host, bytes, hipHostMallocDefault));
-        s.host_bytes = bytes;
+// the staged uploads (vpk_internal.hpp).  The device header is rewritten by a stream-ordered copy (after the previous
+// launch that read it), so only the pinned staging needs care: begin waits for the copy that last used the ring slot.
+int vpk_stage_begin(vpk_handle* h, vpk_staged& s, size_t bytes, void** host) {
+    auto& r = s.ring[s.cur];
+    if (r.ev_valid) VPK_HIP(h, hipEventSynchronize(r.ev));
+    if (r.bytes < bytes) {
+        if (r.host) VPK_HIP(h, hipHostFree(r.host));
+        r.host = nullptr; r.bytes = 0;
+        VPK_HIP(h, hipHostMalloc(&r.host, bytes * 2, hipHostMallocDefault));   // twice the need: a growing batch rarely reallocates
+        r.bytes = bytes * 2;
     }
-    if (!s.ev) VPK_HIP(h, hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-    memcpy(s.host, src, bytes);
-    const int rc = vpk_reserve(h, &s.dev, &s.dev_bytes, bytes, what);
-    if (rc) return rc;
-    VPK_HIP(h, hipMemcpyAsync(s.dev, s.host, bytes, hipMemcpyHostToDevice, h->stream));
-    VPK_HIP(h, hipEventRecord(s.ev, h->stream));
-    s.ev_valid = true;
+    if (!r.ev) VPK_HIP(h, hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
+    *host = r.host;
     return VPK_OK;
+}
+int vpk_stage_commit(vpk_handle* h, vpk_staged& s, size_t bytes, const char* what, size_t tail) {
+    auto& r = s.ring[s.cur];
+    const int rc = vpk_reserve(h, &s.dev, &s.dev_bytes, bytes + tail, what);
+    if (rc) return rc;
+    VPK_HIP(h, hipMemcpyAsync(s.dev, r.host, bytes, hipMemcpyHostToDevice, h->stream));
+    VPK_HIP(h, hipEventRecord(r.ev, h->stream));
+    r.ev_valid = true;
+    s.cur = (s.cur + 1) % s.depth;
+    return VPK_OK;
+}
+int vpk_stage_upload(vpk_handle* h, vpk_staged& s, const void* src, size_t bytes, const char* what) {
+    void* host;
+    if (int rc = vpk_stage_begin(h, s, bytes, &host)) return rc;
+    memcpy(host, src, bytes);
+    return vpk_stage_commit(h, s, bytes, what);
 }
 
 extern "C" {
@@ -94,29 +106,17 @@ int vpk_destroy(vpk_handle* h) {
     (void)hipStreamSynchronize(h->stream);
     vpk_cnn_free(h);
     vpk_train_free(h);
-    if (h->em_ws) (void)hipFree(h->em_ws);
-    if (h->em_hdr) (void)hipFree(h->em_hdr);
-    if (h->em_sess) (void)hipFree(h->em_sess);
     if (h->step_event) (void)hipEventDestroy(h->step_event);
-    for (int i = 0; i < vpk_handle::VPK_HDR_RING; ++i) {
-        if (h->em_hdr_host[i]) (void)hipHostFree(h->em_hdr_host[i]);
-        if (h->em_hdr_ev[i]) (void)hipEventDestroy(h->em_hdr_ev[i]);
-    }
-    if (h->small_ws) (void)hipFree(h->small_ws);
-    if (h->raster_hdr) (void)hipFree(h->raster_hdr);
-    if (h->lsd_ws) (void)hipFree(h->lsd_ws);
-    if (h->lsd_hdr) (void)hipFree(h->lsd_hdr);
-    if (h->lsd_host) (void)hipHostFree(h->lsd_host);
-    if (h->lsd_ev) (void)hipEventDestroy(h->lsd_ev);
-    if (h->vpset_ws) (void)hipFree(h->vpset_ws);
-    if (h->emstep_ws) (void)hipFree(h->emstep_ws);
-    for (vpk_staged* s : {&h->fe_prep, &h->fe_rows, &h->lines_hdr, &h->overlay_hdr, &h->vpset_hdr, &h->estep_hdr, &h->emstep_hdr,
-                          &h->detect_hdr, &h->score_hdr}) {
+    for (void* p : {h->em_ws, h->em_sess, h->small_ws, h->raster_hdr, h->lsd_ws, h->vpset_ws, h->emstep_ws, h->fe_ws})
+        if (p) (void)hipFree(p);
+    for (vpk_staged* s : {&h->em_hdr, &h->lsd_hdr, &h->fe_prep, &h->fe_rows, &h->lines_hdr, &h->overlay_hdr, &h->vpset_hdr,
+                          &h->estep_hdr, &h->emstep_hdr, &h->detect_hdr, &h->score_hdr}) {
         if (s->dev) (void)hipFree(s->dev);
-        if (s->host) (void)hipHostFree(s->host);
-        if (s->ev) (void)hipEventDestroy(s->ev);
+        for (auto& r : s->ring) {
+            if (r.host) (void)hipHostFree(r.host);
+            if (r.ev) (void)hipEventDestroy(r.ev);
+        }
     }
-    if (h->fe_ws) (void)hipFree(h->fe_ws);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return VPK_OK;

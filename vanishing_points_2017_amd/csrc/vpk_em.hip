@@ -3,34 +3,22 @@
 //
 // Compiled with -ffp-contract=off (see em_device.hpp).  One persistent workgroup of EM_THREADS
 // threads per slot; workgroups pull images from a device-side queue (largest N first), so a
-// ragged batch keeps every CU busy without host round trips.
+// ragged batch keeps every CU busy without host round trips.  What vpk_em_batch decides on the host before it
+// launches -- the rules, slots and workgroups, the session's refusals, the header and session layouts -- is em_plan.hpp's.
 #include "em_hooks.hpp"
+#include "em_plan.hpp"
 #include "vpk_internal.hpp"
-
-#include <algorithm>
-#include <string.h>
-#include <numeric>
-#include <vector>
 
 using namespace vpk;
 
 namespace {
 
-constexpr int EM_THREADS = 512;   // 8 waves: 2 per SIMD
 // One workgroup per CU: the (non-inlined) phase functions touch ~250 VGPRs each -- the calling
 // convention's callee-saved registers are striped through the file, so the allocator spreads over all of
 // it -- and two waves per SIMD fill the register file.  Declaring the kernels for 1024 threads makes
 // hipcc give the phases 128 VGPRs and two workgroups fit, but measured (r1): every phase slows down by
 // 15-40 % (spills, narrower smoother) and the batch gains nothing at YUD sizes, +5 % at the stress shape.
 constexpr int EM_BOUND = EM_THREADS;
-constexpr int EM_WAVES = EM_THREADS / 64;
-// dynamic LDS: [Shared | smoother operand tile]; ~77 KiB -> two workgroups per CU (160 KiB)
-constexpr size_t EM_LDS_BYTES = SH_BYTES + WT_DOUBLES * sizeof(double);
-// when a batch leaves at most one workgroup per CU, the workgroup takes (almost) the whole 160 KiB so
-// that the smoother's operand panel of any YUD/ECD-sized image fits and lsim is read once per E-step
-constexpr int WT_DOUBLES_BIG = (int)((163840 - SH_BYTES) / sizeof(double)) / 32 * 32;   // everything a CU has (~147 KiB)
-constexpr size_t EM_LDS_BYTES_BIG = SH_BYTES + WT_DOUBLES_BIG * sizeof(double);
-static_assert(EM_LDS_BYTES_BIG <= 163840, "LDS per CU");
 #define VPK_SHARED_DECL Shared& sh = SH()
 
 struct EmBatchArgs {
@@ -368,26 +356,13 @@ __global__ __launch_bounds__(EM_BOUND) void cluster2_kernel(int n, double* D, in
     hook_cluster2(n, D, member, csize, labels_out, flags_out, smoother, wt_doubles);
 }
 
-template <typename K>
-int allow_lds(vpk_handle* h, K kernel) {
-    VPK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)EM_LDS_BYTES_BIG));
-    return VPK_OK;
-}
 int em_prepare(vpk_handle* h) {
     if (h->em_ready) return VPK_OK;
-    int rc;
-    if ((rc = allow_lds(h, em_batch_kernel<VPK_DIST_ANGLE>))) return rc;
-    if ((rc = allow_lds(h, em_batch_kernel<VPK_DIST_DOTPROD>))) return rc;
-    if ((rc = allow_lds(h, pairwise_kernel))) return rc;
-    if ((rc = allow_lds(h, init_vps_kernel))) return rc;
-    if ((rc = allow_lds(h, estep_kernel))) return rc;
-    if ((rc = allow_lds(h, weight_matrix_kernel))) return rc;
-    if ((rc = allow_lds(h, estep_smooth_kernel))) return rc;
-    if ((rc = allow_lds(h, mstep_kernel))) return rc;
-    if ((rc = allow_lds(h, mstep_full_kernel))) return rc;
-    if ((rc = allow_lds(h, cluster2_kernel))) return rc;
-    if ((rc = allow_lds(h, line_counts_kernel))) return rc;
+    for (auto kernel : {(const void*)em_batch_kernel<VPK_DIST_ANGLE>, (const void*)em_batch_kernel<VPK_DIST_DOTPROD>,
+                        (const void*)pairwise_kernel, (const void*)init_vps_kernel, (const void*)estep_kernel,
+                        (const void*)weight_matrix_kernel, (const void*)estep_smooth_kernel, (const void*)mstep_kernel,
+                        (const void*)mstep_full_kernel, (const void*)cluster2_kernel, (const void*)line_counts_kernel})
+        VPK_HIP(h, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)EM_LDS_BYTES_BIG));
     h->em_ready = true;
     return VPK_OK;
 }
@@ -407,68 +382,29 @@ int hook_launch(vpk_handle* h, void (*kernel)(P...), size_t lds_bytes, A... args
     return VPK_OK;
 }
 
-// One workgroup per CU (see EM_BOUND), with the whole remaining LDS (128 KiB) as the smoother's operand
-// panel: single-pass smoothing for every image whose N x W panel fits.
-struct EmMode { int per_cu; int wt_doubles; size_t lds_bytes; };
-EmMode em_mode(const vpk_handle* h) {
-    if (h->em_lds_doubles <= 0) return EmMode{1, WT_DOUBLES_BIG, EM_LDS_BYTES_BIG};
-    // vpk_em_set_lds_panel: the budget the phases PLAN with; the launch still gets at least the setup phases' scratch
-    const int wt = std::min(std::max(h->em_lds_doubles, 64), WT_DOUBLES_BIG);
-    return EmMode{1, wt, SH_BYTES + (size_t)std::max(wt, PART_DOUBLES) * sizeof(double)};
+// what the launch plan (em_plan.hpp) reads of the handle
+EmFacts em_facts(const vpk_handle* h) {
+    return EmFacts{h->cu_share, h->em_max_workgroups, h->total_mem, h->em_lds_doubles, h->em_slice_ms, h->em_slice_nmax,
+                   h->em_started_cap, h->em_wait_cap, h->em_sess != nullptr, h->em_sess_slot_bytes, h->em_sess_slots,
+                   h->em_sess_wgs, h->em_sess_layout, h->em_unflushed, h->em_ws_bytes};
 }
 
-int em_slots(const vpk_handle* h, int batch, size_t slot_bytes, int per_cu) {
-    int slots = h->cu_share * per_cu;
-    if (h->em_max_workgroups > 0 && slots > h->em_max_workgroups) slots = h->em_max_workgroups;
-    if (slots > batch) slots = batch;
-    size_t budget = h->total_mem / 2;                // never claim more than half of HBM
-    while (slots > 1 && (size_t)slots * slot_bytes > budget) slots /= 2;
-    return slots < 1 ? 1 : slots;
-}
-
-int check_params(vpk_handle* h, const vpk_em_params* p, int n_init, bool has_init) {
-    if (!p) return vpk_fail(h, VPK_ERR_ARG, "params is null");
-    if (p->num_iter < 1 || p->num_iter > 100000) return vpk_fail(h, VPK_ERR_ARG, "num_iter out of range");
-    if (p->split_merge_freq < 1) return vpk_fail(h, VPK_ERR_ARG, "split_merge_freq < 1");
-    if (p->num_init_vp < 1 || p->num_init_vp > MAXM) return vpk_fail(h, VPK_ERR_LIMIT, "num_init_vp must be 1..64");
-    if (has_init && (n_init < 1 || n_init > MAXM)) return vpk_fail(h, VPK_ERR_LIMIT, "n_init must be 1..64");
-    return VPK_OK;
-}
-
-// list capacities: vpk_handle::em_wait_cap (images parked before they were started; a full list makes further ones
-// run on) and ::em_started_cap (suspended images: at most one per workgroup, vpk_em_set_workgroups <= CUs)
-constexpr size_t EM_SESS_HEAD = 256;    // counters
-
-struct SessView { int* ctr; int* busy; EmCarry* started[2]; EmCarry* waiting[2]; };
-SessView sess_view(vpk_handle* h) {
-    char* base = (char*)h->em_sess;
-    SessView v;
-    v.ctr = (int*)base;
-    v.busy = (int*)(base + EM_SESS_HEAD);
-    char* p = base + EM_SESS_HEAD + em_align((size_t)h->em_sess_slots * 4, 256);
-    const size_t sb = em_align(sizeof(EmCarry) * h->em_started_cap, 256), wb = em_align(sizeof(EmCarry) * h->em_wait_cap, 256);
-    v.started[0] = (EmCarry*)p; v.started[1] = (EmCarry*)(p + sb);
-    v.waiting[0] = (EmCarry*)(p + 2 * sb); v.waiting[1] = (EmCarry*)(p + 2 * sb + wb);
-    return v;
-}
-size_t sess_bytes(const vpk_handle* h, int slots) {
-    return EM_SESS_HEAD + em_align((size_t)slots * 4, 256) + 2 * em_align(sizeof(EmCarry) * h->em_started_cap, 256) +
-           2 * em_align(sizeof(EmCarry) * h->em_wait_cap, 256);
-}
-// the previous launch's output lists become this launch's input lists
+// The previous launch's output lists become this launch's input lists.  List capacities: vpk_handle::em_wait_cap (images
+// parked before they were started; a full list makes further ones run on) and ::em_started_cap (suspended images: at most
+// one per workgroup, vpk_em_set_workgroups <= CUs)
 EmSliceArgs sess_next(vpk_handle* h, double slice_ms) {
-    SessView v = sess_view(h);
-    hipLaunchKernelGGL(em_rotate_kernel, dim3(1), dim3(1), 0, h->stream, v.ctr, h->em_wait_cap, h->em_started_cap);
-    h->em_sess_in ^= 1;
+    const EmSessLayout v = em_sess_layout(h->em_sess_slots, h->em_started_cap, h->em_wait_cap, sizeof(EmCarry));
+    char* base = (char*)h->em_sess;
     EmSliceArgs ss;
+    ss.ctr = (int*)(base + v.head);
+    hipLaunchKernelGGL(em_rotate_kernel, dim3(1), dim3(1), 0, h->stream, ss.ctr, h->em_wait_cap, h->em_started_cap);
+    h->em_sess_in ^= 1;
     ss.enabled = 1;
-    ss.budget_ticks = slice_ms > 0 ? (long long)(slice_ms * 1e-3 / (CLOCK_US * 1e-6)) : 0;
-    if (slice_ms > 0 && ss.budget_ticks < 1) ss.budget_ticks = 1;
-    ss.ctr = v.ctr;
-    ss.in_started = v.started[h->em_sess_in]; ss.out_started = v.started[h->em_sess_in ^ 1];
-    ss.in_waiting = v.waiting[h->em_sess_in]; ss.out_waiting = v.waiting[h->em_sess_in ^ 1];
+    ss.budget_ticks = em_slice_ticks(slice_ms);
+    ss.in_started = (EmCarry*)(base + v.started[h->em_sess_in]); ss.out_started = (EmCarry*)(base + v.started[h->em_sess_in ^ 1]);
+    ss.in_waiting = (EmCarry*)(base + v.waiting[h->em_sess_in]); ss.out_waiting = (EmCarry*)(base + v.waiting[h->em_sess_in ^ 1]);
     ss.cap_started = h->em_started_cap; ss.cap_waiting = h->em_wait_cap;
-    ss.busy = v.busy; ss.nslots = h->em_sess_slots;
+    ss.busy = (int*)(base + v.busy); ss.nslots = h->em_sess_slots;
     return ss;
 }
 
@@ -501,15 +437,6 @@ EmLayout small_layout(int n, int m) {
     return em_layout(n, (int)em_align((size_t)(m > 0 ? m : 1), 8), EM_WAVES, true, false);
 }
 
-}  // namespace
-
-// em_mode for the other units that launch the smoother (vpk_emstep.hip)
-vpk_em_lds vpk_em_lds_mode(const vpk_handle* h) {
-    const EmMode m = em_mode(h);
-    return vpk_em_lds{m.wt_doubles, m.lds_bytes, EM_LDS_BYTES_BIG};
-}
-
-namespace {
 // vpk_math_probe: the elementary functions exactly as this translation unit's kernels get them (same compiler flags, same
 // ocml entry points as em_device.hpp's calls), one argument per thread.
 __global__ void math_probe_kernel(int fn, long long n, const double* __restrict__ x, double* __restrict__ y) {
@@ -572,10 +499,7 @@ int vpk_em_set_workgroups(vpk_handle* h, int max_workgroups) {
 
 size_t vpk_em_workspace_bytes(const vpk_handle* h, int batch, int n_max, const vpk_em_params* p, int n_init) {
     if (!h || !p || batch < 1) return 0;
-    int mcap = em_mcap(p->num_init_vp, n_init, n_init > 0, p->do_split != 0, p->num_iter, p->split_merge_freq, MAXM);
-    EmLayout L = em_layout(n_max, mcap, EM_WAVES, p->use_weights != 0, p->do_split != 0);
-    size_t slot = L.total_doubles * sizeof(double);
-    return (size_t)em_slots(h, batch, slot, em_mode(h).per_cu) * slot;
+    return em_plan_slots(em_facts(h), batch, n_max, *p, n_init, n_init > 0, false).ws_bytes();
 }
 
 int vpk_em_batch(vpk_handle* h, int batch, const int64_t* offsets, double* l, const double* lp,
@@ -585,98 +509,58 @@ int vpk_em_batch(vpk_handle* h, int batch, const int64_t* offsets, double* l, co
                  int32_t* iterations_out, int32_t* status_out, uint32_t* flags_out,
                  double* metric_out, double* trace_out) {
     if (!h) return VPK_ERR_ARG;
-    if (batch < 1 || !offsets || !l || !lp || !cnn || !sphere || !vp_out || !sigma_out || !counts_out ||
-        !counts_w_out || !num_vp_out || !assoc_out || !iterations_out || !status_out || !flags_out)
-        return vpk_fail(h, VPK_ERR_ARG, "vpk_em_batch: null buffer or batch < 1");
-    if (sphere_size < GRIDN || max_vp < 1) return vpk_fail(h, VPK_ERR_ARG, "vpk_em_batch: bad sphere_size/max_vp");
-    int rc = check_params(h, p, n_init, init_vp != nullptr);
-    if (rc) return rc;
+    const bool buffers = l && lp && cnn && sphere && vp_out && sigma_out && counts_out && counts_w_out && num_vp_out &&
+                         assoc_out && iterations_out && status_out && flags_out;
+    const EmPlan pl = em_plan(em_facts(h), batch, offsets, buffers, sphere_size, max_vp, p, n_init, init_vp != nullptr);
+    if (pl.rule) {
+        static const char* const what[] = {
+            nullptr,
+            "vpk_em_batch: null buffer or batch < 1",                                 // EM_PLAN_NULL
+            "vpk_em_batch: bad sphere_size/max_vp",                                   // EM_PLAN_SPHERE
+            "params is null",                                                         // EM_PLAN_PARAMS
+            "num_iter out of range",                                                  // EM_PLAN_NUM_ITER
+            "split_merge_freq < 1",                                                   // EM_PLAN_FREQ
+            "num_init_vp must be 1..64",                                              // EM_PLAN_NUM_INIT
+            "n_init must be 1..64",                                                   // EM_PLAN_N_INIT
+            "vpk_em_batch: offsets not monotone",                                     // EM_PLAN_OFFSETS
+            "vpk_em_batch: more than 46000 lines in one image",                       // EM_PLAN_LINES
+            "vpk_em_batch: time-sliced slots exceed half of the device memory",       // EM_PLAN_SLICE_MEM
+            "vpk_em_batch: the slot layout changed (more lines than vpk_em_set_time_slice was told, or other parameters) "
+            "while images are parked: vpk_em_flush first",                            // EM_PLAN_SESS_CHANGED
+            "vpk_em_batch: workspace would move while images are parked: vpk_em_flush first"};   // EM_PLAN_WS_MOVES
+        static_assert(sizeof(what) / sizeof(what[0]) == EM_PLAN_WS_MOVES + 1, "one text per rule");
+        return vpk_fail(h, em_rule_code(pl.rule), what[pl.rule]);
+    }
     VPK_HIP(h, hipSetDevice(h->device));
-    { int rc0 = em_prepare(h); if (rc0) return rc0; }
-    long long nmax = 0;
-    for (int b = 0; b < batch; ++b) {
-        long long n = offsets[b + 1] - offsets[b];
-        if (n < 0) return vpk_fail(h, VPK_ERR_ARG, "vpk_em_batch: offsets not monotone");
-        nmax = std::max(nmax, n);
+    if (int rc = em_prepare(h)) return rc;
+    if (!pl.sliced && h->em_unflushed) { if (int rc = em_flush(h)) return rc; }
+    if (pl.new_session) {
+        const size_t need = em_sess_layout(pl.slots, h->em_started_cap, h->em_wait_cap, sizeof(EmCarry)).total;
+        if (int rc = vpk_reserve(h, &h->em_sess, &h->em_sess_bytes, need, "hipMalloc(EM session)")) return rc;
+        VPK_HIP(h, hipMemsetAsync(h->em_sess, 0, need, h->stream));
+        h->em_sess_slot_bytes = pl.slot_bytes; h->em_sess_slots = pl.slots; h->em_sess_wgs = pl.wgs;
+        h->em_sess_layout = pl.L; h->em_sess_in = 0;
+        h->em_sess_wt_doubles = pl.mode.wt_doubles; h->em_sess_lds = pl.mode.lds_bytes;
     }
-    if (nmax > 46000) return vpk_fail(h, VPK_ERR_LIMIT, "vpk_em_batch: more than 46000 lines in one image");
-    const bool has_init = init_vp != nullptr;
-    const bool sliced = h->em_slice_ms > 0.0;
-    if (!sliced && h->em_unflushed) { rc = em_flush(h); if (rc) return rc; }
-    if (sliced && (long long)h->em_slice_nmax > nmax) nmax = h->em_slice_nmax;
-    int mcap = em_mcap(p->num_init_vp, n_init, has_init, p->do_split != 0, p->num_iter, p->split_merge_freq, MAXM);
-    EmLayout L = em_layout((int)nmax, mcap, EM_WAVES, p->use_weights != 0, p->do_split != 0);
-    const size_t slot_bytes = L.total_doubles * sizeof(double);
-    const EmMode mode = em_mode(h);
-    int slots = em_slots(h, batch, slot_bytes, mode.per_cu);
-    int wgs = slots;
-    if (sliced) {
-        // the workgroups of a sliced launch also resume what earlier launches parked, so their number does not
-        // follow the batch; slots outlive the launch: running (<= wgs) + parked and not yet resumed (<= wgs)
-        wgs = h->cu_share * mode.per_cu;
-        if (h->em_max_workgroups > 0 && wgs > h->em_max_workgroups) wgs = h->em_max_workgroups;
-        slots = 2 * wgs + 8;
-        if ((size_t)slots * slot_bytes > h->total_mem / 2)
-            return vpk_fail(h, VPK_ERR_LIMIT, "vpk_em_batch: time-sliced slots exceed half of the device memory");
-        const bool same = h->em_sess && h->em_sess_slot_bytes == slot_bytes && h->em_sess_slots == slots &&
-                          h->em_sess_wgs == wgs && memcmp(&h->em_sess_layout, &L, sizeof(L)) == 0;
-        if (!same) {
-            if (h->em_unflushed)
-                return vpk_fail(h, VPK_ERR_STATE, "vpk_em_batch: the slot layout changed (more lines than "
-                                "vpk_em_set_time_slice was told, or other parameters) while images are parked: vpk_em_flush first");
-            const size_t need = sess_bytes(h, slots);
-            rc = vpk_reserve(h, &h->em_sess, &h->em_sess_bytes, need, "hipMalloc(EM session)");
-            if (rc) return rc;
-            VPK_HIP(h, hipMemsetAsync(h->em_sess, 0, need, h->stream));
-            h->em_sess_slot_bytes = slot_bytes; h->em_sess_slots = slots; h->em_sess_wgs = wgs;
-            h->em_sess_layout = L; h->em_sess_in = 0;
-            h->em_sess_wt_doubles = mode.wt_doubles; h->em_sess_lds = mode.lds_bytes;
-        }
-    }
-    if (h->em_unflushed && (size_t)slots * slot_bytes > h->em_ws_bytes)
-        return vpk_fail(h, VPK_ERR_STATE, "vpk_em_batch: workspace would move while images are parked: vpk_em_flush first");
-    rc = vpk_reserve(h, &h->em_ws, &h->em_ws_bytes, (size_t)slots * slot_bytes, "hipMalloc(EM workspace)");
-    if (rc) return rc;
-    // header: offsets (B+1 i64) | order (B i32) | queue counter
-    const size_t off_bytes = em_align((size_t)(batch + 1) * 8, 256);
-    const size_t ord_bytes = em_align((size_t)batch * 4, 256);
-    rc = vpk_reserve(h, &h->em_hdr, &h->em_hdr_bytes, off_bytes + ord_bytes + 256, "hipMalloc(EM header)");
-    if (rc) return rc;
-    // The device header is rewritten by a stream-ordered copy (after the previous batch's kernel), so only
-    // the pinned staging buffer needs care: take the next ring slot and wait for the copy that last used it.
-    const int ring = h->em_hdr_next;
-    h->em_hdr_next = (ring + 1) % vpk_handle::VPK_HDR_RING;
-    if (!h->em_hdr_ev[ring]) VPK_HIP(h, hipEventCreateWithFlags(&h->em_hdr_ev[ring], hipEventDisableTiming));
-    if (h->em_hdr_ev_valid[ring]) VPK_HIP(h, hipEventSynchronize(h->em_hdr_ev[ring]));
-    if (h->em_hdr_host_bytes[ring] < off_bytes + ord_bytes) {
-        if (h->em_hdr_host[ring]) VPK_HIP(h, hipHostFree(h->em_hdr_host[ring]));
-        h->em_hdr_host[ring] = nullptr;
-        h->em_hdr_host_bytes[ring] = 0;
-        VPK_HIP(h, hipHostMalloc(&h->em_hdr_host[ring], (off_bytes + ord_bytes) * 2, hipHostMallocDefault));
-        h->em_hdr_host_bytes[ring] = (off_bytes + ord_bytes) * 2;
-    }
-    long long* st_off = (long long*)h->em_hdr_host[ring];
-    int* order = (int*)((char*)h->em_hdr_host[ring] + off_bytes);
-    for (int b = 0; b <= batch; ++b) st_off[b] = offsets[b];
-    std::iota(order, order + batch, 0);
-    std::stable_sort(order, order + batch, [&](int x, int y) {
-        return (offsets[x + 1] - offsets[x]) > (offsets[y + 1] - offsets[y]);   // largest image first
-    });
-    char* hdr = (char*)h->em_hdr;
-    VPK_HIP(h, hipMemcpyAsync(hdr, h->em_hdr_host[ring], off_bytes + ord_bytes, hipMemcpyHostToDevice, h->stream));
-    VPK_HIP(h, hipEventRecord(h->em_hdr_ev[ring], h->stream));
-    h->em_hdr_ev_valid[ring] = true;
-    VPK_HIP(h, hipMemsetAsync(hdr + off_bytes + ord_bytes, 0, 256, h->stream));
+    if (int rc = vpk_reserve(h, &h->em_ws, &h->em_ws_bytes, pl.ws_bytes(), "hipMalloc(EM workspace)")) return rc;
+    // header: offsets | order, filled in the pinned staging; the queue counter behind them is zeroed on the device
+    void* host;
+    if (int rc = vpk_stage_begin(h, h->em_hdr, pl.staged_bytes(), &host)) return rc;
+    memcpy(host, offsets, (size_t)(batch + 1) * sizeof(int64_t));
+    em_order(batch, offsets, (int*)((char*)host + pl.off_bytes));
+    if (int rc = vpk_stage_commit(h, h->em_hdr, pl.staged_bytes(), "hipMalloc(EM header)", 256)) return rc;
+    char* hdr = (char*)h->em_hdr.dev;
+    VPK_HIP(h, hipMemsetAsync(hdr + pl.staged_bytes(), 0, 256, h->stream));
 
     EmBatchArgs a;
     a.B = batch;
     a.offsets = (const long long*)hdr;
-    a.order = (const int*)(hdr + off_bytes);
-    a.queue = (int*)(hdr + off_bytes + ord_bytes);
+    a.order = (const int*)(hdr + pl.off_bytes);
+    a.queue = (int*)(hdr + pl.staged_bytes());
     a.l = l; a.lp = lp; a.cnn = cnn; a.sphere = sphere; a.ssize = sphere_size;
     a.init_vp = init_vp; a.n_init = n_init;
     a.prm = *p;
-    a.L = L;
+    a.L = pl.L;
     a.scratch = (double*)h->em_ws;
     a.max_vp = max_vp;
     a.vp_out = vp_out; a.sigma_out = sigma_out; a.counts_out = counts_out; a.counts_w_out = counts_w_out;
@@ -687,14 +571,14 @@ int vpk_em_batch(vpk_handle* h, int batch, const int64_t* offsets, double* l, co
         a.dist = h->em_dist;
         h->em_dist_set = false;
     }
-    a.wt_doubles = mode.wt_doubles;
+    a.wt_doubles = pl.mode.wt_doubles;
     a.smoother = h->em_smoother;
     EmSliceArgs ss = {};
-    if (sliced) {
+    if (pl.sliced) {
         ss = sess_next(h, h->em_slice_ms);
         h->em_unflushed = true;
     }
-    return em_launch(h, wgs, mode.lds_bytes, a, ss);
+    return em_launch(h, pl.wgs, pl.mode.lds_bytes, a, ss);
 }
 
 int vpk_em_set_distribution_out(vpk_handle* h, const vpk_em_dist_out* d) {
@@ -760,7 +644,7 @@ int vpk_weight_matrix(vpk_handle* h, int n, int m, const double* p_vl, const dou
     const EmLayout L = small_layout(n, m);
     if (int rc = hook_begin(h, L.total_doubles * 8)) return rc;
     // the batch kernel's LDS budget, so that this entry point takes the same smoother an image of this size takes there
-    const EmMode mode = em_mode(h);
+    const EmMode mode = em_mode(h->em_lds_doubles);
     return hook_launch(h, weight_matrix_kernel, mode.lds_bytes, n, m, p_vl, lweight, lsim, bias, L, (double*)h->small_ws,
                        w_out, h->em_smoother, mode.wt_doubles);
 }
@@ -773,7 +657,7 @@ int vpk_estep_smooth(vpk_handle* h, int n, int m, const double* lp, const float*
     const EmLayout L = small_layout(n, m);
     if (int rc = hook_begin(h, L.total_doubles * 8)) return rc;
     // the batch kernel's LDS budget (as vpk_weight_matrix): the E-step plans the panel and the smoother takes it as they do there
-    const EmMode mode = em_mode(h);
+    const EmMode mode = em_mode(h->em_lds_doubles);
     return hook_launch(h, estep_smooth_kernel, mode.lds_bytes, n, m, lp, cnn, v, s, lweight, lsim, bias, L,
                        (double*)h->small_ws, p_vl_out, w_out, (int*)info_out, h->em_smoother, mode.wt_doubles);
 }

@@ -3,15 +3,14 @@
 // emstep_device.hpp's loop over the workgroup's images.  Compiled with -ffp-contract=off like the EM unit.
 #include "emstep_device.hpp"
 #include "batch_args.hpp"
+#include "em_plan.hpp"
 #include "vpk_internal.hpp"
 
 using namespace vpk;
 
 namespace {
 
-constexpr int EMSTEP_THREADS = 512;                    // the EM workgroup's shape: the phase functions are tuned for 8 waves
-constexpr int EMSTEP_WAVES = EMSTEP_THREADS / 64;
-constexpr size_t EMSTEP_LDS_BYTES = SH_BYTES + WT_DOUBLES * sizeof(double);   // [Shared | panel], as the single-image M-step
+constexpr int EMSTEP_THREADS = EM_THREADS, EMSTEP_WAVES = EM_WAVES;   // the EM workgroup's shape: the phase functions are tuned for 8 waves
 constexpr long long EMSTEP_NMAX = 32768;
 
 __global__ __launch_bounds__(EMSTEP_THREADS) void emstep_kernel(EmstepArgs a) { emstep_run(a); }
@@ -40,7 +39,7 @@ int launch(vpk_handle* h, EmstepArgs& a, const std::vector<EmstepImage>& img, lo
     while (grid > 1 && (size_t)grid * stride > budget) grid /= 2;
     if (!h->emstep_ready) {
         VPK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(emstep_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)vpk_em_lds_mode(h).lds_bytes_max));
+                                       (int)EM_LDS_BYTES_BIG));
         h->emstep_ready = true;
     }
     int rc = vpk_reserve(h, &h->emstep_ws, &h->emstep_ws_bytes, (size_t)grid * stride, "hipMalloc(emstep workspace)");
@@ -75,8 +74,8 @@ int vpk_weight_matrix_batch(vpk_handle* h, int batch, const int64_t* line_offset
                                        (const long long*)lsim_offsets, EMSTEP_WEIGHTS, EMSTEP_WAVES, img);
     if (img.empty()) return VPK_OK;
     if (!p_vl || !lweight || !lsim || !w_out) return vpk_fail(h, VPK_ERR_ARG, "vpk_weight_matrix_batch: null buffer");
-    // the batch kernel's LDS budget, so that an image takes the smoother it takes there and in vpk_weight_matrix
-    const vpk_em_lds mode = vpk_em_lds_mode(h);
+    // the batch kernel's LDS budget (em_plan.hpp), so that an image takes the smoother it takes there and in vpk_weight_matrix
+    const EmMode mode = em_mode(h->em_lds_doubles);
     EmstepArgs a = {};
     a.op = EMSTEP_WEIGHTS;
     a.count = (int)img.size();
@@ -111,7 +110,7 @@ int vpk_mstep_batch(vpk_handle* h, int batch, const int64_t* line_offsets, const
     a.max_stdd = max_stdd; a.s_thresh = s_thresh;
     a.vp_out = vp_out; a.s_out = s_out; a.err_out = err_out; a.max_err_out = max_err_out;
     a.removed_out = (int*)removed_out; a.valid_out = (int*)valid_out;
-    return launch(h, a, img, slot, 2, EMSTEP_LDS_BYTES, "vpk_mstep_batch: records");
+    return launch(h, a, img, slot, 2, EM_LDS_BYTES, "vpk_mstep_batch: records");
 }
 
 int vpk_init_vps_batch(vpk_handle* h, int batch, const float* cnn, const uint8_t* sphere, int sphere_size, int num_max,
@@ -127,7 +126,7 @@ int vpk_init_vps_batch(vpk_handle* h, int batch, const float* cnn, const uint8_t
     a.wt_doubles = WT_DOUBLES;
     a.cnn = cnn; a.sphere = sphere; a.ssize = sphere_size; a.num_max = num_max;
     a.v0_out = v0_out; a.m0_out = (int*)m0_out; a.weights_out = weights_out;
-    return launch(h, a, std::vector<EmstepImage>(), 0, 2, EMSTEP_LDS_BYTES, "vpk_init_vps_batch");
+    return launch(h, a, std::vector<EmstepImage>(), 0, 2, EM_LDS_BYTES, "vpk_init_vps_batch");
 }
 
 }  // extern "C"

@@ -13,14 +13,16 @@
 struct vpk_cnn_state;   // vpk_cnn.hip
 struct vpk_train_state; // vpk_train.hip
 
-// a device header uploaded through pinned staging: the staging is reused once the event of the previous upload has fired
+// a device header uploaded through pinned staging.  The device buffer is one, rewritten in stream order; the staging is a ring
+// of `depth` pinned buffers, each reused once the event of the upload that last left it has fired, so a caller waits only for
+// the copy issued `depth` calls ago (vpk_stage_begin / vpk_stage_commit)
 struct vpk_staged {
-    void* host = nullptr;
-    size_t host_bytes = 0;
+    static constexpr int MAX_RING = 4;
+    int depth = 1;
+    int cur = 0;                 // the ring slot of the next upload
+    struct { void* host; size_t bytes; hipEvent_t ev; bool ev_valid; } ring[MAX_RING] = {};
     void* dev = nullptr;
     size_t dev_bytes = 0;
-    hipEvent_t ev = nullptr;
-    bool ev_valid = false;
 };
 
 struct vpk_handle {
@@ -44,16 +46,7 @@ struct vpk_handle {
     // EM workspace (grown on demand, never shrunk)
     void* em_ws = nullptr;
     size_t em_ws_bytes = 0;
-    void* em_hdr = nullptr;   // offsets + order + queue counter
-    size_t em_hdr_bytes = 0;
-    // pinned staging for the header: a ring, so that the call does not have to wait for the previous
-    // batch on this handle (only for the H2D copy issued VPK_HDR_RING calls ago)
-    static constexpr int VPK_HDR_RING = 4;
-    void* em_hdr_host[VPK_HDR_RING] = {};
-    size_t em_hdr_host_bytes[VPK_HDR_RING] = {};
-    hipEvent_t em_hdr_ev[VPK_HDR_RING] = {};
-    bool em_hdr_ev_valid[VPK_HDR_RING] = {};
-    int em_hdr_next = 0;
+    vpk_staged em_hdr = {vpk_staged::MAX_RING};   // offsets + order + queue counter; vpk_em_batch never waits for the previous batch
     void* small_ws = nullptr; // fine-grained entry points
     size_t small_ws_bytes = 0;
     bool raster_ready = false;
@@ -82,18 +75,12 @@ struct vpk_handle {
     vpk::EmLayout em_sess_layout = {};
     hipEvent_t step_event = nullptr; // vpk_pipeline_step: orders the EM stream behind the CNN stream
     vpk_cnn_state* cnn = nullptr;
-    // vpk_lsd_detect_batch (vpk_lsd_gpu.hip): workspace (grown on demand), header (descriptors + Gaussian weights) and its
-    // pinned staging, reused once the event of the previous call's upload has fired
+    // vpk_lsd_detect_batch (vpk_lsd_gpu.hip): workspace (grown on demand), header (descriptors + Gaussian weights)
     size_t lsd_ws_limit = 0;         // vpk_lsd_set_workspace_limit (0 = the default, 4 GiB)
     int lsd_math = 0;                // vpk_lsd_set_math (test hook): 0 = device libm, 1 = portable math
     void* lsd_ws = nullptr;
     size_t lsd_ws_bytes = 0;
-    void* lsd_hdr = nullptr;
-    size_t lsd_hdr_bytes = 0;
-    void* lsd_host = nullptr;
-    size_t lsd_host_bytes = 0;
-    hipEvent_t lsd_ev = nullptr;
-    bool lsd_ev_valid = false;
+    vpk_staged lsd_hdr;
     // vpk_image_prepare_batch / vpk_lsd_rows_to_lines (vpk_frontend.hip): headers (descriptors + Lanczos weights) and the
     // horizontal pass's uint8 intermediate (grown on demand)
     vpk_staged fe_prep, fe_rows;
@@ -115,17 +102,16 @@ struct vpk_handle {
     vpk_train_state* train = nullptr; // vpk_train_create (vpk_train.hip): the dense head's master weights, momentum, activations
 };
 
-// the LDS budget vpk_em_batch launches with under the handle's vpk_em_set_lds_panel setting (vpk_em.hip: em_mode): the
-// panel the phases plan with, the launch's dynamic LDS, and the most any setting asks for
-struct vpk_em_lds { int wt_doubles; size_t lds_bytes; size_t lds_bytes_max; };
-vpk_em_lds vpk_em_lds_mode(const vpk_handle* h);
-
 int vpk_fail(vpk_handle* h, int code, const char* what);
 int vpk_fail_hip(vpk_handle* h, hipError_t e, const char* what);
 int vpk_reserve(vpk_handle* h, void** p, size_t* have, size_t want, const char* what);
 void vpk_cnn_free(vpk_handle* h);
 void vpk_train_free(vpk_handle* h);
-// copies `bytes` of `src` to s.dev through s's pinned staging, asynchronously on the handle's stream
+// An upload to s.dev through s's pinned staging, asynchronously on the handle's stream.  begin: the next ring slot, free of
+// its last upload and at least `bytes` large, as *host; the caller fills it.  commit: s.dev reserved for bytes + tail (the tail
+// is not written), the copy of `bytes`, the slot's event.  vpk_stage_upload: begin, memcpy of src, commit.
+int vpk_stage_begin(vpk_handle* h, vpk_staged& s, size_t bytes, void** host);
+int vpk_stage_commit(vpk_handle* h, vpk_staged& s, size_t bytes, const char* what, size_t tail = 0);
 int vpk_stage_upload(vpk_handle* h, vpk_staged& s, const void* src, size_t bytes, const char* what);
 
 #define VPK_HIP(h, call)                                         \

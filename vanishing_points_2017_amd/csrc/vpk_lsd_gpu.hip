@@ -249,27 +249,15 @@ int vpk_lsd_detect_batch(vpk_handle* h, int batch, const int32_t* dims, const in
     // header: descriptors, then the Gaussian weights of every output coordinate 0..max_c-1
     const size_t desc_bytes = (size_t)align256((long long)batch * sizeof(ImgDesc));
     const size_t hdr_bytes = desc_bytes + (size_t)plan.max_c * q.taps * sizeof(double);
-    if (h->lsd_ev_valid) VPK_HIP(h, hipEventSynchronize(h->lsd_ev));  // the previous call's upload has left the staging
-    if (h->lsd_host_bytes < hdr_bytes) {
-        if (h->lsd_host) VPK_HIP(h, hipHostFree(h->lsd_host));
-        h->lsd_host = nullptr;
-        h->lsd_host_bytes = 0;
-        VPK_HIP(h, hipHostMalloc(&h->lsd_host, hdr_bytes, hipHostMallocDefault));
-        h->lsd_host_bytes = hdr_bytes;
-    }
-    if (!h->lsd_ev) VPK_HIP(h, hipEventCreateWithFlags(&h->lsd_ev, hipEventDisableTiming));
-    unsigned char* stage = (unsigned char*)h->lsd_host;
+    void* host;
+    if (int rc = vpk_stage_begin(h, h->lsd_hdr, hdr_bytes, &host)) return rc;
+    unsigned char* stage = (unsigned char*)host;
     memcpy(stage, plan.desc.data(), (size_t)batch * sizeof(ImgDesc));
     if (plan.max_c) gaussian_weights((double*)(stage + desc_bytes), plan.max_c, q);
-    int rc = vpk_reserve(h, &h->lsd_hdr, &h->lsd_hdr_bytes, hdr_bytes, "vpk_lsd_detect_batch: header");
-    if (rc) return rc;
-    rc = vpk_reserve(h, &h->lsd_ws, &h->lsd_ws_bytes, plan.ws_bytes, "vpk_lsd_detect_batch: workspace");
-    if (rc) return rc;
-    VPK_HIP(h, hipMemcpyAsync(h->lsd_hdr, stage, hdr_bytes, hipMemcpyHostToDevice, h->stream));
-    VPK_HIP(h, hipEventRecord(h->lsd_ev, h->stream));
-    h->lsd_ev_valid = true;
-    const ImgDesc* ddesc = (const ImgDesc*)h->lsd_hdr;
-    const double* wts = (const double*)((unsigned char*)h->lsd_hdr + desc_bytes);
+    if (int rc = vpk_stage_commit(h, h->lsd_hdr, hdr_bytes, "vpk_lsd_detect_batch: header")) return rc;
+    if (int rc = vpk_reserve(h, &h->lsd_ws, &h->lsd_ws_bytes, plan.ws_bytes, "vpk_lsd_detect_batch: workspace")) return rc;
+    const ImgDesc* ddesc = (const ImgDesc*)h->lsd_hdr.dev;
+    const double* wts = (const double*)((unsigned char*)h->lsd_hdr.dev + desc_bytes);
     unsigned char* ws = (unsigned char*)h->lsd_ws;
     Meta* meta = (Meta*)ws;
     for (size_t c = 0; c + 1 < plan.starts.size(); ++c) {

@@ -13,7 +13,6 @@ using namespace vpk;
 namespace {
 
 constexpr int VPSET_THREADS = 512;                     // the EM workgroup's shape: the phase functions are tuned for 8 waves
-constexpr size_t VPSET_LDS_BYTES = SH_BYTES + WT_DOUBLES * sizeof(double);   // [Shared | panel]: two workgroups per CU
 constexpr long long VPSET_NMAX = 32768;                // cluster2 indexes an n x n matrix with ints
 
 // one kernel per distance measure, as vpk_em.hip and vpk_estep.hip have them: no run-time branch in a pair loop
@@ -57,7 +56,7 @@ int launch(vpk_handle* h, int measure, int batch, const std::vector<int64_t>& hd
     if (!h->vpset_ready) {
         for (int m : {VPK_DIST_ANGLE, VPK_DIST_DOTPROD, VPK_DIST_AREA})
             VPK_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel_of(m)), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)VPSET_LDS_BYTES));
+                                           (int)EM_LDS_BYTES));
         h->vpset_ready = true;
     }
     int rc = vpk_reserve(h, &h->vpset_ws, &h->vpset_ws_bytes, (size_t)(ws_doubles > 0 ? ws_doubles : 32) * 8, "hipMalloc(vpset workspace)");
@@ -69,7 +68,7 @@ int launch(vpk_handle* h, int measure, int batch, const std::vector<int64_t>& hd
     a.line_off = d; a.vp_off = d + B1; a.mat_off = d + 2 * B1; a.ws_off = d + 3 * B1; a.active = d + 4 * B1;
     a.ws = (gdp)h->vpset_ws;
     a.wt_doubles = WT_DOUBLES;
-    hipLaunchKernelGGL(kernel_of(measure), dim3((unsigned)active), dim3(VPSET_THREADS), VPSET_LDS_BYTES, h->stream, a);
+    hipLaunchKernelGGL(kernel_of(measure), dim3((unsigned)active), dim3(VPSET_THREADS), EM_LDS_BYTES, h->stream, a);
     VPK_HIP(h, hipGetLastError());
     return VPK_OK;
 }
