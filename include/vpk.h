@@ -905,6 +905,66 @@ int vpk_train_step(vpk_handle* h, const float* X, const float* labels, int B, co
 /* The TEST phase of the same net (:289-424 without Dropout's mask and scale) on any B >= 1, in chunks of 32; changes no
  * weight.  labels may be NULL (then loss_out is not written); with labels, loss_out is required.  The loss is divided by B. */
 int vpk_train_eval(vpk_handle* h, const float* X, const float* labels, int B, float* loss_out, float* sigout_out);
+/* vpk_train_step that also writes dX_out [B x I fp32, required]: the gradient of the loss with respect to X (dA6 W6, with
+ * the weights the forward used).  The weights, the loss and sigout get the bits vpk_train_step gives them.  The fc6
+ * sweep's dX partials (row tiles x B x I floats) are allocated by the first such call and grown when B grows. */
+int vpk_train_step_dx(vpk_handle* h, const float* X, const float* labels, int B, const uint8_t* mask6, const uint8_t* mask7,
+                      unsigned long long seed, float* loss_out, float* sigout_out, float* dX_out);
+
+/* ---- fine-tuning the conv stack: train/train_val.prototxt:66-288 under train/solver.prototxt ---------------------------
+ * A stack is an input shape (C, H, W) and a chain of layers of three kinds.  Fields a kind does not name are ignored.
+ *   VPK_LAYER_CONV  out_channels, kernel, stride (>= 1), pad (>= 0), groups, relu.  Cross-correlation with OIHW weights
+ *                   [OC][C / groups][K][K] on contiguous channel groups, then the bias, then max(., 0) if relu != 0.
+ *                   Output side (in + 2 pad - K) / stride + 1.
+ *   VPK_LAYER_LRN   local_size (n, odd), alpha, beta, k.  ACROSS_CHANNELS: s_i = k + (alpha / n) sum x_j^2 over the
+ *                   channels |j - i| <= n / 2 that exist, in rising j; y_i = x_i s_i^-beta.
+ *   VPK_LAYER_POOL  kernel, stride.  MAX over the window [o stride, min(o stride + K, in)) with Caffe's ceil-mode output
+ *                   side ceil((in - K) / stride) + 1 (in >= K; less one if the last window would start past the plane).  The maximum is the first element in row-major scan order
+ *                   that is strictly greater than all before it; its flat index h W + w in the input plane is kept. */
+enum { VPK_LAYER_CONV = 0, VPK_LAYER_LRN = 1, VPK_LAYER_POOL = 2 };
+typedef struct vpk_stack_layer {
+    int32_t kind;
+    int32_t out_channels, kernel, stride, pad, groups, relu;
+    int32_t local_size;
+    float alpha, beta, k;
+} vpk_stack_layer;
+/* The net's own stack (conv1, norm1, pool1, conv2, norm2, pool2, conv3, conv4, conv5, pool5 on (1, 500, 500)): writes up to
+ * `capacity` layers and in_shape[3] (either may be NULL) and returns the number of layers, 10.  Needs no handle. */
+int vpk_convtrain_net_layers(vpk_stack_layer* layers_out, int capacity, int32_t in_shape[3]);
+/* One conv trainer per handle (a second create: VPK_ERR_STATE), beside the head trainer.  Shapes that do not chain are
+ * VPK_ERR_ARG before anything is allocated: a non-positive size or output side, groups that do not divide both channel
+ * counts, an even local_size, a pool larger than its plane, n_layers outside 1..32; an LRN on more than 512 channels:
+ * VPK_ERR_LIMIT.  Allocates the fp32 master weights and momentum of every CONV layer; the blobs of a step are allocated
+ * by the first forward of a batch size and kept.  vpk_destroy frees it. */
+int vpk_convtrain_create(vpk_handle* h, int C, int H, int W, const vpk_stack_layer* layers, int n_layers);
+int vpk_convtrain_destroy(vpk_handle* h);
+/* The solver's numbers (dropout_ratio is ignored); stepsize >= 1, else VPK_ERR_ARG. */
+int vpk_convtrain_set_params(vpk_handle* h, const vpk_train_params* p);
+/* blobs [host]: two fp32 blobs per CONV layer in stack order, weight then bias.  The rules of vpk_train_load and its kin. */
+int vpk_convtrain_load(vpk_handle* h, const void* const* blobs);
+int vpk_convtrain_store(vpk_handle* h, void* const* blobs_out);
+int vpk_convtrain_load_momentum(vpk_handle* h, const void* const* blobs);
+int vpk_convtrain_store_momentum(vpk_handle* h, void* const* blobs_out);
+int vpk_convtrain_set_iteration(vpk_handle* h, long long iteration);
+int vpk_convtrain_get_iteration(const vpk_handle* h, long long* iteration_out);
+/* The forward of the stack on X [device, B x C x H x W fp32], 1 <= B <= 32 (else VPK_ERR_LIMIT, nothing is launched).
+ * X is copied; every layer's output, every LRN's s and every pool's indices stay on the device until the next forward.
+ * top_out (may be NULL) receives the last blob, B x C' x H' x W'.  VPK_ERR_STATE before vpk_convtrain_load. */
+int vpk_convtrain_forward(vpk_handle* h, const float* X, int B, float* top_out);
+/* d_top [device]: dL / d(last blob) for the batch of the last forward (VPK_ERR_STATE without one; a backward consumes it).
+ * Back-propagates through every layer (ReLU by top > 0; pools by a gather over the windows that contain an element, in
+ * row-major window order; LRN dx_i = dy_i s_i^-beta - (2 alpha beta / n) x_i sum_j dy_j y_j / s_j; convolutions dW, db
+ * and, for every CONV layer but the first, dX), applies V <- mu V + lr_local (dW + decay_local W), W <- W - V to every
+ * CONV layer with vpk_train_step's rate arithmetic, and increments the iteration.  d_input_out (may be NULL): B x C x H x W,
+ * dL / dX; NULL skips the first layer's data gradient.  The weight gradient's reduction over (b, y, x) runs on the f32
+ * matrix cores in slabs whose sums are added in slab order inside the update: no float atomics, the same state and inputs
+ * give the same bits.  The gradient blob of every layer stays on the device until the next forward. */
+int vpk_convtrain_backward(vpk_handle* h, const float* d_top, float* d_input_out);
+/* Copies one kept blob of `layer`, dense, to out [device]: VPK_BLOB_OUTPUT fp32, VPK_BLOB_POOL_INDEX int32 (POOL layers),
+ * VPK_BLOB_GRADIENT fp32 (dL / d output, after a backward), VPK_BLOB_LRN_SCALE fp32 (LRN layers: s, Caffe's scale_ blob).
+ * A kind the layer does not have: VPK_ERR_ARG; a blob that does not exist yet: VPK_ERR_STATE. */
+enum { VPK_BLOB_OUTPUT = 0, VPK_BLOB_POOL_INDEX = 1, VPK_BLOB_GRADIENT = 2, VPK_BLOB_LRN_SCALE = 3 };
+int vpk_convtrain_read(vpk_handle* h, int layer, int kind, void* out);
 
 #ifdef __cplusplus
 }

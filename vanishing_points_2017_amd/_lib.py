@@ -67,6 +67,16 @@ class TrainParams(ctypes.Structure):
                 ("decay_mult_bias", ctypes.c_float), ("dropout_ratio", ctypes.c_float)]
 
 
+class StackLayer(ctypes.Structure):
+    """vpk_stack_layer (include/vpk.h): one layer of a conv stack.  kind: 0 CONV, 1 LRN, 2 POOL."""
+    _fields_ = [("kind", ctypes.c_int32), ("out_channels", ctypes.c_int32), ("kernel", ctypes.c_int32),
+                ("stride", ctypes.c_int32), ("pad", ctypes.c_int32), ("groups", ctypes.c_int32), ("relu", ctypes.c_int32),
+                ("local_size", ctypes.c_int32), ("alpha", ctypes.c_float), ("beta", ctypes.c_float), ("k", ctypes.c_float)]
+
+
+LAYER_CONV, LAYER_LRN, LAYER_POOL = 0, 1, 2             # include/vpk.h: VPK_LAYER_*
+BLOB_OUTPUT, BLOB_POOL_INDEX, BLOB_GRADIENT, BLOB_LRN_SCALE = 0, 1, 2, 3   # include/vpk.h: VPK_BLOB_*
+
 EXPORTS = [
     "vpk_create", "vpk_destroy", "vpk_set_stream", "vpk_get_stream", "vpk_synchronize", "vpk_last_error", "vpk_version",
     "vpk_em_default_params", "vpk_device_info", "vpk_em_set_workgroups", "vpk_em_set_smoother", "vpk_em_set_lds_panel", "vpk_em_set_distance_measure", "vpk_em_set_time_slice", "vpk_em_flush", "vpk_em_set_distribution_out", "vpk_cnn_load", "vpk_cnn_forward", "vpk_cnn_forward_tap",
@@ -90,7 +100,11 @@ EXPORTS = [
     "vpk_horizon_error_batch", "vpk_auc",
     "vpk_train_default_params", "vpk_train_create", "vpk_train_destroy", "vpk_train_set_params",
     "vpk_train_load", "vpk_train_store", "vpk_train_load_momentum", "vpk_train_store_momentum",
-    "vpk_train_set_iteration", "vpk_train_get_iteration", "vpk_train_step", "vpk_train_eval",
+    "vpk_train_set_iteration", "vpk_train_get_iteration", "vpk_train_step", "vpk_train_eval", "vpk_train_step_dx",
+    "vpk_convtrain_net_layers", "vpk_convtrain_create", "vpk_convtrain_destroy", "vpk_convtrain_set_params",
+    "vpk_convtrain_load", "vpk_convtrain_store", "vpk_convtrain_load_momentum", "vpk_convtrain_store_momentum",
+    "vpk_convtrain_set_iteration", "vpk_convtrain_get_iteration", "vpk_convtrain_forward", "vpk_convtrain_backward",
+    "vpk_convtrain_read",
 ]
 
 _lib = None
@@ -210,6 +224,18 @@ def load():
     lib.vpk_train_get_iteration.argtypes = [c_void, ctypes.POINTER(ctypes.c_longlong)]
     lib.vpk_train_step.argtypes = [c_void, c_void, c_void, ctypes.c_int, c_void, c_void, ctypes.c_ulonglong, c_void, c_void]
     lib.vpk_train_eval.argtypes = [c_void, c_void, c_void, ctypes.c_int, c_void, c_void]
+    lib.vpk_train_step_dx.argtypes = lib.vpk_train_step.argtypes + [c_void]
+    lib.vpk_convtrain_net_layers.argtypes = [ctypes.POINTER(StackLayer), ctypes.c_int, ctypes.POINTER(ctypes.c_int32)]
+    lib.vpk_convtrain_create.argtypes = [c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(StackLayer), ctypes.c_int]
+    lib.vpk_convtrain_destroy.argtypes = [c_void]
+    lib.vpk_convtrain_set_params.argtypes = [c_void, ctypes.POINTER(TrainParams)]
+    for fn in (lib.vpk_convtrain_load, lib.vpk_convtrain_store, lib.vpk_convtrain_load_momentum, lib.vpk_convtrain_store_momentum):
+        fn.argtypes = [c_void, ctypes.POINTER(c_void)]
+    lib.vpk_convtrain_set_iteration.argtypes = [c_void, ctypes.c_longlong]
+    lib.vpk_convtrain_get_iteration.argtypes = [c_void, ctypes.POINTER(ctypes.c_longlong)]
+    lib.vpk_convtrain_forward.argtypes = [c_void, c_void, ctypes.c_int, c_void]
+    lib.vpk_convtrain_backward.argtypes = [c_void, c_void, c_void]
+    lib.vpk_convtrain_read.argtypes = [c_void, ctypes.c_int, ctypes.c_int, c_void]
     _lib = lib
     return lib
 

@@ -28,6 +28,7 @@ UNITS = {
     "vpk_emstep.hip": ["-ffp-contract=off"],   # the bodies of the EM's fine-grained entry points for a batch (emstep_device.hpp)
     "vpk_cnn.hip": [],
     "vpk_train.hip": [],                       # the dense head's SGD step (train_device.hpp)
+    "vpk_convtrain.hip": [],                   # the conv stack's forward, backward and SGD step (convtrain_device.hpp)
     "vpk_raster.hip": ["-ffp-contract=off"],   # the curve samples must round like NumPy's separate ufunc calls
     "vpk_horizon.hip": ["-ffp-contract=off"],
     "vpk_detect.hip": ["-ffp-contract=off"],   # the pixel conversion rounds like NumPy's separate ufunc calls (detect_device.hpp)

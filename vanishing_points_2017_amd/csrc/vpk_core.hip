@@ -106,6 +106,7 @@ int vpk_destroy(vpk_handle* h) {
     (void)hipStreamSynchronize(h->stream);
     vpk_cnn_free(h);
     vpk_train_free(h);
+    vpk_convtrain_free(h);
     if (h->step_event) (void)hipEventDestroy(h->step_event);
     for (void* p : {h->em_ws, h->em_sess, h->small_ws, h->raster_hdr, h->lsd_ws, h->vpset_ws, h->emstep_ws, h->fe_ws})
         if (p) (void)hipFree(p);

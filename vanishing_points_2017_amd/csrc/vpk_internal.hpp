@@ -12,6 +12,7 @@
 
 struct vpk_cnn_state;   // vpk_cnn.hip
 struct vpk_train_state; // vpk_train.hip
+struct vpk_convtrain_state; // vpk_convtrain.hip
 
 // a device header uploaded through pinned staging.  The device buffer is one, rewritten in stream order; the staging is a ring
 // of `depth` pinned buffers, each reused once the event of the upload that last left it has fired, so a caller waits only for
@@ -100,6 +101,7 @@ struct vpk_handle {
     vpk_staged detect_hdr;           // vpk_to_pixels_batch (vpk_detect.hip): line offsets + image sizes
     vpk_staged score_hdr;            // vpk_horizon_error_batch (vpk_score.hip): image sizes
     vpk_train_state* train = nullptr; // vpk_train_create (vpk_train.hip): the dense head's master weights, momentum, activations
+    vpk_convtrain_state* convtrain = nullptr; // vpk_convtrain_create (vpk_convtrain.hip): the conv stack's weights, momentum, blobs
 };
 
 int vpk_fail(vpk_handle* h, int code, const char* what);
@@ -107,6 +109,7 @@ int vpk_fail_hip(vpk_handle* h, hipError_t e, const char* what);
 int vpk_reserve(vpk_handle* h, void** p, size_t* have, size_t want, const char* what);
 void vpk_cnn_free(vpk_handle* h);
 void vpk_train_free(vpk_handle* h);
+void vpk_convtrain_free(vpk_handle* h);
 // An upload to s.dev through s's pinned staging, asynchronously on the handle's stream.  begin: the next ring slot, free of
 // its last upload and at least `bytes` large, as *host; the caller fills it.  commit: s.dev reserved for bytes + tail (the tail
 // is not written), the copy of `bytes`, the slot's event.  vpk_stage_upload: begin, memcpy of src, commit.

@@ -250,6 +250,16 @@ __global__ void train_dx_reduce(const float* __restrict__ partial, int tiles, si
     dA[i] = act[i] > 0.f ? s * ((float)mask[i] * scale) : 0.f;
 }
 
+// dX[b][k] = sum over the row tiles, in tile order, as it is (vpk_train_step_dx: the gradient that leaves the head)
+__global__ void train_dx_sum(const float* __restrict__ partial, int tiles, size_t BK, float* __restrict__ dX) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= BK) return;
+    float s = 0.f;
+#pragma unroll 8
+    for (int t = 0; t < tiles; ++t) s += partial[(size_t)t * BK + i];
+    dX[i] = s;
+}
+
 // db[n] = sum_b dY[b][n] in batch order, and the bias's update (lr_mult 2, decay_mult 0 come in through lr and decay)
 __global__ void train_bias(float* __restrict__ bias, float* __restrict__ vb, const float* __restrict__ dY, int B, int N,
                            float lr, float decay, float mu) {
@@ -309,6 +319,8 @@ struct vpk_train_state {
     uint8_t *m6 = nullptr, *m7 = nullptr;
     float* partial = nullptr;         // the sweeps' dX partials: [row tile][B][K]
     float* fpartial = nullptr;        // the forward's slab sums: [slab][B][N]
+    float* xpartial = nullptr;        // fc6's dX partials [row tile][B][I]: vpk_train_step_dx only, allocated by its first call
+    size_t xpartial_bytes = 0;
     vpk_train_params p = {};
     long long iteration = 0;
     bool loaded = false;
@@ -403,7 +415,8 @@ void vpk_train_free(vpk_handle* h) {
         for (float* p : {s->W[l], s->V[l], s->b[l], s->vb[l]})
             if (p) (void)hipFree(p);
     for (void* p : {(void*)s->a6, (void*)s->d6, (void*)s->a7, (void*)s->d7, (void*)s->z, (void*)s->dz, (void*)s->sig,
-                    (void*)s->dA7, (void*)s->dA6, (void*)s->m6, (void*)s->m7, (void*)s->partial, (void*)s->fpartial})
+                    (void*)s->dA7, (void*)s->dA6, (void*)s->m6, (void*)s->m7, (void*)s->partial, (void*)s->fpartial,
+                    (void*)s->xpartial})
         if (p) (void)hipFree(p);
     delete s;
     h->train = nullptr;
@@ -554,17 +567,23 @@ int vpk_train_get_iteration(const vpk_handle* h, long long* iteration_out) {
     return VPK_OK;
 }
 
-int vpk_train_step(vpk_handle* h, const float* X, const float* labels, int B, const uint8_t* mask6, const uint8_t* mask7,
-                   unsigned long long seed, float* loss_out, float* sigout_out) {
+// the step; want_dx: vpk_train_step_dx, which also writes dX_out (the fc6 sweep's DX form and its partials)
+static int train_step(vpk_handle* h, const float* X, const float* labels, int B, const uint8_t* mask6, const uint8_t* mask7,
+                      unsigned long long seed, float* loss_out, float* sigout_out, bool want_dx, float* dX_out) {
     if (!h) return VPK_ERR_ARG;
     vpk_train_state* s = h->train;
     if (!s || !s->loaded) return vpk_fail(h, VPK_ERR_STATE, "vpk_train_step before vpk_train_create / vpk_train_load");
     if (B < 1 || B > TRAIN_MAX_B) return vpk_fail(h, VPK_ERR_LIMIT, "vpk_train_step: the batch must be 1..32");
-    if (!X || !labels || (mask6 == nullptr) != (mask7 == nullptr))
-        return vpk_fail(h, VPK_ERR_ARG, "vpk_train_step: X and labels are required, the masks come both or not at all");
+    if (!X || !labels || (mask6 == nullptr) != (mask7 == nullptr) || (want_dx && !dX_out))
+        return vpk_fail(h, VPK_ERR_ARG, "vpk_train_step: X, labels (and dX_out) are required, the masks come both or not at all");
     VPK_HIP(h, hipSetDevice(h->device));
     hipStream_t st = h->stream;
     const int I = s->dims[0], H6 = s->dims[1], H7 = s->dims[2], O = s->dims[3];
+    if (want_dx) {
+        const int rc = vpk_reserve(h, (void**)&s->xpartial, &s->xpartial_bytes, (size_t)sweep_tiles(H6, I) * B * I * 4,
+                                   "vpk_train_step_dx: fc6 dX partials");
+        if (rc) return rc;
+    }
     const vpk_train_params& p = s->p;
     if (mask6) {
         VPK_HIP(h, hipMemcpyAsync(s->m6, mask6, (size_t)B * H6, hipMemcpyDeviceToDevice, st));
@@ -591,12 +610,26 @@ int vpk_train_step(vpk_handle* h, const float* X, const float* labels, int B, co
     sweep_layer(st, s->W[1], s->V[1], s->dA7, s->d6, B, H7, H6, s->partial, lr_w, dec_w, p.momentum);
     train_bias<<<(H7 + 255) / 256, 256, 0, st>>>(s->b[1], s->vb[1], s->dA7, B, H7, lr_b, dec_b, p.momentum);
     train_dx_reduce<<<(unsigned)((bk6 + 255) / 256), 256, 0, st>>>(s->partial, sweep_tiles(H7, H6), bk6, s->m6, s->a6, scale, s->dA6);
-    // fc6: the conv stack below is frozen, so no dX
-    sweep_layer(st, s->W[0], s->V[0], s->dA6, X, B, H6, I, nullptr, lr_w, dec_w, p.momentum);
+    // fc6: no dX while the conv stack below is frozen (vpk_train_step); vpk_train_step_dx hands it to the caller
+    sweep_layer(st, s->W[0], s->V[0], s->dA6, X, B, H6, I, want_dx ? s->xpartial : nullptr, lr_w, dec_w, p.momentum);
+    if (want_dx) {
+        const size_t bi = (size_t)B * I;
+        train_dx_sum<<<(unsigned)((bi + 255) / 256), 256, 0, st>>>(s->xpartial, sweep_tiles(H6, I), bi, dX_out);
+    }
     train_bias<<<(H6 + 255) / 256, 256, 0, st>>>(s->b[0], s->vb[0], s->dA6, B, H6, lr_b, dec_b, p.momentum);
     VPK_HIP(h, hipGetLastError());
     s->iteration += 1;
     return VPK_OK;
+}
+
+int vpk_train_step(vpk_handle* h, const float* X, const float* labels, int B, const uint8_t* mask6, const uint8_t* mask7,
+                   unsigned long long seed, float* loss_out, float* sigout_out) {
+    return train_step(h, X, labels, B, mask6, mask7, seed, loss_out, sigout_out, false, nullptr);
+}
+
+int vpk_train_step_dx(vpk_handle* h, const float* X, const float* labels, int B, const uint8_t* mask6, const uint8_t* mask7,
+                      unsigned long long seed, float* loss_out, float* sigout_out, float* dX_out) {
+    return train_step(h, X, labels, B, mask6, mask7, seed, loss_out, sigout_out, true, dX_out);
 }
 
 int vpk_train_eval(vpk_handle* h, const float* X, const float* labels, int B, float* loss_out, float* sigout_out) {
