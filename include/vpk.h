@@ -966,6 +966,36 @@ int vpk_convtrain_backward(vpk_handle* h, const float* d_top, float* d_input_out
 enum { VPK_BLOB_OUTPUT = 0, VPK_BLOB_POOL_INDEX = 1, VPK_BLOB_GRADIENT = 2, VPK_BLOB_LRN_SCALE = 3 };
 int vpk_convtrain_read(vpk_handle* h, int layer, int kind, void* out);
 
+/* ---- the training set on the device: train/train_val.prototxt:1-62 without LMDB ------------------------------------------
+ * stands in for: the two Data layers of train_val.prototxt:1-62 (TRAIN batch 5, TEST batch 100, mean_file).  A stored
+ * example is an image's homogeneous lines and its ground-truth VPs; a batch is gathered from the store, mapped by one affine
+ * transform of the image plane per example, and handed to vpk_sphere_raster (l_out, out_offsets) and to the loss
+ * (labels_out).  The rules are csrc/trainset_device.hpp's, fp64, every operation rounded on its own:
+ *   H = [[h00, h01, h02], [h10, h11, h12], [0, 0, 1]];  det = h00 h11 - h01 h10
+ *   line  mx = h11 lx - h10 ly;  my = h00 ly - h01 lx;  mz = det lz - (h02 mx + h12 my)       (det H^-T l)
+ *   VP    wx = (h00 vx + h01 vy) + h02 vz;  wy = (h10 vx + h11 vy) + h12 vz;  wz = vz            (H v)
+ *   cell  the VP normalised and flipped into z >= 0, point_to_angle, angle_to_index on (gh, gw), floor(. + 0.5) on both
+ *         axes (coordinate_conversion.py:23-35, 53-61); -1 for a zero or non-finite VP and for a cell outside the map
+ *   l [device] sum(N) x 3 fp64 and line_offsets [host] n + 1 int64: the store's lines (vpk_lsd_rows_to_lines' l_out)
+ *   vps [device] sum(V) x 3 fp64 and vp_offsets [host] n + 1 int64: its ground-truth VPs
+ *   index [host] B int32 in 0..n-1, repeats allowed; transforms [host] B x 6 fp64 (h00 h01 h02 h10 h11 h12), NULL: the
+ *   identity, and then l_out is the stored lines byte for byte; out_offsets [host] B + 1 int64: the prefix sums of the
+ *   chosen images' line counts (checked); gh, gw 1..64.
+ *   Outputs [device], each may be NULL: l_out sum x 3 fp64; vp_out sum(V_b) x 3 fp64 in batch order; cell_out int32 per
+ *   VP (a gw + b or -1); labels_out B x gh gw fp32, zeroed by the call, 1.0f in every VP's cell (plain stores).
+ * Only the B indexed entries of the store's host offsets are read, and O(B) words are uploaded.  Asynchronous on the
+ * handle's stream.  VPK_ERR_ARG before anything is launched or written: a null handle, null offsets / index / out_offsets,
+ * null l or vps that an output needs, n < 1, B < 1, an index outside 0..n-1, out_offsets that do not match, a non-finite
+ * transform or det == 0, gh or gw outside 1..64. */
+int vpk_trainset_batch(vpk_handle* h, const double* l, const int64_t* line_offsets, const double* vps, const int64_t* vp_offsets,
+                       int n, const int32_t* index, const double* transforms, int B, const int64_t* out_offsets, int gh, int gw,
+                       double* l_out, double* vp_out, int32_t* cell_out, float* labels_out);
+/* stands in for: transform_param.mean_file (train_val.prototxt:1-62; Caffe's compute_image_mean).  Adds B uint8 rasters of P
+ * pixels [device, B x P] into sum [device, P uint32], one thread per pixel, images in index order: integer sums, exact.
+ * count [host]: the images summed so far, in and out; a call that would take it past floor((2^32 - 1) / 255) = 16 843 009
+ * returns VPK_ERR_LIMIT and adds nothing.  B < 1, P < 1, a negative count or a null buffer: VPK_ERR_ARG.  Asynchronous. */
+int vpk_trainset_accumulate(vpk_handle* h, const uint8_t* rasters, int B, int64_t P, uint32_t* sum, int64_t* count);
+
 #ifdef __cplusplus
 }
 #endif

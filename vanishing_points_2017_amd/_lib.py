@@ -105,6 +105,7 @@ EXPORTS = [
     "vpk_convtrain_load", "vpk_convtrain_store", "vpk_convtrain_load_momentum", "vpk_convtrain_store_momentum",
     "vpk_convtrain_set_iteration", "vpk_convtrain_get_iteration", "vpk_convtrain_forward", "vpk_convtrain_backward",
     "vpk_convtrain_read",
+    "vpk_trainset_batch", "vpk_trainset_accumulate",
 ]
 
 _lib = None
@@ -236,6 +237,9 @@ def load():
     lib.vpk_convtrain_forward.argtypes = [c_void, c_void, ctypes.c_int, c_void]
     lib.vpk_convtrain_backward.argtypes = [c_void, c_void, c_void]
     lib.vpk_convtrain_read.argtypes = [c_void, ctypes.c_int, ctypes.c_int, c_void]
+    lib.vpk_trainset_batch.argtypes = [c_void] * 5 + [ctypes.c_int, c_void, c_void, ctypes.c_int, c_void, ctypes.c_int,
+                                                      ctypes.c_int] + [c_void] * 4
+    lib.vpk_trainset_accumulate.argtypes = [c_void, c_void, ctypes.c_int, ctypes.c_int64, c_void, ctypes.POINTER(ctypes.c_int64)]
     _lib = lib
     return lib
 

@@ -29,6 +29,7 @@ UNITS = {
     "vpk_cnn.hip": [],
     "vpk_train.hip": [],                       # the dense head's SGD step (train_device.hpp)
     "vpk_convtrain.hip": [],                   # the conv stack's forward, backward and SGD step (convtrain_device.hpp)
+    "vpk_trainset.hip": ["-ffp-contract=off"], # the transforms of a batch round like NumPy's separate ufunc calls (trainset_device.hpp)
     "vpk_raster.hip": ["-ffp-contract=off"],   # the curve samples must round like NumPy's separate ufunc calls
     "vpk_horizon.hip": ["-ffp-contract=off"],
     "vpk_detect.hip": ["-ffp-contract=off"],   # the pixel conversion rounds like NumPy's separate ufunc calls (detect_device.hpp)

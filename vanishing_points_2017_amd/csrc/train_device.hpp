@@ -65,6 +65,9 @@ VPK_TRAIN_FN void sgd_update(float& w, float& v, float g, float lr_local, float 
 //   h2 = mix(h1 ^ j)
 // with mix = the finaliser of splitmix64 (Steele, Lea, Flood 2014) and GOLDEN = 0x9E3779B97F4A7C15.  The unit is kept when
 // the top 24 bits of h2 are >= floor(p 2^24), p the dropout ratio: P(keep) = 1 - p to 2^-24.  layer: 6 (drop6) or 7 (drop7).
+// The training set's draws (trainset_device.hpp) are the same hash under two more `layer` words: 0x41, the augmentation's
+// uniform draw k of batch slot b, u_k = (mix(mask_key(seed, iteration, 0x41, b) ^ k) >> 11) 2^-53 in [0, 1), and 0x53, the
+// sort key mix(mask_key(seed, epoch, 0x53, 0) ^ i) of example i in an epoch's shuffled order.
 VPK_TRAIN_FN uint64_t mix64(uint64_t z) {
     z ^= z >> 30;
     z *= 0xBF58476D1CE4E5B9ull;

@@ -111,7 +111,7 @@ int vpk_destroy(vpk_handle* h) {
     for (void* p : {h->em_ws, h->em_sess, h->small_ws, h->raster_hdr, h->lsd_ws, h->vpset_ws, h->emstep_ws, h->fe_ws})
         if (p) (void)hipFree(p);
     for (vpk_staged* s : {&h->em_hdr, &h->lsd_hdr, &h->fe_prep, &h->fe_rows, &h->lines_hdr, &h->overlay_hdr, &h->vpset_hdr,
-                          &h->estep_hdr, &h->emstep_hdr, &h->detect_hdr, &h->score_hdr}) {
+                          &h->estep_hdr, &h->emstep_hdr, &h->detect_hdr, &h->score_hdr, &h->trainset_hdr}) {
         if (s->dev) (void)hipFree(s->dev);
         for (auto& r : s->ring) {
             if (r.host) (void)hipHostFree(r.host);

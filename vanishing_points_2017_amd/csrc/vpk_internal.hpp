@@ -100,6 +100,7 @@ struct vpk_handle {
     bool emstep_ready = false;       // dynamic-LDS attribute set on the kernel
     vpk_staged detect_hdr;           // vpk_to_pixels_batch (vpk_detect.hip): line offsets + image sizes
     vpk_staged score_hdr;            // vpk_horizon_error_batch (vpk_score.hip): image sizes
+    vpk_staged trainset_hdr = {vpk_staged::MAX_RING};   // vpk_trainset_batch (vpk_trainset.hip): offsets + transforms of one batch
     vpk_train_state* train = nullptr; // vpk_train_create (vpk_train.hip): the dense head's master weights, momentum, activations
     vpk_convtrain_state* convtrain = nullptr; // vpk_convtrain_create (vpk_convtrain.hip): the conv stack's weights, momentum, blobs
 };
