@@ -11,7 +11,7 @@ from . import simlib
 SO = os.path.join(simlib.BUILD, "libvpk_hostsim_convtrain.so")
 SRC = [os.path.join(simlib.HERE, "sim_convtrain.cpp"), os.path.join(simlib.CSRC, "convtrain_device.hpp")]
 FWD, DGRAD, WGRAD = 0, 1, 2
-TILE, CHUNK, TARGET = 64, 16, 1024          # csrc/vpk_convtrain.hip: CT_TILE, CT_CHUNK, CT_TARGET_BLOCKS
+TILE, CHUNK, TARGET = 64, 16, 1024          # csrc/train_plan.hpp: CT_TILE, CT_CHUNK, CT_TARGET_BLOCKS
 
 _lib = None
 

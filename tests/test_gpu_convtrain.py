@@ -336,6 +336,35 @@ def test_refusals():
     code(lambda: _stack((513, 2, 2), [C.lrn()]), -5)
 
 
+def test_stack_trainer_refused_params_change_neither_half():
+    """StackTrainer.set_params with numbers the head refuses (dropout_ratio 1) raises and leaves both halves as they were: the
+    Python records, and the library's own numbers -- a step equals, bit for bit, that of a trainer that saw no refusal"""
+    from vanishing_points_2017_amd import _lib, train
+    dims, batch = (48, 32, 32, 16), 2
+    rs = np.random.RandomState(60)
+    x = (2.0 * rs.standard_normal((batch,) + C.EDGE_SHAPE)).astype(np.float32)
+    t = (rs.random_sample((batch, dims[3])) < 0.2).astype(np.float32)
+    masks = (np.ones((batch, dims[1]), np.uint8), np.ones((batch, dims[2]), np.uint8))
+    w, _ = C.make_weights(C.EDGE_SHAPE, C.EDGE_STACK, 61, momentum=False)
+    state = R.make_state(dims, 62, momentum=False)
+    res = []
+    for refuse in (True, False):
+        first = train.SolverParams(base_lr=0.003)
+        st = train.StackTrainer(C.EDGE_SHAPE, [_layer(d) for d in C.EDGE_STACK], dims, (w, R.blobs(state)), params=first)
+        try:
+            if refuse:
+                with pytest.raises(_lib.VpkError) as ei:
+                    st.set_params(train.SolverParams(base_lr=1.0, dropout_ratio=1.0))
+                assert "error -1" in str(ei.value), str(ei.value)
+            assert st.stack.params is first and st.head.params is first and st.params is first
+            loss, sig = st.step(x, t, masks)
+            res.append([_np(loss), _np(sig)] + st.stack.store() + st.head.store())
+        finally:
+            st.close()
+    assert all(np.array_equal(p, q) for p, q in zip(*res))
+    assert not np.array_equal(res[0][2], w[0])
+
+
 class _Net(object):
     """NetTrainer's flow at any geometry: a ConvStack below a Head on one handle"""
 

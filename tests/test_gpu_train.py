@@ -141,6 +141,73 @@ def test_batch_limits():
         tr.close()
 
 
+def test_refusals():
+    """each refusal with its code and with the state unchanged (the head's counterpart of test_gpu_convtrain.py's)"""
+    from vanishing_points_2017_amd import _lib, train
+    dims = (48, 8, 8, 4)
+    state = R.make_state(dims, 5)
+    w, v = R.blobs(state), R.blobs(state, "V")
+    x, t, m6, m7 = _batch(dims, 2, 6)
+
+    def code(fn, want):
+        with pytest.raises(_lib.VpkError) as ei:
+            fn()
+        assert "error %d" % want in str(ei.value), str(ei.value)
+
+    tr = train.Head(dims)
+    try:
+        code(tr.store, -4)                                                       # before load
+        code(tr.store_momentum, -4)
+        code(lambda: tr.load_momentum(v), -4)
+        code(lambda: tr.step(x, t), -4)
+        code(lambda: tr.evaluate(x, t), -4)
+        code(lambda: train.Head(dims, runtime=tr.rt), -4)                        # a second trainer on the handle
+        tr.load(w)
+        tr.load_momentum(v)
+        tr.iteration = 7
+        last = train.SolverParams(base_lr=0.01, dropout_ratio=0.25)
+        tr.set_params(last)
+        code(lambda: setattr(tr, "iteration", -1), -1)
+        code(lambda: tr.set_params(train.SolverParams(base_lr=1.0, dropout_ratio=1.0)), -1)
+        code(lambda: tr.set_params(train.SolverParams(base_lr=1.0, stepsize=0)), -1)
+        rt = tr.rt
+        with rt.on_stream():
+            dev = [rt.torch.from_numpy(a).to(rt.tdev) for a in (x, t, m6, m7)]
+            loss, sig = rt.torch.empty((1,), device=rt.tdev), rt.torch.empty((2, dims[3]), device=rt.tdev)
+        for a, b in ((dev[2], None), (None, dev[3])):                            # one mask only
+            code(lambda: rt.check(rt.lib.vpk_train_step(rt.h, rt.ptr(dev[0]), rt.ptr(dev[1]), 2, rt.ptr(a), rt.ptr(b), 0, rt.ptr(loss),
+                                                        rt.ptr(sig))), -1)
+        for b in (0, 33):
+            xb, tb, _, _ = _batch(dims, b, 2)
+            with pytest.raises(_lib.VpkError) as ei:
+                tr.step(xb, tb)
+            assert "error -5" in str(ei.value) or "error -1" in str(ei.value), str(ei.value)     # as test_batch_limits
+        with pytest.raises(ValueError):
+            tr.load(w[:1] + [w[1][:-1]] + w[2:])                                 # a blob of the wrong shape
+        with pytest.raises(ValueError):
+            tr.load_momentum(v[:5])                                              # ... and a list that is short of one
+        tr.synchronize()
+        assert tr.iteration == 7 and tr.params is last
+        assert all(np.array_equal(p, q) for p, q in zip(tr.store(), w))
+        assert all(np.array_equal(p, q) for p, q in zip(tr.store_momentum(), v))
+        # the library's own numbers are the ones set last: a step equals, bit for bit, that of a trainer no refusal touched
+        twin = _trainer(dims, state, iteration=7, params={"base_lr": 0.01, "dropout_ratio": 0.25})
+        try:
+            res = []
+            for h in (tr, twin):
+                loss, sig = h.step(x, t, masks=(m6, m7))
+                res.append([loss.cpu().numpy(), sig.cpu().numpy()] + h.store() + h.store_momentum())
+            assert all(np.array_equal(p, q) for p, q in zip(*res))
+            assert not np.array_equal(res[0][2], w[0]) and tr.iteration == 8
+        finally:
+            twin.close()
+        tr.load(w)
+        assert tr.iteration == 0 and all(np.array_equal(p, q) for p, q in zip(tr.store(), w))
+        assert all(not m.any() for m in tr.store_momentum())
+    finally:
+        tr.close()
+
+
 def test_eval_is_the_forward_without_dropout():
     """B = 70 (three chunks) against the float64 TEST phase; the rows of the first chunk against a step's forward under
     all-one masks with the scale removed (dropout_ratio 0); no weight changes"""

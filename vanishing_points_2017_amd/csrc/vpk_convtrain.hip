@@ -10,25 +10,23 @@
 // No dW buffer beyond the slabs' partials and no float atomic: two runs from the same state give the same bits.
 // Arithmetic: f32 operands, f32 accumulation (v_mfma_f32_32x32x2_f32 is an exact fmaf chain).  The index maps and the
 // per-element rules are convtrain_device.hpp's; the update is train_device.hpp's.
+// What the host decides lives elsewhere: the tile constants, the shapes and limits of a chain, the grids, the slab split and
+// buffer sizes, the kept blobs' life cycle, the solver's rates and the set_params rule in train_plan.hpp (host-tested); the
+// weights, momentum, iteration and their load / store entry points in train_store.hpp, shared with vpk_train.hip.  Here
+// are the kernels, the launches and the refusals of forward, backward and read.
 #include "vpk_internal.hpp"
 #include "convtrain_device.hpp"
 #include "train_device.hpp"
+#include "train_plan.hpp"
+#include "train_store.hpp"
 
 #include <string.h>
 #include <vector>
 
 namespace ct = vpk_convtrain;
+using namespace vpk_train_plan;
 
 namespace {
-
-constexpr int CT_MAX_B = 32;
-constexpr int CT_MAX_LAYERS = 32;
-constexpr int CT_TILE = 64;           // a workgroup's tile of C: 64 x 64, one 32 x 32 quadrant per wave
-constexpr int CT_CHUNK = 16;          // reduction terms staged in LDS at a time
-constexpr int CT_LDS_ROW = CT_TILE + 4;
-constexpr int CT_TARGET_BLOCKS = 1024;
-constexpr int CT_LRN_PIX = 32;        // pixels of an LRN workgroup (x 8 channel lanes)
-constexpr int CT_LRN_MAX_C = 512;     // 64 KiB of LDS
 
 typedef float ct_f32x16 __attribute__((ext_vector_type(16)));
 
@@ -179,67 +177,16 @@ __global__ void ct_pool_bwd(const float* __restrict__ dy, const int32_t* __restr
     dx[i] = s;
 }
 
-struct ct_layer {
-    vpk_stack_layer d = {};
-    int C = 0, H = 0, W = 0;          // input
-    int OC = 0, OH = 0, OW = 0;       // output
-    float *Wt = nullptr, *V = nullptr, *b = nullptr, *vb = nullptr;     // CONV
+struct ct_layer : LayerShape {
+    int blob = -1;                                                      // CONV: its weight in the store, the bias behind it
     float *out = nullptr, *grad = nullptr, *scale = nullptr;            // cap x OC x OH x OW (scale: LRN)
     int32_t* idx = nullptr;                                             // POOL
-    size_t out_size() const { return (size_t)OC * OH * OW; }
-    size_t in_size() const { return (size_t)C * H * W; }
-    size_t weights() const { return (size_t)OC * (C / d.groups) * d.kernel * d.kernel; }
 };
-
-// the shapes of a chain; false where it does not chain.  *limit: an LRN wider than the kernel's LDS column
-bool chain(int C, int H, int W, const vpk_stack_layer* layers, int n, std::vector<ct_layer>& out, bool* limit) {
-    *limit = false;
-    if (C < 1 || H < 1 || W < 1 || !layers || n < 1 || n > CT_MAX_LAYERS) return false;
-    for (int l = 0; l < n; ++l) {
-        ct_layer L;
-        L.d = layers[l];
-        L.C = C; L.H = H; L.W = W;
-        const vpk_stack_layer& d = L.d;
-        if (d.kind == VPK_LAYER_CONV) {
-            if (d.out_channels < 1 || d.kernel < 1 || d.stride < 1 || d.pad < 0 || d.groups < 1) return false;
-            if (C % d.groups || d.out_channels % d.groups) return false;
-            L.OC = d.out_channels;
-            L.OH = ct::conv_out_size(H, d.kernel, d.stride, d.pad);
-            L.OW = ct::conv_out_size(W, d.kernel, d.stride, d.pad);
-        } else if (d.kind == VPK_LAYER_LRN) {
-            if (d.local_size < 1 || d.local_size % 2 == 0) return false;
-            if (C > CT_LRN_MAX_C) *limit = true;
-            L.OC = C; L.OH = H; L.OW = W;
-        } else if (d.kind == VPK_LAYER_POOL) {
-            if (d.kernel < 1 || d.stride < 1) return false;
-            L.OC = C;
-            L.OH = ct::pool_out_size(H, d.kernel, d.stride);
-            L.OW = ct::pool_out_size(W, d.kernel, d.stride);
-        } else {
-            return false;
-        }
-        if (L.OH < 1 || L.OW < 1) return false;
-        if ((double)L.OC * L.OH * L.OW * CT_MAX_B >= 2147483648.0) return false;      // the kernels index pixels in int
-        out.push_back(L);
-        C = L.OC; H = L.OH; W = L.OW;
-    }
-    return true;
-}
-
-ct::ConvGeom geom(const ct_layer& L, int B) {
-    ct::ConvGeom q;
-    q.C = L.C; q.H = L.H; q.W = L.W;
-    q.OC = L.OC; q.K = L.d.kernel; q.stride = L.d.stride; q.pad = L.d.pad; q.groups = L.d.groups; q.relu = L.d.relu ? 1 : 0;
-    q.OH = L.OH; q.OW = L.OW; q.B = B;
-    return q;
-}
 
 template <int MODE>
 void launch_gemm(hipStream_t st, const ct::ConvPtrs& p, const ct::ConvGeom& q, int slabs, int slab_len) {
-    int M, N, R;
-    ct::gemm_dims(MODE, q, M, N, R);
-    const dim3 grid((N + CT_TILE - 1) / CT_TILE, (M + CT_TILE - 1) / CT_TILE, q.groups * slabs);
-    ct_gemm<MODE><<<grid, 256, 0, st>>>(p, q, slabs, slab_len);
+    const Grid g = gemm_grid(MODE, q, slabs);
+    ct_gemm<MODE><<<dim3(g.x, g.y, g.z), 256, 0, st>>>(p, q, slabs, slab_len);
 }
 
 }  // namespace
@@ -247,20 +194,18 @@ void launch_gemm(hipStream_t st, const ct::ConvPtrs& p, const ct::ConvGeom& q, i
 struct vpk_convtrain_state {
     int C = 0, H = 0, W = 0;
     std::vector<ct_layer> L;
+    vpk_param_store ps;               // [W, b] of every CONV layer in stack order, and their momentum
     float* xin = nullptr;             // the forward's copy of X: cap x C x H x W
     int cap = 0;                      // images the blobs are allocated for
-    int fwd_B = 0;                    // batch of the last forward that no backward has consumed (0: none)
-    int blob_B = 0;                   // batch the kept blobs hold
-    bool grads = false;               // the gradient blobs belong to the kept forward
+    KeptBlobs kept;                   // what the blobs hold and who may use it (train_plan.hpp)
     float* partial = nullptr;         // the weight gradient's slabs
     size_t partial_bytes = 0;
-    vpk_train_params p = {};
-    long long iteration = 0;
-    bool loaded = false;
     size_t in_size() const { return (size_t)C * H * W; }
 };
 
 namespace {
+
+vpk_param_store* store_of(const vpk_handle* h) { return h && h->convtrain ? &h->convtrain->ps : nullptr; }
 
 void free_blobs(vpk_convtrain_state* s) {
     for (ct_layer& L : s->L) {
@@ -282,11 +227,10 @@ int reserve_blobs(vpk_handle* h, vpk_convtrain_state* s, int B) {
     auto alloc = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
     alloc((void**)&s->xin, (size_t)B * s->in_size() * 4);
     for (ct_layer& L : s->L) {
-        const size_t bytes = (size_t)B * L.out_size() * 4;
-        alloc((void**)&L.out, bytes);
-        alloc((void**)&L.grad, bytes);
-        if (L.d.kind == VPK_LAYER_LRN) alloc((void**)&L.scale, bytes);
-        if (L.d.kind == VPK_LAYER_POOL) alloc((void**)&L.idx, bytes);
+        alloc((void**)&L.out, blob_bytes(L, B));
+        alloc((void**)&L.grad, blob_bytes(L, B));
+        if (L.d.kind == VPK_LAYER_LRN) alloc((void**)&L.scale, blob_bytes(L, B));
+        if (L.d.kind == VPK_LAYER_POOL) alloc((void**)&L.idx, blob_bytes(L, B));
     }
     if (e != hipSuccess) {
         (void)hipGetLastError();
@@ -297,39 +241,6 @@ int reserve_blobs(vpk_handle* h, vpk_convtrain_state* s, int B) {
     return VPK_OK;
 }
 
-int count_convs(const vpk_convtrain_state* s) {
-    int n = 0;
-    for (const ct_layer& L : s->L) n += L.d.kind == VPK_LAYER_CONV;
-    return n;
-}
-
-int ct_copy(vpk_handle* h, const char* who, void* const* blobs, int momentum, int to_device, bool need_loaded) {
-    if (!h) return VPK_ERR_ARG;
-    vpk_convtrain_state* s = h->convtrain;
-    if (!s || (need_loaded && !s->loaded)) return vpk_fail(h, VPK_ERR_STATE, who);
-    const int n = count_convs(s);
-    if (n > 0 && !blobs) return vpk_fail(h, VPK_ERR_ARG, who);          // a stack without CONV layers has no blobs to name
-    for (int i = 0; i < 2 * n; ++i)
-        if (!blobs[i]) return vpk_fail(h, VPK_ERR_ARG, who);
-    VPK_HIP(h, hipSetDevice(h->device));
-    VPK_HIP(h, hipStreamSynchronize(h->stream));
-    int i = 0;
-    for (ct_layer& L : s->L) {
-        if (L.d.kind != VPK_LAYER_CONV) continue;
-        float* dw = momentum ? L.V : L.Wt;
-        float* db = momentum ? L.vb : L.b;
-        if (to_device) {
-            VPK_HIP(h, hipMemcpy(dw, blobs[i], L.weights() * 4, hipMemcpyHostToDevice));
-            VPK_HIP(h, hipMemcpy(db, blobs[i + 1], (size_t)L.OC * 4, hipMemcpyHostToDevice));
-        } else {
-            VPK_HIP(h, hipMemcpy(blobs[i], dw, L.weights() * 4, hipMemcpyDeviceToHost));
-            VPK_HIP(h, hipMemcpy(blobs[i + 1], db, (size_t)L.OC * 4, hipMemcpyDeviceToHost));
-        }
-        i += 2;
-    }
-    return VPK_OK;
-}
-
 }  // namespace
 
 void vpk_convtrain_free(vpk_handle* h) {
@@ -337,9 +248,7 @@ void vpk_convtrain_free(vpk_handle* h) {
     if (!s) return;
     (void)hipStreamSynchronize(h->stream);
     free_blobs(s);
-    for (ct_layer& L : s->L)
-        for (float* p : {L.Wt, L.V, L.b, L.vb})
-            if (p) (void)hipFree(p);
+    s->ps.free();
     if (s->partial) (void)hipFree(s->partial);
     delete s;
     h->convtrain = nullptr;
@@ -382,26 +291,30 @@ int vpk_convtrain_net_layers(vpk_stack_layer* out, int capacity, int32_t in_shap
 int vpk_convtrain_create(vpk_handle* h, int C, int H, int W, const vpk_stack_layer* layers, int n_layers) {
     if (!h) return VPK_ERR_ARG;
     if (h->convtrain) return vpk_fail(h, VPK_ERR_STATE, "vpk_convtrain_create: the handle already has a conv trainer");
-    std::vector<ct_layer> L;
-    bool limit = false;
-    if (!chain(C, H, W, layers, n_layers, L, &limit))
+    std::vector<LayerShape> shapes;
+    const StackRule rule = chain(C, H, W, layers, n_layers, shapes);
+    if (rule == STACK_NO_CHAIN)
         return vpk_fail(h, VPK_ERR_ARG, "vpk_convtrain_create: the layers do not chain on this input shape");
-    if (limit) return vpk_fail(h, VPK_ERR_LIMIT, "vpk_convtrain_create: an LRN on more than 512 channels");
+    if (rule == STACK_LRN_WIDE) return vpk_fail(h, VPK_ERR_LIMIT, "vpk_convtrain_create: an LRN on more than 512 channels");
     VPK_HIP(h, hipSetDevice(h->device));
     vpk_convtrain_state* s = new vpk_convtrain_state();
     h->convtrain = s;
     s->C = C; s->H = H; s->W = W;
-    s->L = L;
-    vpk_train_default_params(&s->p);
-    hipError_t e = hipSuccess;
-    auto alloc = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
-    for (ct_layer& l : s->L) {
-        if (l.d.kind != VPK_LAYER_CONV) continue;
-        alloc((void**)&l.Wt, l.weights() * 4);
-        alloc((void**)&l.V, l.weights() * 4);
-        alloc((void**)&l.b, (size_t)l.OC * 4);
-        alloc((void**)&l.vb, (size_t)l.OC * 4);
+    static_assert(2 * CT_MAX_LAYERS <= vpk_param_store::MAX_BLOBS, "a weight and a bias per layer");
+    size_t counts[2 * CT_MAX_LAYERS];
+    int blobs = 0;
+    for (const LayerShape& shape : shapes) {
+        ct_layer l;
+        static_cast<LayerShape&>(l) = shape;
+        if (l.d.kind == VPK_LAYER_CONV) {
+            l.blob = blobs;
+            counts[blobs++] = l.weights();
+            counts[blobs++] = (size_t)l.OC;
+        }
+        s->L.push_back(l);
     }
+    vpk_train_default_params(&s->ps.p);
+    const hipError_t e = s->ps.alloc(counts, blobs);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         vpk_convtrain_free(h);
@@ -419,120 +332,87 @@ int vpk_convtrain_destroy(vpk_handle* h) {
 int vpk_convtrain_set_params(vpk_handle* h, const vpk_train_params* p) {
     if (!h || !p) return VPK_ERR_ARG;
     if (!h->convtrain) return vpk_fail(h, VPK_ERR_STATE, "vpk_convtrain_set_params: no conv trainer (vpk_convtrain_create)");
-    if (p->stepsize < 1) return vpk_fail(h, VPK_ERR_ARG, "vpk_convtrain_set_params: stepsize must be >= 1");
-    h->convtrain->p = *p;
+    if (!stack_params_ok(*p)) return vpk_fail(h, VPK_ERR_ARG, "vpk_convtrain_set_params: stepsize must be >= 1");
+    h->convtrain->ps.p = *p;
     return VPK_OK;
 }
 
+// a null list of blobs is looked at after the trainer, and only by a stack that has CONV layers (train_store.hpp)
 int vpk_convtrain_load(vpk_handle* h, const void* const* blobs) {
-    const int rc = ct_copy(h, "vpk_convtrain_load", (void* const*)blobs, 0, 1, false);
-    if (rc) return rc;
-    vpk_convtrain_state* s = h->convtrain;
-    for (ct_layer& L : s->L) {
-        if (L.d.kind != VPK_LAYER_CONV) continue;
-        VPK_HIP(h, hipMemsetAsync(L.V, 0, L.weights() * 4, h->stream));
-        VPK_HIP(h, hipMemsetAsync(L.vb, 0, (size_t)L.OC * 4, h->stream));
-    }
-    VPK_HIP(h, hipStreamSynchronize(h->stream));
-    s->iteration = 0;
-    s->loaded = true;
-    return VPK_OK;
+    return vpk_store_load(h, store_of(h), "vpk_convtrain_load", blobs, false);
 }
 
 int vpk_convtrain_store(vpk_handle* h, void* const* blobs_out) {
-    return ct_copy(h, "vpk_convtrain_store before vpk_convtrain_create / vpk_convtrain_load", blobs_out, 0, 0, true);
+    return vpk_store_copy(h, store_of(h), "vpk_convtrain_store", blobs_out, false, false, true, false);
 }
 
 int vpk_convtrain_load_momentum(vpk_handle* h, const void* const* blobs) {
-    return ct_copy(h, "vpk_convtrain_load_momentum before vpk_convtrain_create / vpk_convtrain_load", (void* const*)blobs, 1, 1,
-                   true);
+    return vpk_store_copy(h, store_of(h), "vpk_convtrain_load_momentum", (void* const*)blobs, true, true, true, false);
 }
 
 int vpk_convtrain_store_momentum(vpk_handle* h, void* const* blobs_out) {
-    return ct_copy(h, "vpk_convtrain_store_momentum before vpk_convtrain_create / vpk_convtrain_load", blobs_out, 1, 0, true);
+    return vpk_store_copy(h, store_of(h), "vpk_convtrain_store_momentum", blobs_out, true, false, true, false);
 }
 
 int vpk_convtrain_set_iteration(vpk_handle* h, long long iteration) {
-    if (!h) return VPK_ERR_ARG;
-    if (!h->convtrain) return vpk_fail(h, VPK_ERR_STATE, "vpk_convtrain_set_iteration: no conv trainer (vpk_convtrain_create)");
-    if (iteration < 0) return vpk_fail(h, VPK_ERR_ARG, "vpk_convtrain_set_iteration: iteration < 0");
-    h->convtrain->iteration = iteration;
-    return VPK_OK;
+    return vpk_store_set_iteration(h, store_of(h), "vpk_convtrain_set_iteration", iteration);
 }
 
 int vpk_convtrain_get_iteration(const vpk_handle* h, long long* iteration_out) {
-    if (!h || !iteration_out || !h->convtrain) return VPK_ERR_ARG;
-    *iteration_out = h->convtrain->iteration;
-    return VPK_OK;
+    return vpk_store_get_iteration(store_of(h), iteration_out);
 }
 
 int vpk_convtrain_forward(vpk_handle* h, const float* X, int B, float* top_out) {
     if (!h) return VPK_ERR_ARG;
     vpk_convtrain_state* s = h->convtrain;
-    if (!s || !s->loaded) return vpk_fail(h, VPK_ERR_STATE, "vpk_convtrain_forward before vpk_convtrain_create / vpk_convtrain_load");
+    if (!s || !s->ps.loaded) return vpk_fail(h, VPK_ERR_STATE, "vpk_convtrain_forward before vpk_convtrain_create / vpk_convtrain_load");
     if (B < 1 || B > CT_MAX_B) return vpk_fail(h, VPK_ERR_LIMIT, "vpk_convtrain_forward: the batch must be 1..32");
     if (!X) return vpk_fail(h, VPK_ERR_ARG, "vpk_convtrain_forward: X is required");
     VPK_HIP(h, hipSetDevice(h->device));
     if (int rc = reserve_blobs(h, s, B)) return rc;
     hipStream_t st = h->stream;
-    s->fwd_B = 0;
-    s->blob_B = 0;
-    s->grads = false;
+    s->kept.forward_begins();         // a refusal above leaves the kept blobs as they were, one below leaves none
     VPK_HIP(h, hipMemcpyAsync(s->xin, X, (size_t)B * s->in_size() * 4, hipMemcpyDeviceToDevice, st));
     const float* in = s->xin;
     for (ct_layer& L : s->L) {
         const vpk_stack_layer& d = L.d;
         if (d.kind == VPK_LAYER_CONV) {
-            ct::ConvPtrs p = {in, L.Wt, L.b, nullptr, nullptr, L.out};
+            ct::ConvPtrs p = {in, s->ps.w[L.blob], s->ps.w[L.blob + 1], nullptr, nullptr, L.out};
             launch_gemm<ct::GEMM_FWD>(st, p, geom(L, B), 1, L.C / d.groups * d.kernel * d.kernel);
         } else if (d.kind == VPK_LAYER_LRN) {
-            const int P = L.H * L.W;
-            const dim3 grid((P + CT_LRN_PIX - 1) / CT_LRN_PIX, B);
-            ct_lrn_fwd<<<grid, 256, (size_t)L.C * CT_LRN_PIX * 4, st>>>(in, L.out, L.scale, L.C, P, d.local_size,
-                                                                        ct::lrn_alpha_over_n(d.alpha, d.local_size), d.beta, d.k);
+            const Grid g = lrn_grid(L, B);
+            ct_lrn_fwd<<<dim3(g.x, g.y), 256, lrn_lds_bytes(L), st>>>(in, L.out, L.scale, L.C, L.H * L.W, d.local_size,
+                                                                      ct::lrn_alpha_over_n(d.alpha, d.local_size), d.beta, d.k);
         } else {
-            const size_t planes = (size_t)B * L.C, total = planes * L.OH * L.OW;
-            ct_pool_fwd<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(in, L.out, L.idx, planes, L.H, L.W, L.OH, L.OW, d.kernel,
+            const size_t planes = (size_t)B * L.C;
+            ct_pool_fwd<<<blocks_of(planes * L.OH * L.OW), 256, 0, st>>>(in, L.out, L.idx, planes, L.H, L.W, L.OH, L.OW, d.kernel,
                                                                          d.stride);
         }
         in = L.out;
     }
     if (top_out)
-        VPK_HIP(h, hipMemcpyAsync(top_out, s->L.back().out, (size_t)B * s->L.back().out_size() * 4, hipMemcpyDeviceToDevice, st));
+        VPK_HIP(h, hipMemcpyAsync(top_out, s->L.back().out, blob_bytes(s->L.back(), B), hipMemcpyDeviceToDevice, st));
     VPK_HIP(h, hipGetLastError());
-    s->fwd_B = B;
-    s->blob_B = B;
+    s->kept.forward_done(B);
     return VPK_OK;
 }
 
 int vpk_convtrain_backward(vpk_handle* h, const float* d_top, float* d_input_out) {
     if (!h) return VPK_ERR_ARG;
     vpk_convtrain_state* s = h->convtrain;
-    if (!s || !s->loaded || s->fwd_B < 1)
+    if (!s || !s->ps.loaded || !s->kept.backward_allowed())
         return vpk_fail(h, VPK_ERR_STATE, "vpk_convtrain_backward without a vpk_convtrain_forward to go back through");
     if (!d_top) return vpk_fail(h, VPK_ERR_ARG, "vpk_convtrain_backward: d_top is required");
     VPK_HIP(h, hipSetDevice(h->device));
-    const int B = s->fwd_B;
+    const int B = s->kept.fwd_B;
     hipStream_t st = h->stream;
     // the slabs of every weight gradient of this batch share one buffer
-    size_t want = 0;
-    for (ct_layer& L : s->L) {
-        if (L.d.kind != VPK_LAYER_CONV) continue;
-        int slabs, slab_len;
-        const ct::ConvGeom q = geom(L, B);
-        ct::wgrad_slabs(q, CT_TILE, CT_CHUNK, CT_TARGET_BLOCKS, slabs, slab_len);
-        const size_t need = (size_t)slabs * L.OC * (q.ICg() * q.K * q.K + 1) * 4;
-        if (need > want) want = need;
-    }
-    if (want)
+    if (const size_t want = slab_buffer_bytes(s->L, B))
         if (int rc = vpk_reserve(h, (void**)&s->partial, &s->partial_bytes, want, "vpk_convtrain_backward: weight-gradient slabs"))
             return rc;
-    const vpk_train_params& sp = s->p;
-    const float lr = vpk_train::learning_rate(sp.base_lr, sp.gamma, sp.stepsize, s->iteration);
-    const float lr_w = lr * sp.lr_mult_weight, dec_w = sp.weight_decay * sp.decay_mult_weight;
-    const float lr_b = lr * sp.lr_mult_bias, dec_b = sp.weight_decay * sp.decay_mult_bias;
+    const Rates r = rates(s->ps.p, s->ps.iteration);
     const int n = (int)s->L.size();
-    VPK_HIP(h, hipMemcpyAsync(s->L[n - 1].grad, d_top, (size_t)B * s->L[n - 1].out_size() * 4, hipMemcpyDeviceToDevice, st));
+    VPK_HIP(h, hipMemcpyAsync(s->L[n - 1].grad, d_top, blob_bytes(s->L[n - 1], B), hipMemcpyDeviceToDevice, st));
     for (int l = n - 1; l >= 0; --l) {
         ct_layer& L = s->L[l];
         const vpk_stack_layer& d = L.d;
@@ -540,42 +420,39 @@ int vpk_convtrain_backward(vpk_handle* h, const float* d_top, float* d_input_out
         float* din = l > 0 ? s->L[l - 1].grad : d_input_out;        // NULL: the stack's input needs no gradient
         if (d.kind == VPK_LAYER_CONV) {
             const ct::ConvGeom q = geom(L, B);
+            float *Wt = s->ps.w[L.blob], *bias = s->ps.w[L.blob + 1];
             if (din) {
-                ct::ConvPtrs p = {in, L.Wt, L.b, L.out, L.grad, din};
+                ct::ConvPtrs p = {in, Wt, bias, L.out, L.grad, din};
                 launch_gemm<ct::GEMM_DGRAD>(st, p, q, 1, q.OCg() * q.K * q.K);
             }
-            int slabs, slab_len;
-            ct::wgrad_slabs(q, CT_TILE, CT_CHUNK, CT_TARGET_BLOCKS, slabs, slab_len);
-            ct::ConvPtrs p = {in, L.Wt, L.b, L.out, L.grad, s->partial};
-            launch_gemm<ct::GEMM_WGRAD>(st, p, q, slabs, slab_len);
-            const int cols = q.ICg() * q.K * q.K + 1;
-            const size_t total = (size_t)L.OC * cols;
-            ct_update<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(L.Wt, L.V, L.b, L.vb, s->partial, slabs, L.OC, cols, lr_w,
-                                                                       dec_w, lr_b, dec_b, sp.momentum);
+            const WgradPlan wg = plan_wgrad(L, B);
+            ct::ConvPtrs p = {in, Wt, bias, L.out, L.grad, s->partial};
+            launch_gemm<ct::GEMM_WGRAD>(st, p, q, wg.slabs, wg.slab_len);
+            ct_update<<<blocks_of((size_t)L.OC * wg.cols), 256, 0, st>>>(Wt, s->ps.v[L.blob], bias, s->ps.v[L.blob + 1], s->partial,
+                                                                         wg.slabs, L.OC, wg.cols, r.lr_w, r.dec_w, r.lr_b, r.dec_b,
+                                                                         r.mu);
         } else if (!din) {
             continue;
         } else if (d.kind == VPK_LAYER_LRN) {
-            const int P = L.H * L.W;
-            const dim3 grid((P + CT_LRN_PIX - 1) / CT_LRN_PIX, B);
-            ct_lrn_bwd<<<grid, 256, (size_t)L.C * CT_LRN_PIX * 4, st>>>(in, L.out, L.scale, L.grad, din, L.C, P, d.local_size, d.beta,
-                                                                        ct::lrn_back_coef(d.alpha, d.beta, d.local_size));
+            const Grid g = lrn_grid(L, B);
+            ct_lrn_bwd<<<dim3(g.x, g.y), 256, lrn_lds_bytes(L), st>>>(in, L.out, L.scale, L.grad, din, L.C, L.H * L.W, d.local_size,
+                                                                      d.beta, ct::lrn_back_coef(d.alpha, d.beta, d.local_size));
         } else {
-            const size_t planes = (size_t)B * L.C, total = planes * L.H * L.W;
-            ct_pool_bwd<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(L.grad, L.idx, din, planes, L.H, L.W, L.OH, L.OW, d.kernel,
-                                                                         d.stride);
+            const size_t planes = (size_t)B * L.C;
+            ct_pool_bwd<<<blocks_of(planes * L.H * L.W), 256, 0, st>>>(L.grad, L.idx, din, planes, L.H, L.W, L.OH, L.OW, d.kernel,
+                                                                       d.stride);
         }
     }
     VPK_HIP(h, hipGetLastError());
-    s->fwd_B = 0;
-    s->grads = true;
-    s->iteration += 1;
+    s->kept.backward_done();
+    s->ps.iteration += 1;
     return VPK_OK;
 }
 
 int vpk_convtrain_read(vpk_handle* h, int layer, int kind, void* out) {
     if (!h) return VPK_ERR_ARG;
     vpk_convtrain_state* s = h->convtrain;
-    if (!s || s->blob_B < 1) return vpk_fail(h, VPK_ERR_STATE, "vpk_convtrain_read without a forward");
+    if (!s || !s->kept.read_allowed()) return vpk_fail(h, VPK_ERR_STATE, "vpk_convtrain_read without a forward");
     if (!out) return vpk_fail(h, VPK_ERR_ARG, "vpk_convtrain_read: out is required");
     if (layer < 0 || layer >= (int)s->L.size()) return vpk_fail(h, VPK_ERR_ARG, "vpk_convtrain_read: no such layer");
     const ct_layer& L = s->L[layer];
@@ -588,13 +465,13 @@ int vpk_convtrain_read(vpk_handle* h, int layer, int kind, void* out) {
         if (L.d.kind != VPK_LAYER_LRN) return vpk_fail(h, VPK_ERR_ARG, "vpk_convtrain_read: not an LRN layer");
         src = L.scale;
     } else if (kind == VPK_BLOB_GRADIENT) {
-        if (!s->grads) return vpk_fail(h, VPK_ERR_STATE, "vpk_convtrain_read: no backward since the last forward");
+        if (!s->kept.gradient_read_allowed()) return vpk_fail(h, VPK_ERR_STATE, "vpk_convtrain_read: no backward since the last forward");
         src = L.grad;
     } else {
         return vpk_fail(h, VPK_ERR_ARG, "vpk_convtrain_read: unknown kind");
     }
     VPK_HIP(h, hipSetDevice(h->device));
-    VPK_HIP(h, hipMemcpyAsync(out, src, (size_t)s->blob_B * L.out_size() * 4, hipMemcpyDeviceToDevice, h->stream));
+    VPK_HIP(h, hipMemcpyAsync(out, src, blob_bytes(L, s->kept.blob_B), hipMemcpyDeviceToDevice, h->stream));
     return VPK_OK;
 }
 

@@ -8,20 +8,19 @@
 //             dX: per-row-tile partial sums, added in tile order with the dropout/ReLU backward applied    (train_dx_reduce)
 // No dW buffer exists and no float atomic is used: two runs from the same state give the same bits.
 // Arithmetic: f32 parameters, f32 accumulation, VALU FMAs.  The per-element functions are train_device.hpp's.
+// What the host decides lives elsewhere: the tile constants, the launch plans, the workspace sizes, the solver's rates and
+// the set_params rule in train_plan.hpp (host-tested); the weights, momentum, iteration and their load / store entry points
+// in train_store.hpp, shared with vpk_convtrain.hip.  Here are the kernels, the launches and the step's own refusals.
 #include "vpk_internal.hpp"
 #include "train_device.hpp"
+#include "train_plan.hpp"
+#include "train_store.hpp"
 
 #include <string.h>
 
-namespace {
+using namespace vpk_train_plan;
 
-constexpr int TRAIN_MAX_B = 32;       // rows of a step: dY and X of a tile stay in LDS, the dX accumulators in registers
-constexpr int FWD_ROWS = 4;           // rows of W per forward wave
-constexpr int FWD_RT = 16;            // ... and per workgroup of four waves
-constexpr int SWEEP_KT = 256;         // columns of a sweep tile: 64 lanes x 4
-constexpr int SWEEP_MAX_RT = 128;     // most rows of a sweep tile (its dY slice is staged in LDS)
-constexpr int SWEEP_MIN_RT = 16;
-constexpr int SWEEP_TARGET_BLOCKS = 2048;
+namespace {
 
 // 4 consecutive floats of a row from column k.  VEC: the row is 16-byte aligned and K % 4 == 0, so a group is wholly inside
 // the row or wholly outside; otherwise element by element.  Outside the row: zeros.
@@ -310,10 +309,7 @@ __global__ void train_masks(uint8_t* __restrict__ m, int B, int H, uint64_t seed
 
 struct vpk_train_state {
     int dims[4] = {};                 // I, H6, H7, O
-    float* W[3] = {};                 // fc6 [H6 x I], fc7 [H7 x H6], fc8 [O x H7]
-    float* V[3] = {};                 // their momentum
-    float* b[3] = {};
-    float* vb[3] = {};
+    vpk_param_store ps;               // fc6 [H6 x I], its bias, fc7 [H7 x H6], its bias, fc8 [O x H7], its bias; their momentum
     float *a6 = nullptr, *d6 = nullptr, *a7 = nullptr, *d7 = nullptr;       // TRAIN_MAX_B rows each
     float *z = nullptr, *dz = nullptr, *sig = nullptr, *dA7 = nullptr, *dA6 = nullptr;
     uint8_t *m6 = nullptr, *m7 = nullptr;
@@ -321,45 +317,18 @@ struct vpk_train_state {
     float* fpartial = nullptr;        // the forward's slab sums: [slab][B][N]
     float* xpartial = nullptr;        // fc6's dX partials [row tile][B][I]: vpk_train_step_dx only, allocated by its first call
     size_t xpartial_bytes = 0;
-    vpk_train_params p = {};
-    long long iteration = 0;
-    bool loaded = false;
+    float* W(int l) const { return ps.w[2 * l]; }
+    float* V(int l) const { return ps.v[2 * l]; }
+    float* b(int l) const { return ps.w[2 * l + 1]; }
+    float* vb(int l) const { return ps.v[2 * l + 1]; }
 };
 
 namespace {
 
-int layer_n(const vpk_train_state* s, int l) { return s->dims[l + 1]; }
-int layer_k(const vpk_train_state* s, int l) { return s->dims[l]; }
-
-// rows of a sweep tile: as many as keep about SWEEP_TARGET_BLOCKS workgroups, a multiple of 8 within the LDS slice
-int sweep_rt(int N, int K) {
-    const long long kt = (K + SWEEP_KT - 1) / SWEEP_KT;
-    long long rt = ((long long)N * kt + SWEEP_TARGET_BLOCKS - 1) / SWEEP_TARGET_BLOCKS;
-    rt = (rt + 7) / 8 * 8;
-    if (rt < SWEEP_MIN_RT) rt = SWEEP_MIN_RT;
-    if (rt > SWEEP_MAX_RT) rt = SWEEP_MAX_RT;
-    return (int)rt;
-}
-int sweep_tiles(int N, int K) { const int rt = sweep_rt(N, K); return (N + rt - 1) / rt; }
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
-// the forward's split of K: 256-column chunks, dealt to as many slabs as keep about SWEEP_TARGET_BLOCKS workgroups
-struct fwd_plan { int chunks, chunks_per_slab, slabs, row_tiles; };
-fwd_plan plan_fwd(int N, int K) {
-    fwd_plan p;
-    p.chunks = (K + SWEEP_KT - 1) / SWEEP_KT;
-    p.row_tiles = (N + FWD_RT - 1) / FWD_RT;
-    int slabs = (SWEEP_TARGET_BLOCKS + p.row_tiles - 1) / p.row_tiles;
-    if (slabs > p.chunks) slabs = p.chunks;
-    if (slabs < 1) slabs = 1;
-    p.chunks_per_slab = (p.chunks + slabs - 1) / slabs;
-    p.slabs = (p.chunks + p.chunks_per_slab - 1) / p.chunks_per_slab;
-    return p;
-}
+vpk_param_store* store_of(const vpk_handle* h) { return h && h->train ? &h->train->ps : nullptr; }
 
 template <int NB>
-void launch_fwd(hipStream_t st, bool vec, const fwd_plan& p, const float* W, const float* X, int B, int N, int K, float* partial) {
+void launch_fwd(hipStream_t st, bool vec, const FwdPlan& p, const float* W, const float* X, int B, int N, int K, float* partial) {
     const dim3 grid(p.slabs, p.row_tiles);
     if (vec) train_fwd<NB, true><<<grid, 256, 0, st>>>(W, X, B, N, K, p.chunks, p.chunks_per_slab, partial);
     else train_fwd<NB, false><<<grid, 256, 0, st>>>(W, X, B, N, K, p.chunks, p.chunks_per_slab, partial);
@@ -367,31 +336,31 @@ void launch_fwd(hipStream_t st, bool vec, const fwd_plan& p, const float* W, con
 
 void forward_layer(hipStream_t st, const float* W, const float* bias, const float* X, int B, int N, int K, float* partial,
                    float* A, float* D, const uint8_t* mask, float scale, int relu) {
-    const bool vec = (K % 4 == 0) && aligned16(W) && aligned16(X);
-    const fwd_plan p = plan_fwd(N, K);
-    if (B <= 8) launch_fwd<8>(st, vec, p, W, X, B, N, K, partial);
+    const bool vec = vec_ok(K, {W, X});
+    const FwdPlan p = plan_fwd(N, K);
+    if (batch_nb(B) == 8) launch_fwd<8>(st, vec, p, W, X, B, N, K, partial);
     else launch_fwd<TRAIN_MAX_B>(st, vec, p, W, X, B, N, K, partial);
-    const size_t bn = (size_t)B * N;
-    train_fwd_finish<<<(unsigned)((bn + 255) / 256), 256, 0, st>>>(partial, p.slabs, B, N, bias, A, D, mask, scale, relu);
+    train_fwd_finish<<<blocks_of((size_t)B * N), 256, 0, st>>>(partial, p.slabs, B, N, bias, A, D, mask, scale, relu);
 }
 
 template <int NB, bool DX>
 void launch_sweep(hipStream_t st, bool vec, float* W, float* V, const float* dY, const float* Xin, int B, int N, int K,
                   float* partial, float lr, float decay, float mu) {
-    const int rt = sweep_rt(N, K);
-    const dim3 grid((K + SWEEP_KT - 1) / SWEEP_KT, (N + rt - 1) / rt);
-    if (vec) train_sweep<NB, true, DX><<<grid, 256, 0, st>>>(W, V, dY, Xin, B, N, K, rt, partial, lr, decay, mu);
-    else train_sweep<NB, false, DX><<<grid, 256, 0, st>>>(W, V, dY, Xin, B, N, K, rt, partial, lr, decay, mu);
+    const SweepPlan p = plan_sweep(N, K);
+    const dim3 grid(p.col_tiles, p.tiles);
+    if (vec) train_sweep<NB, true, DX><<<grid, 256, 0, st>>>(W, V, dY, Xin, B, N, K, p.rt, partial, lr, decay, mu);
+    else train_sweep<NB, false, DX><<<grid, 256, 0, st>>>(W, V, dY, Xin, B, N, K, p.rt, partial, lr, decay, mu);
 }
 
+// partial null: the sweep without its dX
 void sweep_layer(hipStream_t st, float* W, float* V, const float* dY, const float* Xin, int B, int N, int K, float* partial,
                  float lr, float decay, float mu) {
-    const bool vec = (K % 4 == 0) && aligned16(W) && aligned16(V) && aligned16(Xin) && (!partial || aligned16(partial));
+    const bool vec = vec_ok(K, {W, V, Xin, partial});
     if (partial) {
-        if (B <= 8) launch_sweep<8, true>(st, vec, W, V, dY, Xin, B, N, K, partial, lr, decay, mu);
+        if (batch_nb(B) == 8) launch_sweep<8, true>(st, vec, W, V, dY, Xin, B, N, K, partial, lr, decay, mu);
         else launch_sweep<TRAIN_MAX_B, true>(st, vec, W, V, dY, Xin, B, N, K, partial, lr, decay, mu);
     } else {
-        if (B <= 8) launch_sweep<8, false>(st, vec, W, V, dY, Xin, B, N, K, nullptr, lr, decay, mu);
+        if (batch_nb(B) == 8) launch_sweep<8, false>(st, vec, W, V, dY, Xin, B, N, K, nullptr, lr, decay, mu);
         else launch_sweep<TRAIN_MAX_B, false>(st, vec, W, V, dY, Xin, B, N, K, nullptr, lr, decay, mu);
     }
 }
@@ -399,10 +368,10 @@ void sweep_layer(hipStream_t st, float* W, float* V, const float* dY, const floa
 // the forward of B <= TRAIN_MAX_B rows into the state's activations; training: with the masks in s->m6 / s->m7
 void forward(vpk_handle* h, vpk_train_state* s, const float* X, int B, bool training) {
     const int I = s->dims[0], H6 = s->dims[1], H7 = s->dims[2], O = s->dims[3];
-    const float scale = training ? 1.0f / (1.0f - s->p.dropout_ratio) : 1.0f;
-    forward_layer(h->stream, s->W[0], s->b[0], X, B, H6, I, s->fpartial, s->a6, s->d6, training ? s->m6 : nullptr, scale, 1);
-    forward_layer(h->stream, s->W[1], s->b[1], s->d6, B, H7, H6, s->fpartial, s->a7, s->d7, training ? s->m7 : nullptr, scale, 1);
-    forward_layer(h->stream, s->W[2], s->b[2], s->d7, B, O, H7, s->fpartial, s->z, nullptr, nullptr, 1.0f, 0);
+    const float scale = training ? 1.0f / (1.0f - s->ps.p.dropout_ratio) : 1.0f;
+    forward_layer(h->stream, s->W(0), s->b(0), X, B, H6, I, s->fpartial, s->a6, s->d6, training ? s->m6 : nullptr, scale, 1);
+    forward_layer(h->stream, s->W(1), s->b(1), s->d6, B, H7, H6, s->fpartial, s->a7, s->d7, training ? s->m7 : nullptr, scale, 1);
+    forward_layer(h->stream, s->W(2), s->b(2), s->d7, B, O, H7, s->fpartial, s->z, nullptr, nullptr, 1.0f, 0);
 }
 
 }  // namespace
@@ -411,9 +380,7 @@ void vpk_train_free(vpk_handle* h) {
     vpk_train_state* s = h->train;
     if (!s) return;
     (void)hipStreamSynchronize(h->stream);
-    for (int l = 0; l < 3; ++l)
-        for (float* p : {s->W[l], s->V[l], s->b[l], s->vb[l]})
-            if (p) (void)hipFree(p);
+    s->ps.free();
     for (void* p : {(void*)s->a6, (void*)s->d6, (void*)s->a7, (void*)s->d7, (void*)s->z, (void*)s->dz, (void*)s->sig,
                     (void*)s->dA7, (void*)s->dA6, (void*)s->m6, (void*)s->m7, (void*)s->partial, (void*)s->fpartial,
                     (void*)s->xpartial})
@@ -447,17 +414,11 @@ int vpk_train_create(vpk_handle* h, const int32_t dims[4]) {
     vpk_train_state* s = new vpk_train_state();
     h->train = s;
     for (int i = 0; i < 4; ++i) s->dims[i] = dims[i];
-    vpk_train_default_params(&s->p);
-    hipError_t e = hipSuccess;
+    vpk_train_default_params(&s->ps.p);
+    const size_t mb = TRAIN_MAX_B, I = dims[0], H6 = dims[1], H7 = dims[2], O = dims[3];
+    const size_t counts[6] = {H6 * I, H6, H7 * H6, H7, O * H7, O};
+    hipError_t e = s->ps.alloc(counts, 6);
     auto alloc = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
-    for (int l = 0; l < 3; ++l) {
-        const size_t n = layer_n(s, l), wk = (size_t)n * layer_k(s, l);
-        alloc((void**)&s->W[l], wk * 4);
-        alloc((void**)&s->V[l], wk * 4);
-        alloc((void**)&s->b[l], n * 4);
-        alloc((void**)&s->vb[l], n * 4);
-    }
-    const size_t mb = TRAIN_MAX_B, H6 = dims[1], H7 = dims[2], O = dims[3];
     alloc((void**)&s->a6, mb * H6 * 4);
     alloc((void**)&s->d6, mb * H6 * 4);
     alloc((void**)&s->dA6, mb * H6 * 4);
@@ -469,14 +430,8 @@ int vpk_train_create(vpk_handle* h, const int32_t dims[4]) {
     alloc((void**)&s->z, mb * O * 4);
     alloc((void**)&s->dz, mb * O * 4);
     alloc((void**)&s->sig, mb * O * 4);
-    const size_t p7 = (size_t)sweep_tiles((int)H7, (int)H6) * mb * H6, p8 = (size_t)sweep_tiles((int)O, (int)H7) * mb * H7;
-    alloc((void**)&s->partial, (p7 > p8 ? p7 : p8) * 4);
-    size_t fp = 0;
-    for (int l = 0; l < 3; ++l) {
-        const size_t want = (size_t)plan_fwd(layer_n(s, l), layer_k(s, l)).slabs * mb * layer_n(s, l);
-        if (want > fp) fp = want;
-    }
-    alloc((void**)&s->fpartial, fp * 4);
+    alloc((void**)&s->partial, partial_bytes(s->dims));
+    alloc((void**)&s->fpartial, fpartial_bytes(s->dims));
     if (e != hipSuccess) {
         (void)hipGetLastError();
         vpk_train_free(h);
@@ -494,77 +449,35 @@ int vpk_train_destroy(vpk_handle* h) {
 int vpk_train_set_params(vpk_handle* h, const vpk_train_params* p) {
     if (!h || !p) return VPK_ERR_ARG;
     if (!h->train) return vpk_fail(h, VPK_ERR_STATE, "vpk_train_set_params: no trainer (vpk_train_create)");
-    if (!(p->dropout_ratio >= 0.0f && p->dropout_ratio < 1.0f) || p->stepsize < 1)
+    if (!head_params_ok(*p))
         return vpk_fail(h, VPK_ERR_ARG, "vpk_train_set_params: dropout_ratio must be in [0, 1) and stepsize >= 1");
-    h->train->p = *p;
+    h->train->ps.p = *p;
     return VPK_OK;
 }
 
-static int train_copy(vpk_handle* h, const char* who, void* const blobs[6], int momentum, int to_device) {
-    if (!h || !blobs) return VPK_ERR_ARG;
-    vpk_train_state* s = h->train;
-    if (!s) return vpk_fail(h, VPK_ERR_STATE, who);
-    for (int i = 0; i < 6; ++i)
-        if (!blobs[i]) return vpk_fail(h, VPK_ERR_ARG, who);
-    VPK_HIP(h, hipSetDevice(h->device));
-    VPK_HIP(h, hipStreamSynchronize(h->stream));
-    for (int l = 0; l < 3; ++l) {
-        const size_t n = layer_n(s, l), wk = n * layer_k(s, l);
-        float* dw = momentum ? s->V[l] : s->W[l];
-        float* db = momentum ? s->vb[l] : s->b[l];
-        if (to_device) {
-            VPK_HIP(h, hipMemcpy(dw, blobs[2 * l], wk * 4, hipMemcpyHostToDevice));
-            VPK_HIP(h, hipMemcpy(db, blobs[2 * l + 1], n * 4, hipMemcpyHostToDevice));
-        } else {
-            VPK_HIP(h, hipMemcpy(blobs[2 * l], dw, wk * 4, hipMemcpyDeviceToHost));
-            VPK_HIP(h, hipMemcpy(blobs[2 * l + 1], db, n * 4, hipMemcpyDeviceToHost));
-        }
-    }
-    return VPK_OK;
-}
-
+// a null list of blobs is VPK_ERR_ARG without a message, before anything else is looked at (train_store.hpp: silent_null)
 int vpk_train_load(vpk_handle* h, const void* const blobs[6]) {
-    const int rc = train_copy(h, "vpk_train_load", (void* const*)blobs, 0, 1);
-    if (rc) return rc;
-    vpk_train_state* s = h->train;
-    for (int l = 0; l < 3; ++l) {
-        const size_t n = layer_n(s, l), wk = n * layer_k(s, l);
-        VPK_HIP(h, hipMemsetAsync(s->V[l], 0, wk * 4, h->stream));
-        VPK_HIP(h, hipMemsetAsync(s->vb[l], 0, n * 4, h->stream));
-    }
-    VPK_HIP(h, hipStreamSynchronize(h->stream));
-    s->iteration = 0;
-    s->loaded = true;
-    return VPK_OK;
+    return vpk_store_load(h, store_of(h), "vpk_train_load", blobs, true);
 }
 
 int vpk_train_store(vpk_handle* h, void* const blobs_out[6]) {
-    if (h && h->train && !h->train->loaded) return vpk_fail(h, VPK_ERR_STATE, "vpk_train_store before vpk_train_load");
-    return train_copy(h, "vpk_train_store", blobs_out, 0, 0);
+    return vpk_store_copy(h, store_of(h), "vpk_train_store", blobs_out, false, false, true, true);
 }
 
 int vpk_train_load_momentum(vpk_handle* h, const void* const blobs[6]) {
-    if (h && h->train && !h->train->loaded) return vpk_fail(h, VPK_ERR_STATE, "vpk_train_load_momentum before vpk_train_load");
-    return train_copy(h, "vpk_train_load_momentum", (void* const*)blobs, 1, 1);
+    return vpk_store_copy(h, store_of(h), "vpk_train_load_momentum", (void* const*)blobs, true, true, true, true);
 }
 
 int vpk_train_store_momentum(vpk_handle* h, void* const blobs_out[6]) {
-    if (h && h->train && !h->train->loaded) return vpk_fail(h, VPK_ERR_STATE, "vpk_train_store_momentum before vpk_train_load");
-    return train_copy(h, "vpk_train_store_momentum", blobs_out, 1, 0);
+    return vpk_store_copy(h, store_of(h), "vpk_train_store_momentum", blobs_out, true, false, true, true);
 }
 
 int vpk_train_set_iteration(vpk_handle* h, long long iteration) {
-    if (!h) return VPK_ERR_ARG;
-    if (!h->train) return vpk_fail(h, VPK_ERR_STATE, "vpk_train_set_iteration: no trainer (vpk_train_create)");
-    if (iteration < 0) return vpk_fail(h, VPK_ERR_ARG, "vpk_train_set_iteration: iteration < 0");
-    h->train->iteration = iteration;
-    return VPK_OK;
+    return vpk_store_set_iteration(h, store_of(h), "vpk_train_set_iteration", iteration);
 }
 
 int vpk_train_get_iteration(const vpk_handle* h, long long* iteration_out) {
-    if (!h || !iteration_out || !h->train) return VPK_ERR_ARG;
-    *iteration_out = h->train->iteration;
-    return VPK_OK;
+    return vpk_store_get_iteration(store_of(h), iteration_out);
 }
 
 // the step; want_dx: vpk_train_step_dx, which also writes dX_out (the fc6 sweep's DX form and its partials)
@@ -572,7 +485,7 @@ static int train_step(vpk_handle* h, const float* X, const float* labels, int B,
                       unsigned long long seed, float* loss_out, float* sigout_out, bool want_dx, float* dX_out) {
     if (!h) return VPK_ERR_ARG;
     vpk_train_state* s = h->train;
-    if (!s || !s->loaded) return vpk_fail(h, VPK_ERR_STATE, "vpk_train_step before vpk_train_create / vpk_train_load");
+    if (!s || !s->ps.loaded) return vpk_fail(h, VPK_ERR_STATE, "vpk_train_step before vpk_train_create / vpk_train_load");
     if (B < 1 || B > TRAIN_MAX_B) return vpk_fail(h, VPK_ERR_LIMIT, "vpk_train_step: the batch must be 1..32");
     if (!X || !labels || (mask6 == nullptr) != (mask7 == nullptr) || (want_dx && !dX_out))
         return vpk_fail(h, VPK_ERR_ARG, "vpk_train_step: X, labels (and dX_out) are required, the masks come both or not at all");
@@ -580,45 +493,42 @@ static int train_step(vpk_handle* h, const float* X, const float* labels, int B,
     hipStream_t st = h->stream;
     const int I = s->dims[0], H6 = s->dims[1], H7 = s->dims[2], O = s->dims[3];
     if (want_dx) {
-        const int rc = vpk_reserve(h, (void**)&s->xpartial, &s->xpartial_bytes, (size_t)sweep_tiles(H6, I) * B * I * 4,
+        const int rc = vpk_reserve(h, (void**)&s->xpartial, &s->xpartial_bytes, xpartial_bytes(s->dims, B),
                                    "vpk_train_step_dx: fc6 dX partials");
         if (rc) return rc;
     }
-    const vpk_train_params& p = s->p;
+    const vpk_train_params& p = s->ps.p;
+    const long long iteration = s->ps.iteration;
     if (mask6) {
         VPK_HIP(h, hipMemcpyAsync(s->m6, mask6, (size_t)B * H6, hipMemcpyDeviceToDevice, st));
         VPK_HIP(h, hipMemcpyAsync(s->m7, mask7, (size_t)B * H7, hipMemcpyDeviceToDevice, st));
     } else {
         const uint32_t thr = vpk_train::mask_threshold(p.dropout_ratio);
-        train_masks<<<(unsigned)(((size_t)B * H6 + 255) / 256), 256, 0, st>>>(s->m6, B, H6, seed, (uint64_t)s->iteration, 6u, thr);
-        train_masks<<<(unsigned)(((size_t)B * H7 + 255) / 256), 256, 0, st>>>(s->m7, B, H7, seed, (uint64_t)s->iteration, 7u, thr);
+        train_masks<<<blocks_of((size_t)B * H6), 256, 0, st>>>(s->m6, B, H6, seed, (uint64_t)iteration, 6u, thr);
+        train_masks<<<blocks_of((size_t)B * H7), 256, 0, st>>>(s->m7, B, H7, seed, (uint64_t)iteration, 7u, thr);
     }
     forward(h, s, X, B, true);
     float* sig = sigout_out ? sigout_out : s->sig;
     train_loss<<<1, 256, 0, st>>>(s->z, labels, B * O, 1.0f / (float)B, sig, s->dz, loss_out, 0);
 
-    const float lr = vpk_train::learning_rate(p.base_lr, p.gamma, p.stepsize, s->iteration);
-    const float lr_w = lr * p.lr_mult_weight, dec_w = p.weight_decay * p.decay_mult_weight;
-    const float lr_b = lr * p.lr_mult_bias, dec_b = p.weight_decay * p.decay_mult_bias;
+    const Rates r = rates(p, iteration);
     const float scale = 1.0f / (1.0f - p.dropout_ratio);
     // fc8: dY = dz, input d7; its dX goes back through drop7 and relu7
-    sweep_layer(st, s->W[2], s->V[2], s->dz, s->d7, B, O, H7, s->partial, lr_w, dec_w, p.momentum);
-    train_bias<<<(O + 255) / 256, 256, 0, st>>>(s->b[2], s->vb[2], s->dz, B, O, lr_b, dec_b, p.momentum);
+    sweep_layer(st, s->W(2), s->V(2), s->dz, s->d7, B, O, H7, s->partial, r.lr_w, r.dec_w, r.mu);
+    train_bias<<<blocks_of(O), 256, 0, st>>>(s->b(2), s->vb(2), s->dz, B, O, r.lr_b, r.dec_b, r.mu);
     const size_t bk7 = (size_t)B * H7, bk6 = (size_t)B * H6;
-    train_dx_reduce<<<(unsigned)((bk7 + 255) / 256), 256, 0, st>>>(s->partial, sweep_tiles(O, H7), bk7, s->m7, s->a7, scale, s->dA7);
+    train_dx_reduce<<<blocks_of(bk7), 256, 0, st>>>(s->partial, plan_sweep(O, H7).tiles, bk7, s->m7, s->a7, scale, s->dA7);
     // fc7
-    sweep_layer(st, s->W[1], s->V[1], s->dA7, s->d6, B, H7, H6, s->partial, lr_w, dec_w, p.momentum);
-    train_bias<<<(H7 + 255) / 256, 256, 0, st>>>(s->b[1], s->vb[1], s->dA7, B, H7, lr_b, dec_b, p.momentum);
-    train_dx_reduce<<<(unsigned)((bk6 + 255) / 256), 256, 0, st>>>(s->partial, sweep_tiles(H7, H6), bk6, s->m6, s->a6, scale, s->dA6);
+    sweep_layer(st, s->W(1), s->V(1), s->dA7, s->d6, B, H7, H6, s->partial, r.lr_w, r.dec_w, r.mu);
+    train_bias<<<blocks_of(H7), 256, 0, st>>>(s->b(1), s->vb(1), s->dA7, B, H7, r.lr_b, r.dec_b, r.mu);
+    train_dx_reduce<<<blocks_of(bk6), 256, 0, st>>>(s->partial, plan_sweep(H7, H6).tiles, bk6, s->m6, s->a6, scale, s->dA6);
     // fc6: no dX while the conv stack below is frozen (vpk_train_step); vpk_train_step_dx hands it to the caller
-    sweep_layer(st, s->W[0], s->V[0], s->dA6, X, B, H6, I, want_dx ? s->xpartial : nullptr, lr_w, dec_w, p.momentum);
-    if (want_dx) {
-        const size_t bi = (size_t)B * I;
-        train_dx_sum<<<(unsigned)((bi + 255) / 256), 256, 0, st>>>(s->xpartial, sweep_tiles(H6, I), bi, dX_out);
-    }
-    train_bias<<<(H6 + 255) / 256, 256, 0, st>>>(s->b[0], s->vb[0], s->dA6, B, H6, lr_b, dec_b, p.momentum);
+    sweep_layer(st, s->W(0), s->V(0), s->dA6, X, B, H6, I, want_dx ? s->xpartial : nullptr, r.lr_w, r.dec_w, r.mu);
+    if (want_dx)
+        train_dx_sum<<<blocks_of((size_t)B * I), 256, 0, st>>>(s->xpartial, plan_sweep(H6, I).tiles, (size_t)B * I, dX_out);
+    train_bias<<<blocks_of(H6), 256, 0, st>>>(s->b(0), s->vb(0), s->dA6, B, H6, r.lr_b, r.dec_b, r.mu);
     VPK_HIP(h, hipGetLastError());
-    s->iteration += 1;
+    s->ps.iteration += 1;
     return VPK_OK;
 }
 
@@ -635,7 +545,7 @@ int vpk_train_step_dx(vpk_handle* h, const float* X, const float* labels, int B,
 int vpk_train_eval(vpk_handle* h, const float* X, const float* labels, int B, float* loss_out, float* sigout_out) {
     if (!h) return VPK_ERR_ARG;
     vpk_train_state* s = h->train;
-    if (!s || !s->loaded) return vpk_fail(h, VPK_ERR_STATE, "vpk_train_eval before vpk_train_create / vpk_train_load");
+    if (!s || !s->ps.loaded) return vpk_fail(h, VPK_ERR_STATE, "vpk_train_eval before vpk_train_create / vpk_train_load");
     if (B < 1 || !X || (labels && !loss_out)) return vpk_fail(h, VPK_ERR_ARG, "vpk_train_eval: B >= 1, X, and loss_out with labels");
     VPK_HIP(h, hipSetDevice(h->device));
     const int I = s->dims[0], O = s->dims[3];

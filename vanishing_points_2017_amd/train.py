@@ -11,6 +11,7 @@ C-ABI at any sizes, ``StackTrainer`` the two on one handle at any geometry (``Ne
 (vpk_trainset_* in csrc/vpk_trainset.hip, then vpk_sphere_raster): what train_val.prototxt:1-62 reads from LMDB, with
 ``Augment``'s affine maps of the image plane.  ``Solver`` is solver.prototxt's loop around a trainer and a set: iterations,
 test passes, displays, snapshots and resuming.  There is no CPU fallback."""
+import contextlib
 import ctypes
 
 import numpy as np
@@ -97,8 +98,127 @@ def label_maps(vps_or_angles, shape=(20, 20)):
     return out
 
 
-class Head(object):
+def _to_device(rt, x, dtype, shape):
+    """x (numpy or tensor) as a contiguous device tensor (B,) + shape of ``dtype``, ordered on the trainer's stream"""
+    t = rt.torch
+    shape = tuple(int(v) for v in shape)
+    if hasattr(x, "is_cuda"):
+        if x.is_cuda:
+            rt.stream.wait_stream(t.cuda.current_stream(x.device))
+    else:
+        x = t.from_numpy(np.ascontiguousarray(x))
+    with rt.on_stream():
+        x = x.to(device=rt.tdev, dtype=dtype).contiguous()
+    b, row = int(x.shape[0]), int(np.prod(shape))
+    if tuple(x.shape[1:]) != shape:
+        if x.numel() != b * row:
+            raise ValueError("expected %d values per row, got %d" % (row, x.numel() // max(b, 1)))
+        x = x.reshape((b,) + shape)
+    return x
+
+
+@contextlib.contextmanager
+def _on_stream(rt, *inputs):
+    """The body runs on the trainer's stream: what it allocates belongs to that stream and ``inputs`` (device tensors or
+    None) are kept alive for it; afterwards the caller's current stream waits for it, so the results are safe to use there.
+    Nothing of this happens after a body that raises."""
+    with rt.on_stream():
+        yield
+        for buf in inputs:
+            if buf is not None:
+                buf.record_stream(rt.stream)
+    rt.torch.cuda.current_stream(rt.tdev).wait_stream(rt.stream)
+
+
+def _blob_list(weights, names):
+    """[W, b, W, b, ...] of the layers ``names`` from a weight dict"""
+    return [a for name in names for a in weights[name][:2]]
+
+
+def _blob_dict(names, blobs):
+    return {name: (blobs[2 * k], blobs[2 * k + 1]) for k, name in enumerate(names)}
+
+
+def _response_maps(sigout):
+    return sigout.reshape(-1, 20, 20)
+
+
+def _save_caffemodel(self, path):
+    """Writes ``weights()`` as a caffemodel that evaluation.init_caffe reads (fc8 under the prototxt's name fc8_20x20)."""
+    w = self.weights()
+    layers = {}
+    for name, _ in cnn.LAYER_SHAPES:
+        layers["fc8_20x20" if name == "fc8" else name] = [w[name][0], w[name][1]]
+    caffe_io.write_caffemodel(path, layers)
+
+
+class _Params(object):
+    """What ``Head`` and ``ConvStack`` share: the master weights and momentum as host blobs of ``blob_shapes()``, the solver's
+    numbers and the iteration, through the C-ABI functions PREFIX + name.  ``_own``: close() closes the handle too."""
+
+    PREFIX = None
+
+    def _call(self, name, *args):
+        self.rt.check(getattr(self.rt.lib, self.PREFIX + name)(self.rt.h, *args))
+
+    def close(self):
+        if getattr(self, "rt", None) is not None:
+            getattr(self.rt.lib, self.PREFIX + "destroy")(self.rt.h)
+            if self._own:
+                self.rt.handle.close()
+            self.rt = None
+
+    def set_params(self, params):
+        self._call("set_params", ctypes.byref(params.as_struct()))
+        self.params = params
+
+    def _in(self, name, blobs):
+        shapes, blobs = self.blob_shapes(), list(blobs)
+        if len(blobs) != len(shapes):
+            raise ValueError("expected %d blobs, got %d" % (len(shapes), len(blobs)))
+        keep = [np.ascontiguousarray(a, dtype=np.float32) for a in blobs]
+        for a, shape in zip(keep, shapes):
+            if a.shape != shape:
+                raise ValueError("expected a blob of shape %s, got %s" % (shape, a.shape))
+        self._call(name, (ctypes.c_void_p * len(keep))(*[a.ctypes.data for a in keep]))
+
+    def _out(self, name):
+        out = [np.empty(shape, dtype=np.float32) for shape in self.blob_shapes()]
+        self._call(name, (ctypes.c_void_p * len(out))(*[a.ctypes.data for a in out]))
+        return out
+
+    def load(self, blobs):
+        """[W, b] of every layer in order (``blob_shapes()``), float32 on the host; zeroes the momentum and the iteration."""
+        self._in("load", blobs)
+
+    def store(self):
+        return self._out("store")
+
+    def load_momentum(self, blobs):
+        self._in("load_momentum", blobs)
+
+    def store_momentum(self):
+        return self._out("store_momentum")
+
+    @property
+    def iteration(self):
+        it = ctypes.c_longlong()
+        self._call("get_iteration", ctypes.byref(it))
+        return int(it.value)
+
+    @iteration.setter
+    def iteration(self, value):
+        self._call("set_iteration", int(value))
+
+    def synchronize(self):
+        self.rt.synchronize()
+
+
+class Head(_Params):
     """One trainer (vpk_train_create) of sizes ``dims`` = (I, H6, H7, O) on a handle and stream of its own."""
+
+    PREFIX = "vpk_train_"
+    _own = True
 
     def __init__(self, dims, device=0, params=None, seed=0, runtime=None):
         self.dims = tuple(int(d) for d in dims)
@@ -106,80 +226,15 @@ class Head(object):
             raise ValueError("dims must be (I, H6, H7, O)")
         self.rt = runtime if runtime is not None else Runtime(device)
         self.seed = int(seed)
-        arr = (ctypes.c_int32 * 4)(*self.dims)
-        self.rt.check(self.rt.lib.vpk_train_create(self.rt.h, arr))
+        self._call("create", (ctypes.c_int32 * 4)(*self.dims))
         self.params = params if params is not None else SolverParams()
         self.set_params(self.params)
-
-    def close(self):
-        if getattr(self, "rt", None) is not None:
-            self.rt.lib.vpk_train_destroy(self.rt.h)
-            self.rt.handle.close()
-            self.rt = None
 
     def shapes(self):
         i, h6, h7, o = self.dims
         return [(h6, i), (h6,), (h7, h6), (h7,), (o, h7), (o,)]
 
-    def set_params(self, params):
-        p = params.as_struct()
-        self.rt.check(self.rt.lib.vpk_train_set_params(self.rt.h, ctypes.byref(p)))
-        self.params = params
-
-    def _in(self, fn, blobs):
-        keep = []
-        for a, shape in zip(blobs, self.shapes()):
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            if a.shape != shape:
-                raise ValueError("expected a blob of shape %s, got %s" % (shape, a.shape))
-            keep.append(a)
-        arr = (ctypes.c_void_p * 6)(*[a.ctypes.data for a in keep])
-        self.rt.check(fn(self.rt.h, arr))
-
-    def _out(self, fn):
-        out = [np.empty(shape, dtype=np.float32) for shape in self.shapes()]
-        arr = (ctypes.c_void_p * 6)(*[a.ctypes.data for a in out])
-        self.rt.check(fn(self.rt.h, arr))
-        return out
-
-    def load(self, blobs):
-        """[W6, b6, W7, b7, W8, b8] float32 on the host; zeroes the momentum and the iteration."""
-        self._in(self.rt.lib.vpk_train_load, blobs)
-
-    def store(self):
-        return self._out(self.rt.lib.vpk_train_store)
-
-    def load_momentum(self, blobs):
-        self._in(self.rt.lib.vpk_train_load_momentum, blobs)
-
-    def store_momentum(self):
-        return self._out(self.rt.lib.vpk_train_store_momentum)
-
-    @property
-    def iteration(self):
-        it = ctypes.c_longlong()
-        self.rt.check(self.rt.lib.vpk_train_get_iteration(self.rt.h, ctypes.byref(it)))
-        return int(it.value)
-
-    @iteration.setter
-    def iteration(self, value):
-        self.rt.check(self.rt.lib.vpk_train_set_iteration(self.rt.h, int(value)))
-
-    def _dev(self, x, dtype, cols):
-        """x (numpy or tensor) as a contiguous (B, cols) device tensor of ``dtype``, ordered on the trainer's stream"""
-        rt = self.rt
-        t = rt.torch
-        if hasattr(x, "is_cuda"):
-            if x.is_cuda:
-                rt.stream.wait_stream(t.cuda.current_stream(x.device))
-        else:
-            x = t.from_numpy(np.ascontiguousarray(x))
-        with rt.on_stream():
-            x = x.to(device=rt.tdev, dtype=dtype)
-            x = (x.reshape(x.shape[0], -1) if x.shape[0] else x.reshape(0, cols)).contiguous()
-        if x.shape[1] != cols:
-            raise ValueError("expected %d values per row, got %d" % (cols, x.shape[1]))
-        return x
+    blob_shapes = shapes                 # [W6, b6, W7, b7, W8, b8]
 
     def step(self, features, labels, masks=None, want_dx=False):
         """One solver iteration on B <= 32 rows.  features (B, I), labels (B, O) in [0, 1]; masks: None (generated from the
@@ -189,31 +244,26 @@ class Head(object):
         rt = self.rt
         t = rt.torch
         i, h6, h7, o = self.dims
-        x = self._dev(features, t.float32, i)
-        lab = self._dev(labels, t.float32, o)
+        x = _to_device(rt, features, t.float32, (i,))
+        lab = _to_device(rt, labels, t.float32, (o,))
         b = int(x.shape[0])
         if lab.shape[0] != b:
             raise ValueError("features and labels differ in their batch")
         m6 = m7 = None
         if masks is not None and 1 <= b <= MAX_BATCH:
-            m6, m7 = self._dev(masks[0], t.uint8, h6), self._dev(masks[1], t.uint8, h7)
+            m6, m7 = _to_device(rt, masks[0], t.uint8, (h6,)), _to_device(rt, masks[1], t.uint8, (h7,))
             if m6.shape[0] != b or m7.shape[0] != b:
                 raise ValueError("masks and features differ in their batch")
-        with rt.on_stream():
+        with _on_stream(rt, x, lab, m6, m7):
             loss = t.empty((1,), dtype=t.float32, device=rt.tdev)
             sig = t.empty((b, o), dtype=t.float32, device=rt.tdev)
+            args = (rt.ptr(x), rt.ptr(lab), b, rt.ptr(m6), rt.ptr(m7), self.seed, rt.ptr(loss), rt.ptr(sig))
             dx = None
             if want_dx:
                 dx = t.empty((b, i), dtype=t.float32, device=rt.tdev)
-                rt.check(rt.lib.vpk_train_step_dx(rt.h, rt.ptr(x), rt.ptr(lab), b, rt.ptr(m6), rt.ptr(m7), self.seed,
-                                                  rt.ptr(loss), rt.ptr(sig), rt.ptr(dx)))
+                self._call("step_dx", *(args + (rt.ptr(dx),)))
             else:
-                rt.check(rt.lib.vpk_train_step(rt.h, rt.ptr(x), rt.ptr(lab), b, rt.ptr(m6), rt.ptr(m7), self.seed, rt.ptr(loss),
-                                               rt.ptr(sig)))
-            for buf in (x, lab, m6, m7):
-                if buf is not None:
-                    buf.record_stream(rt.stream)
-        t.cuda.current_stream(rt.tdev).wait_stream(rt.stream)      # the results are safe to use on the caller's stream
+                self._call("step", *args)
         return (loss[0], sig, dx) if want_dx else (loss[0], sig)
 
     def evaluate(self, features, labels=None):
@@ -221,23 +271,16 @@ class Head(object):
         rt = self.rt
         t = rt.torch
         i, _, _, o = self.dims
-        x = self._dev(features, t.float32, i)
-        lab = self._dev(labels, t.float32, o) if labels is not None else None
+        x = _to_device(rt, features, t.float32, (i,))
+        lab = _to_device(rt, labels, t.float32, (o,)) if labels is not None else None
         b = int(x.shape[0])
         if lab is not None and lab.shape[0] != b:
             raise ValueError("features and labels differ in their batch")
-        with rt.on_stream():
+        with _on_stream(rt, x, lab):
             loss = t.empty((1,), dtype=t.float32, device=rt.tdev) if lab is not None else None
             sig = t.empty((b, o), dtype=t.float32, device=rt.tdev)
-            rt.check(rt.lib.vpk_train_eval(rt.h, rt.ptr(x), rt.ptr(lab), b, rt.ptr(loss), rt.ptr(sig)))
-            for buf in (x, lab):
-                if buf is not None:
-                    buf.record_stream(rt.stream)
-        t.cuda.current_stream(rt.tdev).wait_stream(rt.stream)
+            self._call("eval", rt.ptr(x), rt.ptr(lab), b, rt.ptr(loss), rt.ptr(sig))
         return (loss[0] if loss is not None else None), sig
-
-    def synchronize(self):
-        self.rt.synchronize()
 
 
 class HeadTrainer(Head):
@@ -249,10 +292,7 @@ class HeadTrainer(Head):
         Head.__init__(self, NET_DIMS, device=device, params=params, seed=seed)
         self.net = net
         self._weights = dict(weights)
-        blobs = []
-        for name in HEAD_LAYERS:
-            blobs += [weights[name][0], weights[name][1]]
-        self.load(blobs)
+        self.load(_blob_list(weights, HEAD_LAYERS))
 
     def features(self, sphere):
         """pool5 of the rasters, flattened to (B, 57600) in Caffe's C x H x W order (a device tensor)."""
@@ -274,23 +314,13 @@ class HeadTrainer(Head):
         if labels is not None:
             labels = labels.reshape(labels.shape[0], -1)
         loss, sig = Head.evaluate(self, self._features_of(sphere_or_features), labels)
-        return loss, sig.reshape(-1, 20, 20)
+        return loss, _response_maps(sig)
 
     def weights(self):
         """The full weight dict: the conv layers as given, the head read back from the device."""
-        out = dict(self._weights)
-        blobs = self.store()
-        for k, name in enumerate(HEAD_LAYERS):
-            out[name] = (blobs[2 * k], blobs[2 * k + 1])
-        return out
+        return dict(self._weights, **_blob_dict(HEAD_LAYERS, self.store()))
 
-    def save_caffemodel(self, path):
-        """Writes ``weights()`` as a caffemodel that evaluation.init_caffe reads (fc8 under the prototxt's name fc8_20x20)."""
-        w = self.weights()
-        layers = {}
-        for name, _ in cnn.LAYER_SHAPES:
-            layers["fc8_20x20" if name == "fc8" else name] = [w[name][0], w[name][1]]
-        caffe_io.write_caffemodel(path, layers)
+    save_caffemodel = _save_caffemodel
 
 
 def conv_layer(out_channels, kernel, stride=1, pad=0, groups=1, relu=True):
@@ -334,9 +364,11 @@ def stack_shapes(in_shape, layers):
     return out
 
 
-class ConvStack(object):
+class ConvStack(_Params):
     """One conv trainer (vpk_convtrain_create) on ``in_shape`` = (C, H, W) and ``layers`` (conv_layer / lrn_layer /
     pool_layer descriptors), on a handle and stream of its own or on ``runtime``'s."""
+
+    PREFIX = "vpk_convtrain_"
 
     def __init__(self, in_shape, layers, device=0, params=None, runtime=None):
         self.in_shape = tuple(int(v) for v in in_shape)
@@ -345,17 +377,10 @@ class ConvStack(object):
         self._own = runtime is None
         arr = (_lib.StackLayer * len(self.layers))(*self.layers)
         c, h, w = self.in_shape
-        self.rt.check(self.rt.lib.vpk_convtrain_create(self.rt.h, c, h, w, arr, len(self.layers)))
+        self._call("create", c, h, w, arr, len(self.layers))
         self.shapes = stack_shapes(self.in_shape, self.layers)
         self.batch = 0                       # of the last forward
         self.set_params(params if params is not None else SolverParams())
-
-    def close(self):
-        if getattr(self, "rt", None) is not None:
-            self.rt.lib.vpk_convtrain_destroy(self.rt.h)
-            if self._own:
-                self.rt.handle.close()
-            self.rt = None
 
     def blob_shapes(self):
         """[(OC, C / groups, K, K), (OC,)] per CONV layer, in stack order"""
@@ -366,82 +391,17 @@ class ConvStack(object):
             c = shape[0]
         return out
 
-    def set_params(self, params):
-        p = params.as_struct()
-        self.rt.check(self.rt.lib.vpk_convtrain_set_params(self.rt.h, ctypes.byref(p)))
-        self.params = params
-
-    def _in(self, fn, blobs):
-        shapes = self.blob_shapes()
-        blobs = list(blobs)
-        if len(blobs) != len(shapes):
-            raise ValueError("expected %d blobs, got %d" % (len(shapes), len(blobs)))
-        keep = []
-        for a, shape in zip(blobs, shapes):
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            if a.shape != shape:
-                raise ValueError("expected a blob of shape %s, got %s" % (shape, a.shape))
-            keep.append(a)
-        arr = (ctypes.c_void_p * len(keep))(*[a.ctypes.data for a in keep])
-        self.rt.check(fn(self.rt.h, arr))
-
-    def _out(self, fn):
-        out = [np.empty(shape, dtype=np.float32) for shape in self.blob_shapes()]
-        arr = (ctypes.c_void_p * len(out))(*[a.ctypes.data for a in out])
-        self.rt.check(fn(self.rt.h, arr))
-        return out
-
-    def load(self, blobs):
-        """[W, b] of every CONV layer in stack order, float32 on the host; zeroes the momentum and the iteration."""
-        self._in(self.rt.lib.vpk_convtrain_load, blobs)
-
-    def store(self):
-        return self._out(self.rt.lib.vpk_convtrain_store)
-
-    def load_momentum(self, blobs):
-        self._in(self.rt.lib.vpk_convtrain_load_momentum, blobs)
-
-    def store_momentum(self):
-        return self._out(self.rt.lib.vpk_convtrain_store_momentum)
-
-    @property
-    def iteration(self):
-        it = ctypes.c_longlong()
-        self.rt.check(self.rt.lib.vpk_convtrain_get_iteration(self.rt.h, ctypes.byref(it)))
-        return int(it.value)
-
-    @iteration.setter
-    def iteration(self, value):
-        self.rt.check(self.rt.lib.vpk_convtrain_set_iteration(self.rt.h, int(value)))
-
-    def _dev(self, x, shape):
-        """x (numpy or tensor) as a contiguous float32 device tensor (B,) + shape, ordered on the trainer's stream"""
-        rt = self.rt
-        t = rt.torch
-        if hasattr(x, "is_cuda"):
-            if x.is_cuda:
-                rt.stream.wait_stream(t.cuda.current_stream(x.device))
-        else:
-            x = t.from_numpy(np.ascontiguousarray(x))
-        with rt.on_stream():
-            x = x.to(device=rt.tdev, dtype=t.float32).contiguous()
-        if tuple(x.shape[1:]) != tuple(shape):
-            x = x.reshape((x.shape[0],) + tuple(shape)) if x.shape[0] else x.reshape((0,) + tuple(shape))
-        return x
-
     def forward(self, x):
         """The stack's forward on (B, C, H, W), 1 <= B <= 32; returns the last blob (B, C', H', W') as a device tensor.  Every
         layer's blobs stay in the library until the next forward (``read``)."""
         rt = self.rt
         t = rt.torch
-        x = self._dev(x, self.in_shape)
+        x = _to_device(rt, x, t.float32, self.in_shape)
         b = int(x.shape[0])
-        with rt.on_stream():
+        with _on_stream(rt, x):
             top = t.empty((b,) + self.shapes[-1], dtype=t.float32, device=rt.tdev)
-            rt.check(rt.lib.vpk_convtrain_forward(rt.h, rt.ptr(x), b, rt.ptr(top)))
-            x.record_stream(rt.stream)
-        self.batch = b
-        t.cuda.current_stream(rt.tdev).wait_stream(rt.stream)
+            self._call("forward", rt.ptr(x), b, rt.ptr(top))
+            self.batch = b
         return top
 
     def backward(self, d_top, want_dx=False):
@@ -449,14 +409,12 @@ class ConvStack(object):
         layer.  Returns the gradient with respect to the input with ``want_dx``, else None (and then it is not computed)."""
         rt = self.rt
         t = rt.torch
-        d = self._dev(d_top, self.shapes[-1])
+        d = _to_device(rt, d_top, t.float32, self.shapes[-1])
         if self.batch and d.shape[0] != self.batch:
             raise ValueError("d_top has %d images, the forward had %d" % (d.shape[0], self.batch))
-        with rt.on_stream():
+        with _on_stream(rt, d):
             dx = t.empty((self.batch,) + self.in_shape, dtype=t.float32, device=rt.tdev) if want_dx else None
-            rt.check(rt.lib.vpk_convtrain_backward(rt.h, rt.ptr(d), rt.ptr(dx)))
-            d.record_stream(rt.stream)
-        t.cuda.current_stream(rt.tdev).wait_stream(rt.stream)
+            self._call("backward", rt.ptr(d), rt.ptr(dx))
         return dx
 
     def read(self, layer, kind="output"):
@@ -467,14 +425,10 @@ class ConvStack(object):
         t = rt.torch
         code = {"output": _lib.BLOB_OUTPUT, "index": _lib.BLOB_POOL_INDEX, "gradient": _lib.BLOB_GRADIENT,
                 "scale": _lib.BLOB_LRN_SCALE}[kind]
-        with rt.on_stream():
+        with _on_stream(rt):
             out = t.empty((self.batch,) + self.shapes[layer], dtype=t.int32 if kind == "index" else t.float32, device=rt.tdev)
-            rt.check(rt.lib.vpk_convtrain_read(rt.h, int(layer), code, rt.ptr(out)))
-        t.cuda.current_stream(rt.tdev).wait_stream(rt.stream)
+            self._call("read", int(layer), code, rt.ptr(out))
         return out
-
-    def synchronize(self):
-        self.rt.synchronize()
 
 
 class StackTrainer(object):
@@ -516,8 +470,8 @@ class StackTrainer(object):
             self.rt = None
 
     def set_params(self, params):
+        self.head.set_params(params)         # the stricter rule first: a refusal leaves both halves as they were
         self.stack.set_params(params)
-        self.head.set_params(params)
         self.params = params
 
     @property
@@ -533,7 +487,7 @@ class StackTrainer(object):
         self.stack.iteration = value
 
     def _data(self, x):
-        x = self.stack._dev(x, self.in_shape)
+        x = _to_device(self.rt, x, self.rt.torch.float32, self.in_shape)
         if self.mean is None:
             return x
         with self.rt.on_stream():
@@ -590,37 +544,20 @@ class NetTrainer(StackTrainer):
 
     def __init__(self, weights, mean, device=0, params=None, seed=0):
         shape, layers = net_stack()
-        conv, head = [], []
-        for name in CONV_LAYERS:
-            conv += [weights[name][0], weights[name][1]]
-        for name in HEAD_LAYERS:
-            head += [weights[name][0], weights[name][1]]
-        StackTrainer.__init__(self, shape, layers, NET_DIMS, (conv, head), mean=np.asarray(mean, dtype=np.float32).reshape(500, 500),
+        blobs = (_blob_list(weights, CONV_LAYERS), _blob_list(weights, HEAD_LAYERS))
+        StackTrainer.__init__(self, shape, layers, NET_DIMS, blobs, mean=np.asarray(mean, dtype=np.float32).reshape(500, 500),
                               device=device, params=params, seed=seed)
 
     def evaluate(self, rasters, labels=None):
         """The TEST phase of the whole net: (loss or None, response maps (B, 20, 20)); changes no weight."""
         loss, sig = StackTrainer.evaluate(self, rasters, labels)
-        return loss, sig.reshape(-1, 20, 20)
+        return loss, _response_maps(sig)
 
     def weights(self):
         """All eight layers read back from the device, as the dict ``cnn.Net`` takes."""
-        out = {}
-        blobs = self.stack.store()
-        for k, name in enumerate(CONV_LAYERS):
-            out[name] = (blobs[2 * k], blobs[2 * k + 1])
-        blobs = self.head.store()
-        for k, name in enumerate(HEAD_LAYERS):
-            out[name] = (blobs[2 * k], blobs[2 * k + 1])
-        return out
+        return dict(_blob_dict(CONV_LAYERS, self.stack.store()), **_blob_dict(HEAD_LAYERS, self.head.store()))
 
-    def save_caffemodel(self, path):
-        """Writes ``weights()`` as a caffemodel that evaluation.init_caffe reads (fc8 under the prototxt's name fc8_20x20)."""
-        w = self.weights()
-        layers = {}
-        for name, _ in cnn.LAYER_SHAPES:
-            layers["fc8_20x20" if name == "fc8" else name] = [w[name][0], w[name][1]]
-        caffe_io.write_caffemodel(path, layers)
+    save_caffemodel = _save_caffemodel
 
 
 # ---- the training set on the device, its augmentation and the solver's loop (C-ABI: vpk_trainset_* in csrc/vpk_trainset.hip) ----
@@ -809,7 +746,7 @@ class TrainSet(object):
             rasters = t.empty((b, self.size, self.size), dtype=t.uint8, device=rt.tdev)
         rt.stream.wait_stream(cur)
         vp = ctypes.c_void_p
-        with rt.on_stream():
+        with _on_stream(rt):
             rt.check(rt.lib.vpk_trainset_batch(
                 rt.h, rt.ptr(self.l), self.line_offsets.ctypes.data_as(vp), rt.ptr(self.vps), self.vp_offsets.ctypes.data_as(vp),
                 self.n, index.ctypes.data_as(vp), transforms.ctypes.data_as(vp) if transforms is not None else None, b,
@@ -821,7 +758,6 @@ class TrainSet(object):
             if flags.any():
                 raise _lib.VpkError("sphere raster: the kernel's buffers were too small for a line of example(s) %s: their "
                                     "rasters are incomplete" % index[np.nonzero(flags)[0]].tolist())
-        cur.wait_stream(rt.stream)
         return {"rasters": rasters, "labels": labels, "l_out": l_out, "vp_out": vp_out, "cell_out": cell_out, "index": index,
                 "offsets": offsets, "vp_offsets": vp_offsets, "transforms": transforms}
 
