@@ -131,6 +131,15 @@ class Net(object):
                   "conv4": 2 * 384 * 900 * 1728, "conv5": 2 * 256 * 900 * 1728, "fc6": 2 * 57600 * 4096,
                   "fc7": 2 * 4096 * 4096, "fc8": 2 * 4096 * 400}
 
+    # What the kernels launch per image, as executed_flop counts it.  Literals: tests/test_cnn_model.py holds the work items and K16
+    # steps to the totals of csrc/cnn_model.hpp, which the driver launches.
+    # conv1 by set_fusion mode: (tiles, waves, matrix instructions per wave, M x N x K of one, pipe) -- 168 tiles x 12 waves x 72
+    # v_mfma_f32_16x16x32_bf16 (cnn_conv1_pieces.hpp) / x 48 v_mfma_f32_16x16x32_f16 / 168 tiles x 8 waves x 186 v_mfma_f32_16x16x4_f32
+    EXEC_CONV1 = {3: (168, 12, 72, 16 * 16 * 32, "bf16"), 4: (168, 12, 48, 16 * 16 * 32, "f16"), 1: (168, 8, 186, 16 * 16 * 4, "f32")}
+    # fp16 pairs: tiles of 128 channels x 4 rows (conv4: 64 x 8) x 32 columns: (groups x row tiles x column tiles x channel tiles, K16 steps)
+    EXEC_PAIRS = {"conv2": (2 * 16 * 2 * 1, 75), "conv3": (1 * 8 * 1 * 3, 16 * 9), "conv4": (2 * 4 * 1 * 3, 12 * 9), "conv5": (2 * 8 * 1 * 1, 12 * 9)}
+    EXEC_TRIPLES_CONV2 = (64, 75)      # conv2 on bf16 triples: 64 tiles of 75 K16 steps
+
     @classmethod
     def executed_flop(cls, layer, fusion=3, precision=0, algorithm=4, batch=102):
         """(matrix-core flops the kernels EXECUTE for `layer` per image, which pipe: "f32" or "bf16") under a setting -- tile padding,
@@ -138,22 +147,19 @@ class Net(object):
         included; the roofline's numerator.  Pipes: "f32", "bf16", "f16" (the last two: the same dense peak)."""
         alg = cls.LAYER_FLOP[layer]
         if layer == "conv1":
-            if fusion == 3:      # 168 tiles x 12 waves x 72 v_mfma_f32_16x16x32_bf16 (cnn_conv1_pieces.hpp)
-                return 168 * 12 * 72 * 2.0 * 16 * 16 * 32, "bf16"
-            if fusion == 4:      # ... x 48 v_mfma_f32_16x16x32_f16
-                return 168 * 12 * 48 * 2.0 * 16 * 16 * 32, "f16"
-            if fusion == 1:      # 168 tiles x 8 waves x 186 v_mfma_f32_16x16x4_f32
-                return 168 * 8 * 186 * 2.0 * 16 * 16 * 4, "f32"
+            if fusion in cls.EXEC_CONV1:
+                tiles, waves, mfmas, shape, pipe = cls.EXEC_CONV1[fusion]
+                return tiles * waves * mfmas * 2.0 * shape, pipe
             return alg * 128.0 / 121.0, "f32"
         if layer in ("conv2", "conv3", "conv4", "conv5"):
             if precision == 1:
                 return 6.0 * alg, "bf16"
-            if algorithm == 4:      # fp16 pairs: tiles of 128 channels x 4 rows (conv4: 64 x 8) x 32 columns, 4 waves x 12 v_mfma_f32_32x32x16_f16 per K16 step
-                tiles, steps = {"conv2": (2 * 16 * 2 * 1, 75), "conv3": (1 * 8 * 1 * 3, 16 * 9), "conv4": (2 * 4 * 1 * 3, 12 * 9),
-                                "conv5": (2 * 8 * 1 * 1, 12 * 9)}[layer]       # (groups x row tiles x column tiles x channel tiles, K16 steps)
+            if algorithm == 4:      # 4 waves x 12 v_mfma_f32_32x32x16_f16 per K16 step
+                tiles, steps = cls.EXEC_PAIRS[layer]
                 return tiles * steps * 4 * 12 * 2.0 * 32 * 32 * 16, "f16"
-            if layer == "conv2" and algorithm >= 2:      # 64 tiles x 4 waves x 75 steps x 24 v_mfma_f32_32x32x16_bf16
-                return 64 * 4 * 75 * 24 * 2.0 * 32 * 32 * 16, "bf16"
+            if layer == "conv2" and algorithm >= 2:      # 4 waves x 24 v_mfma_f32_32x32x16_bf16 per K16 step
+                tiles, steps = cls.EXEC_TRIPLES_CONV2
+                return tiles * 4 * steps * 24 * 2.0 * 32 * 32 * 16, "bf16"
             if algorithm >= 1:
                 return alg * (36.0 / 100.0 if layer == "conv2" else 16.0 / 36.0), "f32"
             return alg, "f32"

@@ -20,7 +20,6 @@ namespace {
 constexpr int CAL_N = 6;
 constexpr int CAL_LAYER[CAL_N] = {1, 2, 3, 4, 5, 6};          // conv2, conv3, conv4, conv5, fc6, fc7
 constexpr int CAL_TAP[CAL_N] = {1, 3, 4, 5, 7, 8};            // taps of their inputs: pool1, pool2, conv3, conv4, pool5, fc6
-constexpr size_t CAL_SIZE[CAL_N] = {A_POOL1, A_POOL2, A_CONV3, A_CONV4, A_POOL5, A_FC6};
 constexpr int CAL_CHUNK = 8;                                   // rasters per calibration forward
 
 // max |x| as the bit pattern of a non-negative float (ordered like unsigned integers; a NaN's pattern is above infinity's)
@@ -72,32 +71,28 @@ float scale_for_maximum(float m) {
 // the six blob maxima over n rasters on the device
 int blob_maxima(vpk_handle* h, const uint8_t* d_imgs, int n, float mx[CAL_N]) {
     vpk_cnn_state* S = h->cnn;
-    float *d_out = nullptr, *d_tap = nullptr;
-    unsigned* d_max = nullptr;
-    auto release = [&]() { (void)hipFree(d_out); (void)hipFree(d_tap); (void)hipFree(d_max); };
+    DeviceBuffer<float> d_out, d_tap;
+    DeviceBuffer<unsigned> d_max;
     const int chunk = n < CAL_CHUNK ? n : CAL_CHUNK;
-    if (hipMalloc((void**)&d_out, (size_t)chunk * 400 * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&d_tap, (size_t)chunk * A_POOL1 * sizeof(float)) != hipSuccess ||        // (the largest tapped blob)
-        hipMalloc((void**)&d_max, CAL_N * sizeof(unsigned)) != hipSuccess ||
-        hipMemsetAsync(d_max, 0, CAL_N * sizeof(unsigned), h->stream) != hipSuccess) {
-        release();
+    if (hipMalloc(d_out.out(), (size_t)chunk * OUTPUTS_PER_IMAGE * sizeof(float)) != hipSuccess ||
+        hipMalloc(d_tap.out(), (size_t)chunk * A_POOL1 * sizeof(float)) != hipSuccess ||        // (the largest tapped blob)
+        hipMalloc(d_max.out(), CAL_N * sizeof(unsigned)) != hipSuccess ||
+        hipMemsetAsync(d_max.p, 0, CAL_N * sizeof(unsigned), h->stream) != hipSuccess)
         return vpk_fail(h, VPK_ERR_HIP, "vpk_cnn_calibrate: buffers of the calibration forwards");
-    }
     CnnConfig direct = S->cfg;                   // the f32 direct kernels: they depend on no scale
     direct.algorithm = 0; direct.fusion = 1; direct.precision = 0; direct.profiling = false;
     int rc = VPK_OK;
     for (int b0 = 0; b0 < n && rc == VPK_OK; b0 += chunk) {
         const int nb = n - b0 < chunk ? n - b0 : chunk;
         for (int i = 0; i < CAL_N && rc == VPK_OK; ++i) {
-            rc = run_forward(h, direct, Images{d_imgs + (size_t)b0 * 500 * 500, false}, nb, d_out, CAL_TAP[i], d_tap, FwdCtl{S->range_word, nullptr, nullptr});
-            if (rc == VPK_OK) hipLaunchKernelGGL(absmax_kernel, dim3(256), dim3(256), 0, h->stream, d_tap, (size_t)nb * CAL_SIZE[i], d_max + i);
+            rc = run_forward(h, direct, Images{d_imgs + (size_t)b0 * IMAGE_PIXELS, false}, nb, d_out.p, CAL_TAP[i], d_tap.p, FwdCtl{S->range_word.p, nullptr, nullptr});
+            if (rc == VPK_OK) hipLaunchKernelGGL(absmax_kernel, dim3(256), dim3(256), 0, h->stream, (const float*)d_tap.p, (size_t)nb * TAP_FLOATS[CAL_TAP[i]], d_max.p + i);
         }
     }
     unsigned bits[CAL_N] = {};
     if (rc == VPK_OK && (hipStreamSynchronize(h->stream) != hipSuccess ||
-                         hipMemcpy(bits, d_max, sizeof(bits), hipMemcpyDeviceToHost) != hipSuccess))
+                         hipMemcpy(bits, d_max.p, sizeof(bits), hipMemcpyDeviceToHost) != hipSuccess))
         rc = vpk_fail(h, VPK_ERR_HIP, "vpk_cnn_calibrate: calibration forward failed");
-    release();
     for (int i = 0; i < CAL_N; ++i) memcpy(&mx[i], &bits[i], 4);
     return rc;
 }
@@ -105,21 +100,19 @@ int blob_maxima(vpk_handle* h, const uint8_t* d_imgs, int n, float mx[CAL_N]) {
 // rasters == nullptr: the built-in set
 int calibrate(vpk_handle* h, const uint8_t* rasters, int n) {
     vpk_cnn_state* S = h->cnn;
-    uint8_t* d_img = nullptr;
+    DeviceBuffer<uint8_t> d_img;
     if (!rasters) {
         std::vector<uint8_t> img;
         builtin_calibration_rasters(img);
-        n = (int)(img.size() / (500 * 500));
-        if (hipMalloc((void**)&d_img, img.size()) != hipSuccess ||
-            hipMemcpy(d_img, img.data(), img.size(), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d_img);
+        n = (int)(img.size() / IMAGE_PIXELS);
+        if (hipMalloc(d_img.out(), img.size()) != hipSuccess ||
+            hipMemcpy(d_img.p, img.data(), img.size(), hipMemcpyHostToDevice) != hipSuccess)
             return vpk_fail(h, VPK_ERR_HIP, "vpk_cnn_calibrate: the built-in calibration rasters");
-        }
-        rasters = d_img;
+        rasters = d_img.p;
     }
     float mx[CAL_N];
     const int rc = blob_maxima(h, rasters, n, mx);
-    (void)hipFree(d_img);
+    d_img.reset();
     if (rc != VPK_OK) return rc;
     for (int i = 0; i < CAL_N; ++i)
         if (!std::isfinite(mx[i]))

@@ -41,7 +41,6 @@ constexpr int C1B_PROWS = 36, C1B_PCOLS = 80;          // raw patch in LDS (pixe
 constexpr int C1B_LDW = C1B_PCOLS;                     // row stride of the raw patch in LDS (bf16 elements; 88 / 96 / 104 / 192 measured: no faster)
 constexpr int C1B_XS = C1B_PROWS * C1B_LDW;            // bf16 per patch buffer
 constexpr int C1B_STEPS = 6;                           // K steps of 32
-constexpr int C1B_PATCHES = C1_TR * C1_TC;             // 168 patch positions per image
 
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));

@@ -42,26 +42,7 @@
 namespace {
 
 constexpr int CP_THREADS = 256;            // four waves; TWO workgroups per CU (one's prologue / epilogue under the other's products)
-constexpr int CP_TC = 32;                       // columns of a tile (its rows: the kernel's NB)
-
-struct PieceDims {
-    int B;                                      // images
-    int Cg16, CGtot, Hp, Wp;                    // input: channel groups (of 16) per conv group / in the tensor; padded plane
-    int OC, OH, OW, groups;                     // OC = output channels per conv group
-    int KW, ntaps, ksteps;                      // kernel width; KH * KW; K16 steps per conv group (Cg16 * ntaps)
-    int mblocks;                                // 32-row blocks per conv group in the packed weights
-    int mtiles, rtiles, ctiles;                 // tiles per (image, conv group): output-channel tiles, row tiles, column tiles
-    int relu;
-    int OHp, OWp, opad;                         // f32 NCHW output planes
-    long long in_image;                         // bytes per image of the input tensor (planes of 16-byte words)
-    int o_cgtot, o_Hp, o_Wp, o_pad;             // the NEXT layer's piece planes (written instead of the f32 planes when the kernel gets them)
-    float o_ascale;                             //   and its activation scale
-    unsigned* range_word;                       //   and where an activation beyond fp16's range is reported (split2h_guard), as bit
-    unsigned range_bit;                         //   range_bit (the consuming layer's)
-    unsigned* img_range;                        //   and into the image's word of the forward's per-image flags (null: not kept)
-    const int* live;                            // recompute pass (vpk_cnn_set_range_policy): the device count of images, B is its upper bound
-    float oscale;                               // 1 / (weight scale x activation scale) of the fp16-pair operands (a power of two); 1 for bf16 pieces
-};
+// (PieceDims and a tile's 32 columns, CP_TC: cnn_model.hpp)
 
 // fp16 PAIRS (round 5): an f32 operand x is h0 + h1 with h0 = fp16(x), h1 = fp16(x - h0): 22 significand bits of its 24 (the
 // remainder is at most 2^-23 |x|), and of the four partial products h_i h_j (each EXACT in f32: 11 x 11 bits) the three with

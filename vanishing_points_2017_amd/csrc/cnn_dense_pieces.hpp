@@ -22,19 +22,9 @@
 namespace {
 
 constexpr int DP_THREADS = 512;
-constexpr int DP_BM = 256, DP_BN = 128;         // rows (outputs) x columns (images) of a tile
-constexpr int DP_CHUNK = 32;                    // k per chunk = two K16 steps
-template <int NP> constexpr int DP_STAGE = NP * 2 * 4 * 1024;   // bytes of one chunk's B fragments: [piece][step][column block][lane][8]
+// (DenseDims and the tile: DP_BM x DP_BN outputs x images, chunks of DP_CHUNK k, DP_STAGE bytes of B fragments each: cnn_model.hpp)
 constexpr int DP_NST = 3;
 constexpr int DP_FOLD = 8;                      // chunks per block sum
-
-struct DenseDims {
-    int N, K, OC;                               // images, inputs, outputs
-    int chunks, kparts, cpp;                    // K / 32; split-K parts; chunks per part
-    int mtiles, ntiles;
-    float wscale, oscale;                       // fp16 pairs (NP = 2): weights x wscale before the split; partials x oscale (powers of two)
-    const int* live = nullptr;                  // recompute pass (vpk_cnn_set_range_policy): the device count of images, N its upper bound
-};
 
 // X f32 [N][K] -> B fragments [column tile][chunk][piece][step][column block][lane][8] (columns >= N: zeros): NP = 3 bf16 triples,
 // NP = 2 fp16 pairs of ascale x (cnn_conv_pieces.hpp)

@@ -5,25 +5,13 @@
 #ifndef VPK_CNN_GEMM_F32_HPP_
 #define VPK_CNN_GEMM_F32_HPP_
 
+#include "cnn_model.hpp"   // ConvDims, BK, C1_*
+
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int BK = 16;          // K depth of one LDS stage
 constexpr int CONV_THREADS = 256;
-
-struct ConvDims {
-    int B, IC, Hp, Wp;          // input: IC = channels per group; Hp x Wp = PADDED plane (zero border = conv padding)
-    int OC, OH, OW;             // output (OC = channels per group)
-    int groups;
-    int K;                      // IC*KH*KW (unpadded)
-    int Kp;                     // K padded to a multiple of BK
-    int Mp;                     // OC padded to a multiple of BM
-    int N;                      // B*OH*OW
-    int ksplit;                 // split-K factor (dense layers); 1 = fused epilogue
-    int relu;
-    int OHp, OWp, opad;         // output plane layout: (oh, ow) is stored at (oh + opad, ow + opad) of an OHp x OWp plane
-};
 
 // --------------------------------------------------------------------------------------------
 // implicit-GEMM convolution / dense layer
@@ -74,12 +62,7 @@ __device__ __forceinline__ void dma4(unsigned voff, const void* sbase, unsigned 
 // goes to LDS (over the then idle stage buffers), is normalised in place and max-pooled to 3 x 8 outputs per
 // channel, and only those are written -- conv1's 0.59 GB output (B = 102) never exists.  Neighbouring patches
 // share one conv row / column (pooling windows overlap by one), i.e. 7/6 x 17/16 = 1.24x the MFMA work.
-constexpr int C1_PR = 7, C1_PC = 17;               // conv outputs per patch (rows x cols): 119 of the tile's 128 columns
-constexpr int C1_QR = 3, C1_QC = 8;                // pooled outputs per patch
-constexpr int C1_OUT = 123, C1_POOL = 61;          // conv1 / pool1 output size (deploy.prototxt:9-55)
-constexpr int C1_TR = (C1_POOL + C1_QR - 1) / C1_QR, C1_TC = (C1_POOL + C1_QC - 1) / C1_QC;   // 21 x 8 patches per image
-constexpr int C1_LD = 129;                         // row stride of the patch in LDS ([channel][column])
-constexpr int C1_PH = 4, C1_PW = 125;              // conv1 reads its input as 4 x 4 stride-4 phase planes of 125 x 125 (prep_input_kernel)
+// (the patch constants C1_*: cnn_model.hpp)
 
 template <int WAVES_M, int WAVES_N, int TM, int TN, bool DENSE, bool C1FUSE = false, int NST = 3, int WPC = 3>
 __global__ __launch_bounds__(CONV_THREADS, WPC) void conv_gemm_dma_kernel(ConvDims d, const float* __restrict__ in,

@@ -29,7 +29,7 @@ __global__ void prep_input_kernel(const Px* __restrict__ sphere, const float* __
 // Fused LRN (across channels, local_size 5, x * (1 + alpha/n * sum x^2)^-beta) + MAX pool 3x3 stride 2, ceil
 // mode with clipped windows (deploy.prototxt:34-55, 82-103): the normalised map (0.6 GB at B = 102 for
 // norm1) is never written to or re-read from HBM.
-constexpr int LRN_CCH = 16;   // channels per workgroup (plus a 2-channel halo on each side)
+// (LRN_CCH, cnn_model.hpp: channels per workgroup, plus a 2-channel halo on each side)
 // A workgroup owns TPH x TPW pooled outputs of 16 channels.
 //   1. the raw input patch ((2 TPH + 1) x (2 TPW + 1) pixels, 16 + 4 halo channels) goes to LDS;
 //   2. one thread per pixel walks the channels with a 5-deep register window and overwrites the patch in

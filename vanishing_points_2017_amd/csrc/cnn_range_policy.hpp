@@ -71,18 +71,18 @@ int recompute_flagged(vpk_handle* h, Images img, int nb, float* out, const unsig
     hipStream_t st = h->stream;
     size_t off_fca = 0;
     for (int i = 0; i < R_FCA; ++i) off_fca += (size_t)S->act_batch * REGION_FLOATS[i];
-    void* slots = S->act;                                                 // R_IN (region 0): 4 bytes per raster byte (one float image) of room
-    float* maps = S->act + off_fca;                                       // R_FCA: 4096 floats per image of room
-    hipLaunchKernelGGL(range_compact_kernel, dim3(1), dim3(1024), 0, st, img_range, nb, S->rc_list, S->rc_total);
+    void* slots = S->act.p;                                                 // R_IN (region 0): 4 bytes per raster byte (one float image) of room
+    float* maps = S->act.p + off_fca;                                       // R_FCA: 4096 floats per image of room
+    hipLaunchKernelGGL(range_compact_kernel, dim3(1), dim3(1024), 0, st, img_range, nb, S->rc_list.p, S->rc_total.p);
     if (img.f32)
-        hipLaunchKernelGGL(range_gather_kernel<float>, dim3(8, (unsigned)nb), dim3(256), 0, st, img.f(), S->rc_list, static_cast<float*>(slots));
+        hipLaunchKernelGGL(range_gather_kernel<float>, dim3(8, (unsigned)nb), dim3(256), 0, st, img.f(), S->rc_list.p, static_cast<float*>(slots));
     else
-        hipLaunchKernelGGL(range_gather_kernel<uint8_t>, dim3(8, (unsigned)nb), dim3(256), 0, st, img.u8(), S->rc_list, static_cast<uint8_t*>(slots));
+        hipLaunchKernelGGL(range_gather_kernel<uint8_t>, dim3(8, (unsigned)nb), dim3(256), 0, st, img.u8(), S->rc_list.p, static_cast<uint8_t*>(slots));
     CnnConfig exact = S->cfg;                    // exact operands, every kernel reads the device count (cnn_plan.hpp)
     exact.algorithm = 2; exact.fusion = 3; exact.precision = 0; exact.profiling = false;
-    const int rc = run_forward(h, exact, Images{slots, img.f32}, nb, maps, -1, nullptr, FwdCtl{S->range_word + 1, nullptr, S->rc_list});
+    const int rc = run_forward(h, exact, Images{slots, img.f32}, nb, maps, -1, nullptr, FwdCtl{S->range_word.p + 1, nullptr, S->rc_list.p});
     if (rc) return rc;
-    hipLaunchKernelGGL(range_scatter_kernel, dim3((unsigned)nb), dim3(128), 0, st, maps, S->rc_list, out);
+    hipLaunchKernelGGL(range_scatter_kernel, dim3((unsigned)nb), dim3(128), 0, st, maps, S->rc_list.p, out);
     VPK_HIP(h, hipGetLastError());
     return VPK_OK;
 }

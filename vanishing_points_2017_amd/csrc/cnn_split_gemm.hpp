@@ -32,18 +32,7 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
-struct SplitDims {
-    int B, Cg, Ctot, Hp, Wp;        // input: channels per group / in total; padded plane
-    int OC, OH, OW, groups;         // OC = output channels per group
-    int KW, ntaps, csteps, ksteps;  // kernel width; KH * KW; K16 steps per tap (Cg / 16); K16 steps in total (ntaps * csteps)
-    int mblocks;                    // 32-row blocks per group in the packed weights
-    int N;                          // B * OH * OW
-    int relu;
-    int OHp, OWp, opad;             // f32 NCHW output planes
-};
-
-constexpr int SG_BN = 256;          // columns per tile: 8 blocks of 32
-
+// (SplitDims and the tile's 256 columns, SG_BN: cnn_model.hpp)
 // f32 -> three bf16 pieces, each the round-to-nearest-even bf16 of what is left: x - p0 and (x - p0) - p1 are exact in
 // f32 and the last remainder has at most 8 significant bits, so p0 + p1 + p2 == x exactly.  Rounding (not truncating)
 // keeps |p1| <= 2^-8 |x| and |p2| <= 2^-16 |x|, which bounds the dropped products at 2^-24 |a b|.

@@ -28,20 +28,7 @@
 namespace {
 
 constexpr int WG_THREADS = 512;
-constexpr int WG_TB = 64;            // tiles (of 2 x 2 outputs) per workgroup tile
-constexpr int WG_OCB = 64;           // output channels per workgroup tile
-constexpr int WG_KC = 8;             // input channels per LDS stage
-constexpr int WG_TILES_PER_IMAGE = 15 * 15;
-
-struct WinoDims {
-    int IC, OC, groups;              // channels per group
-    int ctot_in, ctot_out;           // channels of the input / output blob
-    int tiles;                       // B * 225
-    int ocblocks;                    // OC / 64 per group
-    int chunks;                      // IC / 8
-    int OHp, OWp, opad;              // output planes: (oh, ow) at (oh + opad, ow + opad) of an OHp x OWp plane
-    int relu;
-};
+// (WinoDims, Wino5Dims and the workgroup tiles WG_TB, WG_OCB, WG_KC, WG_TILES_PER_IMAGE, W5_TB, W5_OCB, W5_KC, W5_TPI: cnn_model.hpp)
 
 // U[g][oc block][chunk][p][kc][64] from Caffe's OIHW weights (host, at load): U_p = (G g G^T)_p in float64, rounded once
 inline void winograd_weights(const float* w, int G, int OC, int IC, std::vector<float>& out) {
@@ -304,12 +291,8 @@ __global__ __launch_bounds__(WG_THREADS, 1) void conv3x3_winograd_kernel(WinoDim
 // tile row / column (outputs 60, "61") reads input rows / columns up to 65 of a 65-pixel plane: the index is clamped to
 // 64, which IS the zero border the missing pixel would hold.
 constexpr int W5_THREADS = 768;
-constexpr int W5_TB = 30;            // tiles per workgroup tile (of the 32 columns of an MFMA tile: see the transform's lane map)
 constexpr int W5_NB = 32;            // columns of the B operand
-constexpr int W5_OCB = 64;
-constexpr int W5_KC = 4;
 constexpr int W5_P = 36;
-constexpr int W5_TPI = 31 * 31;      // tiles per image (61 x 61 outputs)
 constexpr int W5_PLANE = 65 * 65;
 
 // U[g][oc block][chunk][p][kc][64] for conv2 (host, at load; float64, rounded once)
@@ -352,13 +335,6 @@ __device__ __forceinline__ void w5_bt(const float (&x)[6], float (&o)[6]) {
     o[4] = fmaf(2.f, a, -b);                                         // -2 x1 +   x2 + 2 x3 -   x4
     o[5] = fmaf(2.f, x[1] + x[5], fmaf(-3.f, b, -4.f * x[3]));       //  2 x1 + 3 x2 - 4 x3 - 3 x4 + 2 x5
 }
-
-struct Wino5Dims {
-    int IC, OC, groups, ctot_in, ctot_out;
-    int tiles;                       // B * 961
-    int ocblocks, chunks;
-    int relu;
-};
 
 __global__ __launch_bounds__(W5_THREADS, 1) void conv5x5_winograd_kernel(Wino5Dims d, const float* __restrict__ in,
                                                                          const float* __restrict__ U,

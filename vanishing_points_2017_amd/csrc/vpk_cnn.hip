@@ -17,7 +17,9 @@
 //                           the defaults: exact bf16 triples / scaled fp16 pairs of the f32 operands
 //   cnn_winograd.hpp        Winograd minimal filtering on the f32-input matrix cores
 //   cnn_calibrate.hpp, cnn_range_policy.hpp   activation scales of the fp16 pairs; exact recompute of images that leave their range
-// Activations live in HBM for the whole batch (cnn_topology.hpp: B x 96 x 123 x 123 fp32 is 0.6 GB at B = 102; 288 GB of HBM3E
+// Every number the host decides -- the kernels' dimension structs per layer and per batch, the work items of each launch, the arena -- is
+// cnn_model.hpp's, plain C++ that the CPU suite tests; load_model and run_forward ask it, pack, upload and launch.
+// Activations live in HBM for the whole batch (cnn_model.hpp: B x 96 x 123 x 123 fp32 is 0.6 GB at B = 102; 288 GB of HBM3E
 // makes chunking unnecessary up to B ~ 4000).
 #include "vpk_internal.hpp"
 
@@ -27,7 +29,7 @@
 #include <vector>
 
 #include "cnn_plan.hpp"
-#include "cnn_topology.hpp"
+#include "cnn_model.hpp"
 #include "cnn_gemm_f32.hpp"
 #include "cnn_conv1_direct.hpp"
 #include "cnn_norm_pool.hpp"
@@ -43,27 +45,42 @@ namespace {
 #include "cnn_dense_pieces.hpp"
 #include "cnn_winograd.hpp"
 
+// a device allocation owned by its holder: move-only, released with it
+template <typename T>
+struct DeviceBuffer {
+    T* p = nullptr;
+    DeviceBuffer() = default;
+    DeviceBuffer(DeviceBuffer&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DeviceBuffer& operator=(DeviceBuffer&& o) noexcept { if (this != &o) { reset(); p = o.p; o.p = nullptr; } return *this; }
+    ~DeviceBuffer() { reset(); }
+    void reset() { if (p) (void)hipFree(p); p = nullptr; }
+    void** out() { return (void**)&p; }     // for hipMalloc / vpk_reserve
+    operator T*() const { return p; }
+};
+
+// the dimension structs are cnn_model.hpp's for the layer; run_forward copies and patches them per batch
 struct Layer {
     ConvDims d;
-    float* wp = nullptr;     // packed weights
-    float* bias = nullptr;
-    unsigned* ktab = nullptr;   // im2col table (conv layers): byte offset of tap k inside the padded input planes
-    unsigned short* wsplit = nullptr;   // conv2..5: weights as three bf16 pieces in MFMA fragment order (cnn_split_gemm.hpp)
+    DeviceBuffer<float> wp;     // packed weights
+    DeviceBuffer<float> bias;
+    DeviceBuffer<unsigned> ktab;   // im2col table (conv layers): byte offset of tap k inside the padded input planes
+    DeviceBuffer<unsigned short> wsplit;   // conv2..5: weights as three bf16 pieces in MFMA fragment order (cnn_split_gemm.hpp)
     float ascale = CP_DEFAULT_ASCALE;   // conv2..5, fc6, fc7 on fp16 pairs: the power of two the layer's INPUT is multiplied by (calibrate())
     float hscale = 1.f;                 // conv2..5, fc6, fc7: the power of two the weights are multiplied by before the fp16 split (largest in [2^13, 2^14))
-    unsigned short* whalf = nullptr;    // conv2..5: weights as scaled fp16 pairs in the same order (cnn_conv_pieces.hpp, NP = 2)
-    PieceDims pdh;                      //            and the layer's dimensions for that path (own block padding, output scale)
+    DeviceBuffer<unsigned short> whalf;    // conv2..5: weights as scaled fp16 pairs in the same order (cnn_conv_pieces.hpp, NP = 2)
+    PieceDims pdh;                      //            and the layer's dimensions for that path (own block padding)
     SplitDims sd;
-    float* wino = nullptr;      // conv2..5: G g G^T in the chunk order of the Winograd kernels (cnn_winograd.hpp)
-    unsigned short* c1frag = nullptr;   // conv1: three bf16 pieces of every weight in MFMA fragment order (cnn_conv1_pieces.hpp)
-    unsigned short* c1half = nullptr;   // conv1: scaled fp16 pairs in the same order (c1scale: the power of two)
+    DeviceBuffer<float> wino;   // conv2..5: G g G^T in the chunk order of the Winograd kernels (cnn_winograd.hpp)
+    DeviceBuffer<unsigned short> c1frag;   // conv1: three bf16 pieces of every weight in MFMA fragment order (cnn_conv1_pieces.hpp)
+    DeviceBuffer<unsigned short> c1half;   // conv1: scaled fp16 pairs in the same order (c1scale: the power of two)
     float c1scale = 1.f;
-    float* c1map = nullptr;     // conv1: bias - conv1(mean), 123 x 123 x 96
+    DeviceBuffer<float> c1map;  // conv1: bias - conv1(mean), 123 x 123 x 96
     WinoDims wd;
     Wino5Dims wd5;
     PieceDims pd;               // conv2..5 on exact bf16 pieces from an LDS-resident patch (cnn_conv_pieces.hpp)
-    float* wraw = nullptr;      // fc6, fc7: the f32 weights in tile order (dense_tile_weights_kernel), streamed by dense_pieces_kernel (cnn_dense_pieces.hpp)
-    unsigned short* wpair = nullptr;   // fc6, fc7: the same weights as scaled fp16 pairs in A-fragment order (dense_pair_weights_kernel): the default's stream
+    DenseDims dd;               // fc6, fc7 on pieces (cnn_dense_pieces.hpp)
+    DeviceBuffer<float> wraw;   // fc6, fc7: the f32 weights in tile order (dense_tile_weights_kernel), streamed by dense_pieces_kernel
+    DeviceBuffer<unsigned short> wpair;   // fc6, fc7: the same weights as scaled fp16 pairs in A-fragment order (dense_pair_weights_kernel): the default's stream
 };
 
 }  // namespace
@@ -71,56 +88,37 @@ struct Layer {
 struct vpk_cnn_state {
     // the loaded model
     Layer L[8];              // conv1..5, fc6..8
-    float* mean = nullptr;
+    DeviceBuffer<float> mean;
     bool loaded = false;
     // how the layers are computed: the user's setting (vpk_cnn_set_precision / _algorithm / _fusion / _profiling, cnn_plan.hpp)
     CnnConfig cfg;
     // workspaces (grown on demand)
-    float* act = nullptr;              // the activation arena (cnn_topology.hpp)
+    DeviceBuffer<float> act;           // the activation arena (cnn_model.hpp)
     size_t act_bytes = 0;
     int act_batch = 0;
-    unsigned short* xfrag = nullptr;   // fc6's input as bf16 B fragments (dense_split_kernel)
+    DeviceBuffer<unsigned short> xfrag;   // fc6's input as bf16 B fragments (dense_split_kernel)
     size_t xfrag_bytes = 0;
     // value range of the fp16 pairs
-    unsigned* range_word = nullptr;    // bit li set when a scaled INPUT value of layer li reached fp16's range (split2h_guard);
+    DeviceBuffer<unsigned> range_word; // bit li set when a scaled INPUT value of layer li reached fp16's range (split2h_guard);
                                        // sticky until vpk_cnn_range_flags reads and clears it.  range_word[1]: where the pair pass
                                        // reports under RECOMPUTE_EXACT (its flagged images are recomputed, so nothing reaches word 0)
     int range_policy = 0;              // vpk_cnn_set_range_policy: 0 = RAISE, 1 = RECOMPUTE_EXACT
-    unsigned* img_range = nullptr;     // the last vpk_cnn_forward's per-image bits (image b at [b]), grown on demand
+    DeviceBuffer<unsigned> img_range;  // the last vpk_cnn_forward's per-image bits (image b at [b]), grown on demand
     size_t img_range_bytes = 0;
     int img_range_batch = 0;           // its batch (0: no forward yet)
-    int* rc_list = nullptr;            // recompute pass: [0] = device count of flagged images of the chunk, [1 ..] their indices in order
-    unsigned long long* rc_total = nullptr;   // images recomputed since vpk_cnn_recomputed last read it
+    DeviceBuffer<int> rc_list;         // recompute pass: [0] = device count of flagged images of the chunk, [1 ..] their indices in order
+    DeviceBuffer<unsigned long long> rc_total;   // images recomputed since vpk_cnn_recomputed last read it
     // optional per-layer timing (cfg.profiling): HIP events on the handle's stream
     static constexpr int EV_RING = 64;   // event sets of the last 64 profiled passes (vpk_cnn_mean_layer_ms)
     hipEvent_t ev[EV_RING][14] = {};
     long long ev_pass = 0;   // profiled passes recorded since profiling was switched on
     bool ev_ready = false;
     bool ev_valid = false;
+    __attribute__((visibility("hidden"))) ~vpk_cnn_state() = default;   // (only vpk_cnn_free deletes one: not an export of the library)
 };
 
-void vpk_cnn_free(vpk_handle* h) {
+void vpk_cnn_free(vpk_handle* h) {      // (the state's buffers go with it)
     if (!h->cnn) return;
-    for (auto& l : h->cnn->L) {
-        if (l.wp) (void)hipFree(l.wp);
-        if (l.bias) (void)hipFree(l.bias);
-        if (l.ktab) (void)hipFree(l.ktab);
-        if (l.wsplit) (void)hipFree(l.wsplit);
-        if (l.whalf) (void)hipFree(l.whalf);
-        if (l.wino) (void)hipFree(l.wino);
-        if (l.c1frag) (void)hipFree(l.c1frag);
-        if (l.c1half) (void)hipFree(l.c1half);
-        if (l.c1map) (void)hipFree(l.c1map);
-        if (l.wraw) (void)hipFree(l.wraw);
-        if (l.wpair) (void)hipFree(l.wpair);
-    }
-    if (h->cnn->mean) (void)hipFree(h->cnn->mean);
-    if (h->cnn->act) (void)hipFree(h->cnn->act);
-    if (h->cnn->xfrag) (void)hipFree(h->cnn->xfrag);
-    if (h->cnn->range_word) (void)hipFree(h->cnn->range_word);
-    if (h->cnn->img_range) (void)hipFree(h->cnn->img_range);
-    if (h->cnn->rc_list) (void)hipFree(h->cnn->rc_list);
-    if (h->cnn->rc_total) (void)hipFree(h->cnn->rc_total);
     if (h->cnn->ev_ready)
         for (auto& set : h->cnn->ev)
             for (auto& e : set) (void)hipEventDestroy(e);
@@ -133,10 +131,9 @@ namespace {
 template <typename KernelT>
 void launch_dma(vpk_handle* h, KernelT kernel, const ConvDims& d, int BM, const float* in, const Layer& l, float* out,
                 int stride, int* counter, int wpc = 3, const int* live = nullptr) {
-    long long ntiles = (d.N + 127) / 128;
-    long long total = (long long)d.groups * d.ksplit * ntiles * (d.Mp / BM);
+    const long long total = dma_total(d, BM);
     long long blocks = std::min<long long>(total, (long long)wpc * h->num_cu);   // wpc workgroups fit a CU (LDS, registers)
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(CONV_THREADS), 0, h->stream, d, in, l.wp, l.bias, l.ktab,
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(CONV_THREADS), 0, h->stream, d, in, l.wp.p, l.bias.p, l.ktab.p,
                        out, stride, counter, (int)total, live);
 }
 
@@ -153,7 +150,7 @@ struct Images {
     bool f32;
     const uint8_t* u8() const { return static_cast<const uint8_t*>(p); }
     const float* f() const { return static_cast<const float*>(p); }
-    Images at(size_t b) const { return Images{f32 ? (const void*)(f() + b * 250000) : (const void*)(u8() + b * 250000), f32}; }
+    Images at(size_t b) const { return Images{f32 ? (const void*)(f() + b * IMAGE_PIXELS) : (const void*)(u8() + b * IMAGE_PIXELS), f32}; }
 };
 
 // One forward of at most MAX_CHUNK images under `cfg`: the handle's setting, or the arithmetic an internal pass needs (the calibration
@@ -166,7 +163,7 @@ int run_forward(vpk_handle* h, const CnnConfig& cfg, Images img, int batch, floa
     const int* live = fc.live;
     if (batch > S->act_batch) {     // grow the arena; all borders (and everything else) start as zeros
         const size_t need = ((size_t)batch * arena_floats_per_image() + GUARD_FLOATS + CTR_FLOATS) * sizeof(float);
-        int rc = vpk_reserve(h, (void**)&S->act, &S->act_bytes, need, "hipMalloc(CNN activations)");
+        int rc = vpk_reserve(h, S->act.out(), &S->act_bytes, need, "hipMalloc(CNN activations)");
         if (rc) return rc;
         VPK_HIP(h, hipMemsetAsync(S->act, 0, need, st));
         S->act_batch = batch;
@@ -183,20 +180,16 @@ int run_forward(vpk_handle* h, const CnnConfig& cfg, Images img, int batch, floa
             VPK_HIP(h, hipMemcpyAsync(tap_out, src, per * batch * sizeof(float), hipMemcpyDeviceToDevice, st));
         return VPK_OK;
     };
-    auto ew_blocks = [](long long n) { return (unsigned)((n + 255) / 256); };
-    auto tapunpad = [&](int id, const float* src, int C, int H, int W, int pad) {
+    auto tapunpad = [&](int id, const float* src, int li) {       // the bordered planes that layer li reads
         if (tap == id && tap_out) {
-            const long long planes = (long long)batch * C;
-            hipLaunchKernelGGL(unpad_kernel, dim3(ew_blocks(planes * H * W)), dim3(256), 0, st, src, tap_out, planes, H, W,
-                               H + 2 * pad, W + 2 * pad, pad);
+            const Planes p = input_planes(li);
+            const long long planes = (long long)batch * p.C;
+            hipLaunchKernelGGL(unpad_kernel, dim3((unsigned)ew_blocks(planes * p.H * p.W)), dim3(EW_THREADS), 0, st, src, tap_out, planes,
+                               p.H, p.W, p.Hp, p.Wp, p.pad);
         }
     };
-    auto dims = [&](int li) {
-        ConvDims d = S->L[li].d;
-        d.B = batch;
-        d.N = batch * d.OH * d.OW;
-        return d;
-    };
+    auto dims = [&](int li) { return at_batch(S->L[li].d, batch); };
+    const Planes pool1 = input_planes(1), pool2 = input_planes(2);
     // profiling: 14 events per pass, one in front of conv1 and one behind each of the 13 slots of vpk_cnn_last_layer_ms (vpk.h);
     // a stage that covers several slots records all of their events when it ends
     int evi = 0;
@@ -209,65 +202,62 @@ int run_forward(vpk_handle* h, const CnnConfig& cfg, Images img, int batch, floa
 
     // ---- conv1 + relu1 + norm1 + pool1 -> pool1's planes with conv2's border of 2 (slots conv1, norm1, pool1) ----
     if (plan.prep_input) {          // uint8 raster (float image) - mean -> fp32 phase planes for the GEMM forms
+        const dim3 grid((unsigned)ew_blocks(IMAGE_PIXELS), batch);
         if (img.f32)
-            hipLaunchKernelGGL(prep_input_kernel<float>, dim3((500 * 500 + 255) / 256, batch), dim3(256), 0, st, img.f(), S->mean, R[R_IN],
-                               500 * 500);
+            hipLaunchKernelGGL(prep_input_kernel<float>, grid, dim3(EW_THREADS), 0, st, img.f(), S->mean.p, R[R_IN], (int)IMAGE_PIXELS);
         else
-            hipLaunchKernelGGL(prep_input_kernel<unsigned char>, dim3((500 * 500 + 255) / 256, batch), dim3(256), 0, st, img.u8(), S->mean,
-                               R[R_IN], 500 * 500);
+            hipLaunchKernelGGL(prep_input_kernel<unsigned char>, grid, dim3(EW_THREADS), 0, st, img.u8(), S->mean.p, R[R_IN], (int)IMAGE_PIXELS);
     }
     switch (plan.conv1) {
     case Conv1Impl::GEMM:           // separate kernels: the only form that writes the conv1 blob
         launch_dma(h, conv_gemm_dma_kernel<1, 4, 3, 1, false>, dims(0), 96, R[R_IN], S->L[0], R[R_CONV1], 1, ctr + 0);   // stride 1 over the phase planes
         mark(1);
         if ((rc = tapcopy(0, R[R_CONV1], A_CONV1))) return rc;
-        hipLaunchKernelGGL((lrn5_pool3s2_tiled_kernel<7, 16>), dim3((unsigned)(batch * ((96 + LRN_CCH - 1) / LRN_CCH) * 9 * 4)),
-                           dim3(256), 0, st, R[R_CONV1], R[R_POOL1], 96, 123, 123, 61, 61, 1e-4f, 0.75f, 65, 65, 2);
+        hipLaunchKernelGGL((lrn5_pool3s2_tiled_kernel<N1_TPH, N1_TPW>), dim3((unsigned)norm1_blocks(batch)), dim3(256), 0, st, R[R_CONV1],
+                           R[R_POOL1], TOPO[0].OC, TOPO[0].OH, TOPO[0].OW, pool1.H, pool1.W, 1e-4f, 0.75f, pool1.Hp, pool1.Wp, pool1.pad);
         mark(2);
         break;
     // the fused forms: 21 x 8 patches of 7 x 17 conv outputs per image, straight into pool1's planes
     case Conv1Impl::PIECES3:        // exact bf16 pieces / scaled fp16 pairs on the matrix cores (cnn_conv1_pieces.hpp)
     case Conv1Impl::PIECES2: {
         const int group = cfg.conv1_group;
-        const int total = C1B_PATCHES * ((batch + group - 1) / group);
+        const int total = (int)conv1_pieces_total(batch, group);
         // fp16 pairs downstream and pool1 not tapped: the pooling stage writes conv2's piece planes itself (no f32 pool1 blob)
         unsigned short* c2planes = plan.conv1_hands_planes ? reinterpret_cast<unsigned short*>(R[R_P6_2]) : nullptr;
         if (plan.conv1 == Conv1Impl::PIECES2)
             hipLaunchKernelGGL(conv1_pieces_kernel<2>, dim3((unsigned)std::min(total, h->num_cu)), dim3(C1B_THREADS), 0, st, img.u8(),
-                               S->L[0].c1half, S->L[0].c1map, R[R_POOL1], 65, 65, 2, batch, group, 1.f / S->L[0].c1scale, ctr + 0, total,
+                               S->L[0].c1half.p, S->L[0].c1map.p, R[R_POOL1], pool1.Hp, pool1.Wp, pool1.pad, batch, group, 1.f / S->L[0].c1scale, ctr + 0, total,
                                c2planes, S->L[1].ascale, fc.range_word, fc.img_range, live);
         else if (img.f32)               // float images: three pieces per pixel, six products per K step
             hipLaunchKernelGGL((conv1_pieces_kernel<3, float>), dim3((unsigned)std::min(total, h->num_cu)), dim3(C1B_THREADS), 0, st,
-                               img.f(), S->L[0].c1frag, S->L[0].c1map, R[R_POOL1], 65, 65, 2, batch, group, 1.f, ctr + 0, total,
+                               img.f(), S->L[0].c1frag.p, S->L[0].c1map.p, R[R_POOL1], pool1.Hp, pool1.Wp, pool1.pad, batch, group, 1.f, ctr + 0, total,
                                c2planes, S->L[1].ascale, fc.range_word, fc.img_range, live);
         else
             hipLaunchKernelGGL(conv1_pieces_kernel<3>, dim3((unsigned)std::min(total, h->num_cu)), dim3(C1B_THREADS), 0, st, img.u8(),
-                               S->L[0].c1frag, S->L[0].c1map, R[R_POOL1], 65, 65, 2, batch, group, 1.f, ctr + 0, total,
+                               S->L[0].c1frag.p, S->L[0].c1map.p, R[R_POOL1], pool1.Hp, pool1.Wp, pool1.pad, batch, group, 1.f, ctr + 0, total,
                                c2planes, S->L[1].ascale, fc.range_word, fc.img_range, live);
         mark(3);
         break;
     }
     case Conv1Impl::GEMM_FUSED: {   // the implicit-GEMM kernel with the fused epilogue (kept for comparison)
-        ConvDims df = dims(0);
-        df.N = batch * C1_TR * C1_TC * 128;           // one 128-column tile per patch
-        df.OHp = 65; df.OWp = 65; df.opad = 2;
-        launch_dma(h, conv_gemm_dma_kernel<1, 4, 3, 1, false, true>, df, 96, R[R_IN], S->L[0], R[R_POOL1], 1, ctr + 0);
+        launch_dma(h, conv_gemm_dma_kernel<1, 4, 3, 1, false, true>, conv1_fused_at_batch(S->L[0].d, batch), 96, R[R_IN], S->L[0], R[R_POOL1],
+                   1, ctr + 0);
         mark(3);
         break;
     }
     case Conv1Impl::DIRECT_F32: {   // reads the rasters itself (cnn_conv1_direct.hpp)
-        const int total = batch * C1_TR * C1_TC;
+        const int total = (int)conv1_direct_total(batch);
         if (img.f32)
             hipLaunchKernelGGL(conv1_direct_kernel<float>, dim3((unsigned)std::min(total, h->num_cu)), dim3(C1D_THREADS), 0, st, img.f(),
-                               S->mean, S->L[0].wp, S->L[0].bias, R[R_POOL1], 65, 65, 2, ctr + 0, total);
+                               S->mean.p, S->L[0].wp.p, S->L[0].bias.p, R[R_POOL1], pool1.Hp, pool1.Wp, pool1.pad, ctr + 0, total);
         else
             hipLaunchKernelGGL(conv1_direct_kernel<unsigned char>, dim3((unsigned)std::min(total, h->num_cu)), dim3(C1D_THREADS), 0, st,
-                               img.u8(), S->mean, S->L[0].wp, S->L[0].bias, R[R_POOL1], 65, 65, 2, ctr + 0, total);
+                               img.u8(), S->mean.p, S->L[0].wp.p, S->L[0].bias.p, R[R_POOL1], pool1.Hp, pool1.Wp, pool1.pad, ctr + 0, total);
         mark(3);
         break;
     }
     }
-    tapunpad(1, R[R_POOL1], 96, 61, 61, 2);
+    tapunpad(1, R[R_POOL1], 1);
 
     // ---- conv2 .. conv5 (+ relu): the launchers of the four forms, then conv_stage picks by the plan ----
     // (a 2-stage / 4-workgroups-per-CU build of the f32 GEMM, NST = 2, WPC = 4, was measured in round 2: conv2 +2 %,
@@ -276,9 +266,7 @@ int run_forward(vpk_handle* h, const CnnConfig& cfg, Images img, int batch, floa
     // src_split: the input already is in split format (written by the previous layer); dst_split: write that format
     auto conv_split = [&](int li, int tiling, const float* src, const unsigned short* src_split, void* dst, bool dst_split) {
         const Layer& l = S->L[li];
-        SplitDims sd = l.sd;
-        sd.B = batch;
-        sd.N = batch * sd.OH * sd.OW;
+        const SplitDims sd = at_batch(l.sd, batch);
         const unsigned short* sp = src_split;
         if (!sp) {
             unsigned short* cv = reinterpret_cast<unsigned short*>(R[R_SPLIT]);
@@ -286,37 +274,34 @@ int run_forward(vpk_handle* h, const CnnConfig& cfg, Images img, int batch, floa
                                (size_t)sd.Ctot * (sd.Wp + 1) * sizeof(float), st, src, cv, sd.Ctot, sd.Hp, sd.Wp);
             sp = cv;
         }
-        const int ntiles = (sd.N + SG_BN - 1) / SG_BN;
-        auto go = [&](auto kernel, int blk, int threads, int per_cu) {
-            const int total = sd.groups * ntiles * (sd.mblocks / blk);
-            hipLaunchKernelGGL(kernel, dim3((unsigned)std::min(total, per_cu * h->num_cu)), dim3(threads), 0, st, sd, sp, l.wsplit,
-                               l.bias, dst, ctr + li, total);
+        const int total = (int)split_total(sd, blocks_per_tile(li, false));     // 32-row blocks per tile: the kernels' WAVES_M x TM
+        auto go = [&](auto kernel, int threads, int per_cu) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)std::min(total, per_cu * h->num_cu)), dim3(threads), 0, st, sd, sp, l.wsplit.p,
+                               l.bias.p, dst, ctr + li, total);
         };
         if (sd.OC == 192) {
-            if (dst_split) go(conv_gemm_split_kernel<2, 4, 3, 3, 2, true>, 6, 512, 1);
-            else go(conv_gemm_split_kernel<2, 4, 3, 3, 2, false>, 6, 512, 1);
+            if (dst_split) go(conv_gemm_split_kernel<2, 4, 3, 3, 2, true>, 512, 1);
+            else go(conv_gemm_split_kernel<2, 4, 3, 3, 2, false>, 512, 1);
         } else if (tiling == 1) {       // two independent 4-wave workgroups per CU, two stages each
-            if (dst_split) go(conv_gemm_split_kernel<2, 2, 2, 2, 2, true>, 4, 256, 2);
-            else go(conv_gemm_split_kernel<2, 2, 2, 2, 2, false>, 4, 256, 2);
+            if (dst_split) go(conv_gemm_split_kernel<2, 2, 2, 2, 2, true>, 256, 2);
+            else go(conv_gemm_split_kernel<2, 2, 2, 2, 2, false>, 256, 2);
         } else {
-            if (dst_split) go(conv_gemm_split_kernel<2, 4, 2, 3, 2, true>, 4, 512, 1);
-            else go(conv_gemm_split_kernel<2, 4, 2, 3, 2, false>, 4, 512, 1);
+            if (dst_split) go(conv_gemm_split_kernel<2, 4, 2, 3, 2, true>, 512, 1);
+            else go(conv_gemm_split_kernel<2, 4, 2, 3, 2, false>, 512, 1);
         }
     };
     auto conv_wino = [&](int li, const float* src, float* dst) {      // conv2 by F(2 x 2, 5 x 5), conv3 / conv4 / conv5 by F(2 x 2, 3 x 3)
         if (li == 1) {
-            Wino5Dims w5 = S->L[1].wd5;
-            w5.tiles = batch * W5_TPI;
-            const int total = w5.groups * w5.ocblocks * ((w5.tiles + W5_TB - 1) / W5_TB);
+            const Wino5Dims w5 = at_batch(S->L[1].wd5, batch);
+            const int total = (int)wino5_total(w5);
             hipLaunchKernelGGL(conv5x5_winograd_kernel, dim3((unsigned)std::min(total, h->num_cu)), dim3(W5_THREADS), 0, st, w5, src,
-                               S->L[1].wino, S->L[1].bias, dst, ctr + 1, total);
+                               S->L[1].wino.p, S->L[1].bias.p, dst, ctr + 1, total);
             return;
         }
-        WinoDims wd = S->L[li].wd;
-        wd.tiles = batch * WG_TILES_PER_IMAGE;
-        const int total = wd.groups * wd.ocblocks * ((wd.tiles + WG_TB - 1) / WG_TB);
+        const WinoDims wd = at_batch(S->L[li].wd, batch);
+        const int total = (int)wino_total(wd);
         hipLaunchKernelGGL(conv3x3_winograd_kernel, dim3((unsigned)std::min(total, h->num_cu)), dim3(WG_THREADS), 0, st, wd, src,
-                           S->L[li].wino, S->L[li].bias, dst, ctr + li, total, live);
+                           S->L[li].wino.p, S->L[li].bias.p, dst, ctr + li, total, live);
     };
     // direct convolutions on pieces (cnn_conv_pieces.hpp), pairs: scaled fp16 pairs, else exact bf16 triples.  to_p6: layer li's bordered
     // f32 input planes as its piece planes
@@ -330,18 +315,15 @@ int run_forward(vpk_handle* h, const CnnConfig& cfg, Images img, int batch, floa
     };
     // (planes_next: the next layer's input planes, written by the epilogue instead of the f32 blob -- fp16 pairs only)
     auto conv_pieces = [&](int li, bool pairs, const unsigned short* src6, float* dst, unsigned short* planes_next) {
-        PieceDims pd = pairs ? S->L[li].pdh : S->L[li].pd;
-        pd.B = batch;
-        if (planes_next) { const PieceDims& nx = S->L[li + 1].pdh; pd.o_cgtot = nx.CGtot; pd.o_Hp = nx.Hp; pd.o_Wp = nx.Wp; pd.o_pad = 1; pd.o_ascale = S->L[li + 1].ascale; }
+        PieceDims pd = at_batch(pairs ? S->L[li].pdh : S->L[li].pd, batch);
+        if (planes_next) hand_planes_to(pd, S->L[li + 1].pdh, S->L[li + 1].ascale);
         pd.range_word = fc.range_word; pd.range_bit = 1u << (li + 1); pd.img_range = fc.img_range; pd.live = live;
-        if (pairs) pd.oscale = 1.f / (S->L[li].hscale * S->L[li].ascale);
-        constexpr int nb = 4;                                               // rows of a wave's four 32 x 32 blocks
-        const int tile_rows = pairs && li == 3 ? 2 * nb : nb;               // (conv4 on pairs: 64 channels x 8 rows per tile)
-        pd.rtiles = (pd.OH + tile_rows - 1) / tile_rows;
-        const int total = pd.groups * batch * pd.rtiles * pd.ctiles * pd.mtiles;
+        if (pairs) pd.oscale = pair_oscale(S->L[li].hscale, S->L[li].ascale);
+        constexpr int nb = CP_NB;                                           // rows of a wave's four 32 x 32 blocks
+        const int total = (int)pieces_total(pd);
         const unsigned blocks = (unsigned)std::min(total, 2 * h->num_cu);   // two workgroups per CU (LDS: two patch buffers each)
         auto go = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(CP_THREADS), 0, st, pd, src6, pairs ? S->L[li].whalf : S->L[li].wsplit, S->L[li].bias,
+            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(CP_THREADS), 0, st, pd, src6, pairs ? S->L[li].whalf.p : S->L[li].wsplit.p, S->L[li].bias.p,
                                dst, planes_next, ctr + li, total);
         };
         if (pairs) { if (li == 1) go(conv_pieces_kernel<5, nb, 2, 1>); else if (li == 3) go(conv_pieces_kernel<3, nb, 2, 2>); else go(conv_pieces_kernel<3, nb, 2, 1>); }
@@ -384,27 +366,27 @@ int run_forward(vpk_handle* h, const CnnConfig& cfg, Images img, int batch, floa
     // (13 rows x 61 columns = 793 pixels per channel and workgroup <= 4 x 256 thread slots; 5 row tiles x 8 channel ranges
     //  of 32 channels per image; measured at B = 102: 0.177 ms against 0.235 ms for lrn5_pool3s2_tiled_kernel<6, 15>)
     if (plan.norm2_planes)          // fp16 pairs: conv3's input planes straight from the pooling stage (cnn_norm_pool_planes.hpp), unless pool2 is tapped
-        hipLaunchKernelGGL((lrn5_pool3s2_planes_kernel<6>), dim3((unsigned)(batch * 5 * 8)), dim3(256), 0, st, R[R_CONV2], R[R_POOL2],
-                           plan.norm2_hands_planes ? p6_3 : nullptr, 256, 61, 61, 30, 30, 1e-4f, 32, 32, 1, 8,
-                           S->L[2].ascale, fc.range_word, 1u << 2, fc.img_range);
+        hipLaunchKernelGGL((lrn5_pool3s2_planes_kernel<N2_TPH>), dim3((unsigned)norm2_blocks(batch)), dim3(256), 0, st, R[R_CONV2], R[R_POOL2],
+                           plan.norm2_hands_planes ? p6_3 : nullptr, pool2.C, TOPO[1].OH, TOPO[1].OW, pool2.H, pool2.W, 1e-4f, pool2.Hp, pool2.Wp,
+                           pool2.pad, N2_CGROUPS, S->L[2].ascale, fc.range_word, 1u << 2, fc.img_range);
     else
-        hipLaunchKernelGGL((lrn5_pool3s2_stream_kernel<6, 4>), dim3((unsigned)(batch * 5 * 8)), dim3(256), 0, st, R[R_CONV2], R[R_POOL2],
-                           256, 61, 61, 30, 30, 1e-4f, 0.75f, 32, 32, 1, 8, live);
+        hipLaunchKernelGGL((lrn5_pool3s2_stream_kernel<N2_TPH, 4>), dim3((unsigned)norm2_blocks(batch)), dim3(256), 0, st, R[R_CONV2], R[R_POOL2],
+                           pool2.C, TOPO[1].OH, TOPO[1].OW, pool2.H, pool2.W, 1e-4f, 0.75f, pool2.Hp, pool2.Wp, pool2.pad, N2_CGROUPS, live);
     mark(2);
-    tapunpad(3, R[R_POOL2], 256, 30, 30, 1);
+    tapunpad(3, R[R_POOL2], 2);
     // conv3 -> conv4 -> conv5.  Pieces: conv3's epilogue writes conv4's planes into p6_5, conv4's writes conv5's into p6_3, which conv3
     // has finished reading; the split GEMM chains through s4 and s5.  A tapped f32 blob is written as such and converted for the next layer.
     conv_stage(2, R[R_POOL2], R[R_CONV3], p6_3, p6_5, nullptr, s4);
     mark(1);
-    tapunpad(4, R[R_CONV3], 384, 30, 30, 1);
+    tapunpad(4, R[R_CONV3], 3);
     conv_stage(3, R[R_CONV3], R[R_CONV4], p6_5, p6_3, s4, s5);
     mark(1);
-    tapunpad(5, R[R_CONV4], 384, 30, 30, 1);
+    tapunpad(5, R[R_CONV4], 4);
     conv_stage(4, R[R_CONV4], R[R_CONV5], plan.conv[2].writes_next_planes ? p6_3 : p6_5, nullptr, s5, nullptr);
     mark(1);
     if ((rc = tapcopy(6, R[R_CONV5], A_CONV5))) return rc;
-    hipLaunchKernelGGL((pool5_kernel<8>), dim3((unsigned)(((long long)batch * 256 + 7) / 8)), dim3(256), 0, st, R[R_CONV5], R[R_POOL5],
-                       (long long)batch * 256, live);
+    hipLaunchKernelGGL((pool5_kernel<POOL5_PL>), dim3((unsigned)pool5_blocks(batch)), dim3(256), 0, st, R[R_CONV5], R[R_POOL5],
+                       pool5_planes(batch), live);
     mark(1);
     if ((rc = tapcopy(7, R[R_POOL5], A_POOL5))) return rc;
 
@@ -420,33 +402,26 @@ int run_forward(vpk_handle* h, const CnnConfig& cfg, Images img, int batch, floa
             // on pieces (cnn_dense_pieces.hpp): the input split into B fragments; the weights streamed as f32 in tile order and split in
             // registers -- exact bf16 triples, or scaled fp16 pairs -- or, the pairs' default, streamed pre-split
             const bool pairs = impl != DenseImpl::PIECES3;
-            DenseDims dd;
-            dd.N = batch; dd.K = d.K; dd.OC = d.OC; dd.chunks = d.K / DP_CHUNK;
-            dd.kparts = li == 5 ? 45 : 16;                        // work items: 16 x 45 / 16 x 16 row tiles x K parts
-            dd.cpp = dd.chunks / dd.kparts;
-            dd.mtiles = (d.OC + DP_BM - 1) / DP_BM; dd.ntiles = (batch + DP_BN - 1) / DP_BN;
-            dd.wscale = pairs ? S->L[li].hscale : 1.f;
+            DenseDims dd = at_batch(S->L[li].dd, batch, pairs, S->L[li].hscale, S->L[li].ascale);
             dd.live = live;
-            dd.oscale = pairs ? 1.f / (S->L[li].hscale * S->L[li].ascale) : 1.f;
-            const size_t need = (size_t)dd.ntiles * (TOPO[5].IC / DP_CHUNK) * DP_STAGE<3>;
-            if ((rc = vpk_reserve(h, (void**)&S->xfrag, &S->xfrag_bytes, need, "hipMalloc(dense input fragments)"))) return rc;
-            const int total = dd.mtiles * dd.ntiles * dd.kparts;
+            if ((rc = vpk_reserve(h, S->xfrag.out(), &S->xfrag_bytes, xfrag_bytes(batch), "hipMalloc(dense input fragments)"))) return rc;
+            const int total = (int)dense_total(dd);
             const dim3 split_grid((unsigned)dd.chunks, (unsigned)dd.ntiles), grid((unsigned)std::min(total, h->num_cu));
             if (pairs)
-                hipLaunchKernelGGL(dense_split_kernel<2>, split_grid, dim3(256), 0, st, fc_in, S->xfrag, batch,
+                hipLaunchKernelGGL(dense_split_kernel<2>, split_grid, dim3(256), 0, st, fc_in, S->xfrag.p, batch,
                                    d.K, dd.chunks, S->L[li].ascale, fc.range_word, 1u << li, fc.img_range, nullptr);
             else
-                hipLaunchKernelGGL(dense_split_kernel<3>, split_grid, dim3(256), 0, st, fc_in, S->xfrag, batch,
+                hipLaunchKernelGGL(dense_split_kernel<3>, split_grid, dim3(256), 0, st, fc_in, S->xfrag.p, batch,
                                    d.K, dd.chunks, 1.f, fc.range_word, 0u, nullptr, live);
             switch (impl) {
             case DenseImpl::PIECES2_PRESPLIT:
-                hipLaunchKernelGGL(dense_pairs_kernel, grid, dim3(DP_THREADS), 0, st, dd, S->L[li].wpair, S->xfrag, R[R_PART], ctr + li, total);
+                hipLaunchKernelGGL(dense_pairs_kernel, grid, dim3(DP_THREADS), 0, st, dd, S->L[li].wpair.p, S->xfrag.p, R[R_PART], ctr + li, total);
                 break;
             case DenseImpl::PIECES2_STREAMED:
-                hipLaunchKernelGGL(dense_pieces_kernel<2>, grid, dim3(DP_THREADS), 0, st, dd, S->L[li].wraw, S->xfrag, R[R_PART], ctr + li, total);
+                hipLaunchKernelGGL(dense_pieces_kernel<2>, grid, dim3(DP_THREADS), 0, st, dd, S->L[li].wraw.p, S->xfrag.p, R[R_PART], ctr + li, total);
                 break;
             default:
-                hipLaunchKernelGGL(dense_pieces_kernel<3>, grid, dim3(DP_THREADS), 0, st, dd, S->L[li].wraw, S->xfrag, R[R_PART], ctr + li, total);
+                hipLaunchKernelGGL(dense_pieces_kernel<3>, grid, dim3(DP_THREADS), 0, st, dd, S->L[li].wraw.p, S->xfrag.p, R[R_PART], ctr + li, total);
                 break;
             }
             d.ksplit = dd.kparts;
@@ -454,7 +429,7 @@ int run_forward(vpk_handle* h, const CnnConfig& cfg, Images img, int batch, floa
         const long long tot = (long long)d.N * d.OC;
         float* dst = li == 7 ? out : fc_out;
         float* pre = (li == 7 && tap == 10) ? tap_out : nullptr;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(ew_blocks(tot)), dim3(256), 0, st, R[R_PART], S->L[li].bias, d.ksplit,
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)ew_blocks(tot)), dim3(EW_THREADS), 0, st, R[R_PART], S->L[li].bias.p, d.ksplit,
                            d.N, d.OC, li == 7 ? 2 : 1, dst, pre, live);
         mark(1);
         if (li == 5 && (rc = tapcopy(8, fc_out, A_FC6))) return rc;
@@ -476,147 +451,103 @@ int run_forward(vpk_handle* h, const CnnConfig& cfg, Images img, int batch, floa
 
 namespace {
 
-// a device allocation that lives for one scope (the raw weights of a layer while its packed forms are made)
-struct ScopedDeviceBuffer {
-    void* p = nullptr;
-    ~ScopedDeviceBuffer() { if (p) (void)hipFree(p); }
-};
-
-// host data -> a new device allocation at *dst (owned by the state: vpk_cnn_free releases it, also after a failure here)
+// host data -> a new device allocation in dst (owned by the state: released with it, also after a failure here)
 template <typename T>
-int upload(vpk_handle* h, T** dst, const T* src, size_t n) {
-    VPK_HIP(h, hipMalloc((void**)dst, n * sizeof(T)));
-    VPK_HIP(h, hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
+int upload(vpk_handle* h, DeviceBuffer<T>& dst, const T* src, size_t n) {
+    VPK_HIP(h, hipMalloc(dst.out(), n * sizeof(T)));
+    VPK_HIP(h, hipMemcpy(dst.p, src, n * sizeof(T), hipMemcpyHostToDevice));
     return VPK_OK;
 }
+template <typename T>
+int upload(vpk_handle* h, DeviceBuffer<T>& dst, const std::vector<T>& v) { return upload(h, dst, v.data(), v.size()); }
 
-// every packed form of every layer's weights into the fresh state h->cnn, then the calibration.  On failure the state is left as far
-// as it got: vpk_cnn_load frees it.
+// every packed form of every layer's weights into the fresh state h->cnn, then the calibration.  Per layer: the dimension structs from
+// cnn_model.hpp, the packers of the kernel headers, upload.  On failure the state is left as far as it got: vpk_cnn_load frees it.
 int load_model(vpk_handle* h, const float* const blobs[16], const float* mean) {
     vpk_cnn_state* S = h->cnn;
     int rc;
-    if ((rc = upload(h, &S->mean, mean, (size_t)500 * 500))) return rc;
+    if ((rc = upload(h, S->mean, mean, IMAGE_PIXELS))) return rc;
     if (const char* e = getenv("VPK_CONV1_GROUP")) { const int v = atoi(e); if (v >= 1 && v <= 64) S->cfg.conv1_group = v; }
     if (const char* e = getenv("VPK_DENSE_PRESPLIT")) S->cfg.dense_presplit = atoi(e) != 0;
     for (int li = 0; li < 8; ++li) {
         const Topo& t = TOPO[li];
         const float* w = blobs[2 * li];
         Layer& l = S->L[li];
-        ConvDims& d = l.d;
-        d.B = 0; d.IC = t.IC; d.Hp = t.H + 2 * t.P; d.Wp = t.W + 2 * t.P; d.OC = t.OC; d.OH = t.OH; d.OW = t.OW; d.groups = t.G;
-        d.OHp = t.OH + 2 * t.OP; d.OWp = t.OW + 2 * t.OP; d.opad = t.OP;
-        if (li == 0) { d.IC = C1_PH * C1_PH; d.Hp = C1_PW; d.Wp = C1_PW; }   // phase planes (K stays 11 x 11)
-        d.K = t.IC * t.KH * t.KH;
-        d.Kp = (d.K + BK - 1) / BK * BK;
-        d.Mp = (t.OC + t.BM - 1) / t.BM * t.BM;
-        d.N = 0;
-        d.ksplit = KSPLIT[li];
-        d.relu = 1;
+        const ConvDims& d = l.d = conv_dims(li);
         const size_t w_floats = (size_t)t.G * t.OC * d.K;
         const size_t p_floats = (size_t)t.G * d.Kp * d.Mp;
-        {   // the forms the device packs from the raw weights: the f32 GEMM's k-major panels ...
-            ScopedDeviceBuffer rawbuf;
-            VPK_HIP(h, hipMalloc(&rawbuf.p, w_floats * sizeof(float)));
-            const float* raw = static_cast<const float*>(rawbuf.p);
-            VPK_HIP(h, hipMemcpy(rawbuf.p, w, w_floats * sizeof(float), hipMemcpyHostToDevice));
-            VPK_HIP(h, hipMalloc((void**)&l.wp, p_floats * sizeof(float)));
-            hipLaunchKernelGGL(pack_weights_kernel, dim3((unsigned)((p_floats + 255) / 256)), dim3(256), 0, h->stream, raw,
-                               l.wp, t.G, t.OC, d.K, d.Kp, d.Mp);
+        {   // the forms the device packs from the raw weights (which live for this scope): the f32 GEMM's k-major panels ...
+            DeviceBuffer<float> raw;
+            VPK_HIP(h, hipMalloc(raw.out(), w_floats * sizeof(float)));
+            VPK_HIP(h, hipMemcpy(raw.p, w, w_floats * sizeof(float), hipMemcpyHostToDevice));
+            VPK_HIP(h, hipMalloc(l.wp.out(), p_floats * sizeof(float)));
+            hipLaunchKernelGGL(pack_weights_kernel, dim3((unsigned)ew_blocks((long long)p_floats)), dim3(EW_THREADS), 0, h->stream,
+                               (const float*)raw.p, l.wp.p, t.G, t.OC, d.K, d.Kp, d.Mp);
             VPK_HIP(h, hipStreamSynchronize(h->stream));
             if (li == 5 || li == 6) {       // ... fc6, fc7: also as f32 in tile order for the pieces path (cnn_dense_pieces.hpp)
-                const int chunks = d.K / DP_CHUNK, mtiles = (t.OC + DP_BM - 1) / DP_BM;
-                const long long total4 = (long long)mtiles * chunks * DP_BM * (DP_CHUNK / 4);
-                VPK_HIP(h, hipMalloc((void**)&l.wraw, (size_t)total4 * 16));
-                hipLaunchKernelGGL(dense_tile_weights_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, h->stream, raw, l.wraw, t.OC, d.K,
-                                   chunks, total4);
+                const DenseDims& dd = l.dd = dense_dims(li);
+                const long long total4 = (long long)dd.mtiles * dd.chunks * DP_BM * (DP_CHUNK / 4);
+                VPK_HIP(h, hipMalloc(l.wraw.out(), (size_t)total4 * 16));
+                hipLaunchKernelGGL(dense_tile_weights_kernel, dim3((unsigned)ew_blocks(total4)), dim3(EW_THREADS), 0, h->stream,
+                                   (const float*)raw.p, l.wraw.p, t.OC, d.K, dd.chunks, total4);
                 VPK_HIP(h, hipStreamSynchronize(h->stream));
                 l.hscale = weight_scale_pow2(w, w_floats);
                 // ... and as scaled fp16 pairs in the A-fragment order of dense_pairs_kernel (4 bytes per weight, like the f32 copy)
-                const long long total16 = (long long)mtiles * chunks * 8 * 2 * 2 * 64;
-                VPK_HIP(h, hipMalloc((void**)&l.wpair, (size_t)total16 * 16));
-                hipLaunchKernelGGL(dense_pair_weights_kernel, dim3((unsigned)((total16 + 255) / 256)), dim3(256), 0, h->stream, raw, l.wpair, t.OC,
-                                   d.K, chunks, l.hscale, total16);
+                const long long total16 = (long long)dd.mtiles * dd.chunks * 8 * 2 * 2 * 64;
+                VPK_HIP(h, hipMalloc(l.wpair.out(), (size_t)total16 * 16));
+                hipLaunchKernelGGL(dense_pair_weights_kernel, dim3((unsigned)ew_blocks(total16)), dim3(EW_THREADS), 0, h->stream,
+                                   (const float*)raw.p, l.wpair.p, t.OC, d.K, dd.chunks, l.hscale, total16);
                 VPK_HIP(h, hipStreamSynchronize(h->stream));
             }
         }
-        if (li < 5) {   // convolution: byte offset of tap k from the patch origin, in the bordered planes;
-                        // the K padding (conv1: 121 -> 128) points at offset 0 and meets zero weights
-            std::vector<unsigned> tab(d.Kp, 0u);
-            for (int k = 0; k < d.K; ++k) {
-                int ic = k / (t.KH * t.KH), r = k % (t.KH * t.KH), kh = r / t.KH, kw = r % t.KH;
-                if (li == 0)   // conv1 reads the stride-4 phase planes written by prep_input_kernel
-                    tab[k] = (unsigned)((((kh % C1_PH) * C1_PH + kw % C1_PH) * C1_PW + kh / C1_PH) * C1_PW + kw / C1_PH) * 4u;
-                else
-                    tab[k] = (unsigned)((ic * d.Hp + kh) * d.Wp + kw) * 4u;
-            }
-            if ((rc = upload(h, &l.ktab, tab.data(), tab.size()))) return rc;
-        }
-        if (li >= 1 && li <= 4) {   // conv2..5 in MFMA fragment order: three bf16 pieces of every weight, and scaled fp16 pairs
-            SplitDims& sd = l.sd;
-            const int blk = t.OC == 192 ? 6 : 4;                      // 32-row blocks per tile
-            sd.B = 0; sd.Cg = t.IC; sd.Ctot = t.IC * t.G; sd.Hp = d.Hp; sd.Wp = d.Wp; sd.OC = t.OC; sd.OH = t.OH; sd.OW = t.OW;
-            sd.groups = t.G; sd.KW = t.KH; sd.ntaps = t.KH * t.KH; sd.csteps = t.IC / 16; sd.ksteps = sd.ntaps * sd.csteps;
-            sd.mblocks = (t.OC / 32 + blk - 1) / blk * blk; sd.N = 0; sd.relu = 1; sd.OHp = d.OHp; sd.OWp = d.OWp; sd.opad = d.opad;
+        if (li < 5 && (rc = upload(h, l.ktab, conv_ktab(li)))) return rc;
+        if (li >= 1 && li <= 4) {   // conv2..5 in MFMA fragment order: three bf16 pieces of every weight (split GEMM and conv_pieces_kernel
+                                    // read the same fragments), and scaled fp16 pairs: weights x 2^k (the largest in [2^13, 2^14))
+            l.sd = split_dims(li);
+            l.pd = piece_dims(li, false);
+            l.pdh = piece_dims(li, true);
             std::vector<unsigned short> pk;
-            pack_conv_fragments<3>(w, t.G, t.OC, t.IC, t.KH, sd.mblocks, 1.f, pk);
-            if ((rc = upload(h, &l.wsplit, pk.data(), pk.size()))) return rc;
-            PieceDims& pd = l.pd;                                     // the same fragments feed conv_pieces_kernel
-            pd.B = 0; pd.Cg16 = t.IC / 16; pd.CGtot = t.IC * t.G / 16; pd.Hp = d.Hp; pd.Wp = d.Wp; pd.OC = t.OC; pd.OH = t.OH; pd.OW = t.OW;
-            pd.groups = t.G; pd.KW = t.KH; pd.ntaps = t.KH * t.KH; pd.ksteps = sd.ksteps; pd.mblocks = sd.mblocks;
-            pd.mtiles = sd.mblocks / blk; pd.rtiles = (t.OH + 3) / 4; pd.ctiles = (t.OW + CP_TC - 1) / CP_TC; pd.relu = 1;
-            pd.OHp = d.OHp; pd.OWp = d.OWp; pd.opad = d.opad;
-            pd.in_image = (long long)pd.CGtot * 6 * d.Hp * d.Wp * 16;
-            pd.oscale = 1.f;
-            // the same layer on fp16 pairs: weights x 2^k (the largest in [2^13, 2^14)), two pieces each; 32-row blocks padded to
-            // whole tiles (none needed: 4 per tile, conv4 2)
-            PieceDims& ph = l.pdh;
-            ph = pd;
-            const int mbt = li == 3 ? 2 : 4;                          // 32-row blocks per tile: 128 channels x 4 rows; conv4 (192 channels per group) 64 x 8
-            ph.mblocks = (t.OC / 32 + mbt - 1) / mbt * mbt;
-            ph.mtiles = ph.mblocks / mbt;
-            ph.in_image = (long long)ph.CGtot * 4 * d.Hp * d.Wp * 16;
+            pack_conv_fragments<3>(w, t.G, t.OC, t.IC, t.KH, l.sd.mblocks, 1.f, pk);
+            if ((rc = upload(h, l.wsplit, pk))) return rc;
             l.hscale = weight_scale_pow2(w, w_floats);
-            ph.oscale = 1.f / (l.hscale * l.ascale);             // (set again per forward: the activation scale is calibrated after the load)
-            pack_conv_fragments<2>(w, t.G, t.OC, t.IC, t.KH, ph.mblocks, l.hscale, pk);
-            if ((rc = upload(h, &l.whalf, pk.data(), pk.size()))) return rc;
+            pack_conv_fragments<2>(w, t.G, t.OC, t.IC, t.KH, l.pdh.mblocks, l.hscale, pk);
+            if ((rc = upload(h, l.whalf, pk))) return rc;
         }
         if (li == 0) {              // conv1 on the matrix cores: bf16 triples and scaled fp16 pairs in fragment order, bias - conv1(mean)
             std::vector<unsigned short> fr;
             conv1_pieces_weights(w, fr);
-            if ((rc = upload(h, &l.c1frag, fr.data(), fr.size()))) return rc;
+            if ((rc = upload(h, l.c1frag, fr))) return rc;
             l.c1scale = weight_scale_pow2(w, w_floats);
             conv1_pieces_weights(w, fr, 2, l.c1scale);
-            if ((rc = upload(h, &l.c1half, fr.data(), fr.size()))) return rc;
+            if ((rc = upload(h, l.c1half, fr))) return rc;
             std::vector<float> cm;
             conv1_pieces_cmap(w, blobs[1], mean, cm);
-            if ((rc = upload(h, &l.c1map, cm.data(), cm.size()))) return rc;
+            if ((rc = upload(h, l.c1map, cm))) return rc;
         }
         if (li >= 1 && li <= 4) {   // G g G^T of every filter, in the order the Winograd kernels stream it (cnn_winograd.hpp)
             std::vector<float> u;
             if (li == 1) {          // conv2: F(2 x 2, 5 x 5)
                 winograd5_weights(w, t.G, t.OC, t.IC, u);
-                Wino5Dims& w5 = l.wd5;
-                w5.IC = t.IC; w5.OC = t.OC; w5.groups = t.G; w5.ctot_in = t.IC * t.G; w5.ctot_out = t.OC * t.G; w5.tiles = 0;
-                w5.ocblocks = t.OC / W5_OCB; w5.chunks = t.IC / W5_KC; w5.relu = 1;
+                l.wd5 = wino5_dims(li);
             } else {                // conv3..5: F(2 x 2, 3 x 3)
                 winograd_weights(w, t.G, t.OC, t.IC, u);
-                WinoDims& wd = l.wd;
-                wd.IC = t.IC; wd.OC = t.OC; wd.groups = t.G; wd.ctot_in = t.IC * t.G; wd.ctot_out = t.OC * t.G; wd.tiles = 0;
-                wd.ocblocks = t.OC / WG_OCB; wd.chunks = t.IC / WG_KC; wd.OHp = d.OHp; wd.OWp = d.OWp; wd.opad = d.opad; wd.relu = 1;
+                l.wd = wino_dims(li);
             }
-            if ((rc = upload(h, &l.wino, u.data(), u.size()))) return rc;
+            if ((rc = upload(h, l.wino, u))) return rc;
         }
-        if ((rc = upload(h, &l.bias, blobs[2 * li + 1], (size_t)t.G * t.OC))) return rc;
+        if ((rc = upload(h, l.bias, blobs[2 * li + 1], (size_t)t.G * t.OC))) return rc;
     }
-    VPK_HIP(h, hipMalloc((void**)&S->range_word, 256));
-    VPK_HIP(h, hipMemset(S->range_word, 0, 256));
-    VPK_HIP(h, hipMalloc((void**)&S->rc_list, (1 + MAX_CHUNK) * sizeof(int)));
-    VPK_HIP(h, hipMalloc((void**)&S->rc_total, sizeof(unsigned long long)));
-    VPK_HIP(h, hipMemset(S->rc_total, 0, sizeof(unsigned long long)));
+    VPK_HIP(h, hipMalloc(S->range_word.out(), 256));
+    VPK_HIP(h, hipMemset(S->range_word.p, 0, 256));
+    VPK_HIP(h, hipMalloc(S->rc_list.out(), (1 + MAX_CHUNK) * sizeof(int)));
+    VPK_HIP(h, hipMalloc(S->rc_total.out(), sizeof(unsigned long long)));
+    VPK_HIP(h, hipMemset(S->rc_total.p, 0, sizeof(unsigned long long)));
     // the activation scales of the fp16-pair layers: six tapped forwards of the built-in calibration rasters on the f32 direct
     // kernels (calibrate()); their arena (batch 3) is released again so that the first real forward allocates once, for its batch
     rc = calibrate(h, nullptr, 0);
-    if (S->act) { (void)hipFree(S->act); S->act = nullptr; S->act_bytes = 0; S->act_batch = 0; }
+    S->act.reset();
+    S->act_bytes = 0;
+    S->act_batch = 0;
     return rc;
 }
 
@@ -768,24 +699,22 @@ int forward_chunks(vpk_handle* h, Images sphere, int batch, float* out, int tap,
     const size_t per_img = arena_floats_per_image() * sizeof(float);
     int chunk = (int)std::min<size_t>(std::min<size_t>((size_t)batch, MAX_CHUNK),
                                       std::max<size_t>(1, (h->total_mem / 3) / per_img));
-    static const size_t tap_size[11] = {A_CONV1, A_POOL1, A_CONV2, A_POOL2, A_CONV3, A_CONV4, A_CONV5, A_POOL5,
-                                        A_FC6, A_FC7, A_FC8};
     vpk_cnn_state* S = h->cnn;
     if (policy) {
-        int rc = vpk_reserve(h, (void**)&S->img_range, &S->img_range_bytes, (size_t)batch * sizeof(unsigned), "hipMalloc(per-image range flags)");
+        int rc = vpk_reserve(h, S->img_range.out(), &S->img_range_bytes, (size_t)batch * sizeof(unsigned), "hipMalloc(per-image range flags)");
         if (rc) return rc;
-        VPK_HIP(h, hipMemsetAsync(S->img_range, 0, (size_t)batch * sizeof(unsigned), h->stream));
+        VPK_HIP(h, hipMemsetAsync(S->img_range.p, 0, (size_t)batch * sizeof(unsigned), h->stream));
         S->img_range_batch = batch;
     }
     // only the fp16-pair configuration can clamp: the recompute pass is not even launched for the others
     const bool recompute = policy && S->range_policy == 1 && S->cfg.precision == 0 && S->cfg.algorithm == 4;
     for (int b0 = 0; b0 < batch; b0 += chunk) {
         int nb = std::min(chunk, batch - b0);
-        float* tp = (tap_out && tap >= 0 && tap <= 10) ? tap_out + (size_t)b0 * tap_size[tap] : nullptr;
+        float* tp = (tap_out && tap >= 0 && tap <= 10) ? tap_out + (size_t)b0 * TAP_FLOATS[tap] : nullptr;
         const Images sp = sphere.at((size_t)b0);
-        float* op = out + (size_t)b0 * 400;
-        unsigned* img = policy ? S->img_range + b0 : nullptr;
-        int rc = run_forward(h, S->cfg, sp, nb, op, tp ? tap : -1, tp, FwdCtl{recompute ? S->range_word + 1 : S->range_word, img, nullptr});
+        float* op = out + (size_t)b0 * OUTPUTS_PER_IMAGE;
+        unsigned* img = policy ? S->img_range.p + b0 : nullptr;
+        int rc = run_forward(h, S->cfg, sp, nb, op, tp ? tap : -1, tp, FwdCtl{S->range_word.p + (recompute ? 1 : 0), img, nullptr});
         if (!rc && recompute) rc = recompute_flagged(h, sp, nb, op, img);
         if (rc) return rc;
     }
