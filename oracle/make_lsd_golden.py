@@ -1,6 +1,6 @@
 """Recorded rows of the line segment detector under the portable math policy.
 
-TEST INFRASTRUCTURE.  Compiles tests/hostsim/sim_lsd.cpp with g++ (the build tests/test_hostsim_lsd.py uses) and stores,
+TEST INFRASTRUCTURE.  Loads the g++ build of tests/hostsim/sim_lsd.cpp (the one tests/test_hostsim_lsd.py uses) and stores,
 in tests/golden/lsd/lsd_portable.npz, five small images as uint8 grey levels -- so the inputs are the same bytes on every
 machine -- and for each the rows of sim_lsd_portable at scales 0.8, 1.0 and 0.5.  The portable policy
 (csrc/lsd_portable_math.hpp) is exact arithmetic: the same bits come out whatever libm a machine has, on the host and,
@@ -15,7 +15,6 @@ Usage:  python oracle/make_lsd_golden.py
 """
 import os
 import sys
-import tempfile
 
 import numpy as np
 
@@ -43,7 +42,7 @@ def images():
 
 
 def main():
-    run = build_sim(tempfile.mkdtemp(), "sim_lsd_portable")
+    run = build_sim("sim_lsd_portable")
     out = {}
     for name, img in images().items():
         out["image_" + name] = img

@@ -2,8 +2,7 @@
 // tests/test_cnn_model.py, every launch total, the tap tables and the arena, walked in one process with the invariants the kernels
 // rely on (tiles cover the layer, totals fit an int, taps stay inside the bordered planes).  Made to be built with the host
 // sanitizers and run on its own; it prints one line and returns 0 when every call answered as expected:
-//     g++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=all
-//         tests/hostsim/cnn_model_driver.cpp -o cnn_model_driver && ./cnn_model_driver
+//     python tests/hostsim/hostbuild.py drivers
 // No test runs it.
 #include <limits.h>
 #include <stdio.h>

@@ -2,8 +2,7 @@
 // and without a time slice, the session's refusals, every limit, the header and session layouts, the queue order -- walked in
 // one process.  Made to be built with the host sanitizers and run on its own; it prints one line and returns 0 when every
 // call answered as expected:
-//     g++ -O1 -g -std=c++17 -Wall -Wno-unknown-pragmas -Wno-unused-function -fsanitize=address,undefined -fno-sanitize-recover=all
-//         tests/hostsim/em_plan_driver.cpp -o em_plan_driver && ./em_plan_driver
+//     python tests/hostsim/hostbuild.py drivers
 // No test runs it.
 #include <stdio.h>
 

@@ -2,8 +2,7 @@
 // (csrc/lsd_host.hpp) with both math policies on small images at the scales where a scaled side is 1 pixel, below 1, 1 and
 // above 1, and plan_batch (csrc/lsd_plan.hpp) on a planned batch and on every refusal.  Made to be built with the host
 // sanitizers and run on its own; it prints one line and returns 0 when every call answered as expected:
-//     g++ -O1 -g -std=c++17 -ffp-contract=off -fno-builtin -fsanitize=address,undefined -fno-sanitize-recover=all
-//         tests/hostsim/lsd_host_driver.cpp -o lsd_host_driver && ./lsd_host_driver
+//     python tests/hostsim/hostbuild.py drivers
 // No test runs it.
 #include <stdio.h>
 

@@ -1,20 +1,13 @@
 """ctypes access to the TEST-ONLY host build of the EM device source (tests/hostsim/sim_em.cpp).
 
-Builds tests/hostsim/_build/libvpk_hostsim.so with g++ on first use.  See hip_sim.hpp for what
+hostbuild.py builds tests/hostsim/_build/libvpk_hostsim.so on first use.  See hip_sim.hpp for what
 this is (a single-lane logic check of the device code) and is not (a product path)."""
 import ctypes
-import glob
 import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-BUILD = os.path.join(HERE, "_build")
-SO = os.path.join(BUILD, "libvpk_hostsim.so")
-CSRC = os.path.join(HERE, "..", "..", "vanishing_points_2017_amd", "csrc")
-# sim_em.cpp first (the one file g++ is given); every header it can reach makes the library stale
-SRC = [os.path.join(HERE, "sim_em.cpp")] + sorted(glob.glob(os.path.join(HERE, "*.hpp")) + glob.glob(os.path.join(CSRC, "*.hpp")))
+from . import hostbuild
 
 
 class EmParams(ctypes.Structure):
@@ -26,20 +19,8 @@ class EmParams(ctypes.Structure):
                 ("final_convergence", ctypes.c_double), ("s_thresh", ctypes.c_double)]
 
 
-_lib = None
-
-
 def lib():
-    global _lib
-    if _lib is not None:
-        return _lib
-    os.makedirs(BUILD, exist_ok=True)
-    stale = (not os.path.exists(SO)) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC)
-    if stale:
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                               "-Wno-unknown-pragmas", SRC[0], "-o", SO])
-    _lib = ctypes.CDLL(SO)
-    return _lib
+    return hostbuild.load("em")
 
 
 def _p(a, t):
@@ -200,8 +181,6 @@ def line_counts(lp, v, s, w, lweight, thresh=1.96 ** 2):
 
 
 # ---- the rasteriser (csrc/raster_device.hpp, raster_curve.hpp, raster_coverage.hpp) ----------------------------------------
-RASTER_SO = os.path.join(BUILD, "libvpk_hostsim_raster.so")
-RASTER_SRC = [os.path.join(HERE, "sim_raster.cpp"), os.path.join(HERE, "hip_sim.hpp")] + sorted(glob.glob(os.path.join(CSRC, "raster_*.hpp")))
 _raster_lib = None
 
 
@@ -209,11 +188,7 @@ def raster_lib():
     global _raster_lib
     if _raster_lib is not None:
         return _raster_lib
-    os.makedirs(BUILD, exist_ok=True)
-    stale = (not os.path.exists(RASTER_SO)) or any(os.path.getmtime(s) > os.path.getmtime(RASTER_SO) for s in RASTER_SRC)
-    if stale:
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", RASTER_SRC[0], "-o", RASTER_SO])
-    _raster_lib = ctypes.CDLL(RASTER_SO)
+    _raster_lib = hostbuild.load("raster")
     _raster_lib.sim_raster.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                        ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_longlong)]
     _raster_lib.sim_raster_pool.argtypes = [ctypes.c_int]

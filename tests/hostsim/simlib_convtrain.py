@@ -1,29 +1,17 @@
 """ctypes access to the TEST-ONLY host build of csrc/convtrain_device.hpp (tests/hostsim/sim_convtrain.cpp): the per-element
-rules of the conv stack's training step.  A library of its own, built with g++ on first use."""
+rules of the conv stack's training step.  A library of its own, built by hostbuild.py on first use."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-from . import simlib
+from . import hostbuild, simlib
 
-SO = os.path.join(simlib.BUILD, "libvpk_hostsim_convtrain.so")
-SRC = [os.path.join(simlib.HERE, "sim_convtrain.cpp"), os.path.join(simlib.CSRC, "convtrain_device.hpp")]
 FWD, DGRAD, WGRAD = 0, 1, 2
 TILE, CHUNK, TARGET = 64, 16, 1024          # csrc/train_plan.hpp: CT_TILE, CT_CHUNK, CT_TARGET_BLOCKS
 
-_lib = None
-
 
 def lib():
-    global _lib
-    if _lib is None:
-        os.makedirs(simlib.BUILD, exist_ok=True)
-        if (not os.path.exists(SO)) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", SRC[0], "-o", SO])
-        _lib = ctypes.CDLL(SO)
-    return _lib
+    return hostbuild.load("convtrain")
 
 
 def conv_out_size(size, k, stride, pad):

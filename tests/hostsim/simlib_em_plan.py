@@ -1,18 +1,11 @@
 """ctypes access to the TEST-ONLY host build of csrc/em_plan.hpp (tests/hostsim/sim_em_plan.cpp): what vpk_em_batch decides on
-the host before it launches.  A library of its own, built with g++ -Wall on first use."""
+the host before it launches.  A library of its own, built by hostbuild.py on first use."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-from . import simlib
+from . import hostbuild
 from .simlib import EmParams
-
-SO = os.path.join(simlib.BUILD, "libvpk_hostsim_em_plan.so")
-SRC = [os.path.join(simlib.HERE, "sim_em_plan.cpp"), os.path.join(simlib.HERE, "hip_sim.hpp"),
-       os.path.join(simlib.HERE, "..", "..", "include", "vpk.h")] + \
-      [os.path.join(simlib.CSRC, f) for f in ("em_plan.hpp", "em_ctx.hpp", "em_layout.hpp", "prior_device.hpp", "line_device.hpp")]
 
 _Z, _I, _U = ctypes.c_size_t, ctypes.c_int, ctypes.c_ulonglong
 
@@ -49,12 +42,7 @@ def default_params(**kw):
 def lib():
     global _lib
     if _lib is None:
-        os.makedirs(simlib.BUILD, exist_ok=True)
-        if (not os.path.exists(SO)) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-            # (the two -Wno: pragmas and unused device functions of the EM headers em_plan.hpp includes)
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function", "-fPIC",
-                                   "-shared", SRC[0], "-o", SO])
-        _lib = ctypes.CDLL(SO)
+        _lib = hostbuild.load("em_plan")
         sizes = (ctypes.c_int * 4)()
         _lib.sim_em_plan_sizes(sizes)
         assert list(sizes) == [ctypes.sizeof(EmFacts), ctypes.sizeof(EmLayout), ctypes.sizeof(Plan), ctypes.sizeof(EmParams)]

@@ -1,30 +1,17 @@
 """ctypes access to the TEST-ONLY host build tests/hostsim/sim_em_estep_zeros.cpp: a lone E-step + smoother and the whole EM
 on one image, under either measure AND either setting of EmCtx::smoother (0: the E-step's three passes, 1: the dense form).
-A library of its own, built with g++ on first use; simlib.py's stays as it is."""
+A library of its own, built by hostbuild.py on first use; simlib.py's stays as it is."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-from . import simlib
+from . import hostbuild, simlib
 
-SO = os.path.join(simlib.BUILD, "libvpk_hostsim_estep_zeros.so")
-SRC = [os.path.join(simlib.HERE, "sim_em_estep_zeros.cpp")] + simlib.SRC[1:]
 MEASURES = {"angle": 0, "dotprod": 1}       # include/vpk.h: VPK_DIST_ANGLE, VPK_DIST_DOTPROD
-
-_lib = None
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        os.makedirs(simlib.BUILD, exist_ok=True)
-        if (not os.path.exists(SO)) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                                   "-Wno-unknown-pragmas", SRC[0], "-o", SO])
-        _lib = ctypes.CDLL(SO)
-    return _lib
+    return hostbuild.load("estep_zeros")
 
 
 def estep_smooth(l, lp, cnn, v, s, lweight, lsim, measure="angle", smoother=0, lds_doubles=None, bias=1.0):

@@ -1,29 +1,16 @@
 """ctypes access to the TEST-ONLY host build of em_run<MEASURE> (tests/hostsim/sim_em_measure.cpp): the EM driver on one
-image under "angle" or "dotprod".  A library of its own, built with g++ on first use; simlib.py's stays as it is."""
+image under "angle" or "dotprod".  A library of its own, built by hostbuild.py on first use; simlib.py's stays as it is."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-from . import simlib
+from . import hostbuild, simlib
 
-SO = os.path.join(simlib.BUILD, "libvpk_hostsim_measure.so")
-SRC = [os.path.join(simlib.HERE, "sim_em_measure.cpp")] + simlib.SRC[1:]
 MEASURES = {"angle": 0, "dotprod": 1}       # include/vpk.h: VPK_DIST_ANGLE, VPK_DIST_DOTPROD
-
-_lib = None
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        os.makedirs(simlib.BUILD, exist_ok=True)
-        if (not os.path.exists(SO)) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                                   "-Wno-unknown-pragmas", SRC[0], "-o", SO])
-        _lib = ctypes.CDLL(SO)
-    return _lib
+    return hostbuild.load("measure")
 
 
 def em_single(l, lp, cnn, sphere, distance_measure="dotprod", init_vp=None, max_vp=64, sliced=False, lds_doubles=None,

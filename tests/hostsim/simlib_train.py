@@ -1,15 +1,10 @@
 """ctypes access to the TEST-ONLY host build of csrc/train_device.hpp (tests/hostsim/sim_train.cpp): the per-element
-functions of the dense head's training step.  A library of its own, built with g++ on first use."""
+functions of the dense head's training step.  A library of its own, built by hostbuild.py on first use."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-from . import simlib
-
-SO = os.path.join(simlib.BUILD, "libvpk_hostsim_train.so")
-SRC = [os.path.join(simlib.HERE, "sim_train.cpp"), os.path.join(simlib.CSRC, "train_device.hpp")]
+from . import hostbuild, simlib
 
 _lib = None
 
@@ -17,10 +12,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        os.makedirs(simlib.BUILD, exist_ok=True)
-        if (not os.path.exists(SO)) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", SRC[0], "-o", SO])
-        _lib = ctypes.CDLL(SO)
+        _lib = hostbuild.load("train")
         _lib.sim_train_learning_rate.restype = ctypes.c_float
         _lib.sim_train_learning_rate.argtypes = [ctypes.c_float, ctypes.c_float, ctypes.c_longlong, ctypes.c_longlong]
     return _lib

@@ -1,16 +1,10 @@
 """ctypes access to the TEST-ONLY host build of csrc/train_plan.hpp (tests/hostsim/sim_train_plan.cpp): what vpk_train.hip and
-vpk_convtrain.hip decide on the host before they launch.  A library of its own, built with g++ -Wall on first use."""
+vpk_convtrain.hip decide on the host before they launch.  A library of its own, built by hostbuild.py on first use."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-from . import simlib
-
-SO = os.path.join(simlib.BUILD, "libvpk_hostsim_train_plan.so")
-SRC = [os.path.join(simlib.HERE, "sim_train_plan.cpp"), os.path.join(simlib.HERE, "..", "..", "include", "vpk.h")] + \
-      [os.path.join(simlib.CSRC, f) for f in ("train_plan.hpp", "train_device.hpp", "convtrain_device.hpp")]
+from . import hostbuild
 
 _I, _F, _U = ctypes.c_int32, ctypes.c_float, ctypes.c_ulonglong
 OK, NO_CHAIN, LRN_WIDE = 0, 1, 2                                 # csrc/train_plan.hpp: StackRule
@@ -37,10 +31,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        os.makedirs(simlib.BUILD, exist_ok=True)
-        if (not os.path.exists(SO)) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-fPIC", "-shared", SRC[0], "-o", SO])
-        _lib = ctypes.CDLL(SO)
+        _lib = hostbuild.load("train_plan")
         _lib.sim_tp_vec.argtypes = [ctypes.c_int, _U, _U, _U, _U]
         _lib.sim_tp_slab_buffer.restype = _U
         _lib.sim_tp_rates.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]

@@ -1,28 +1,14 @@
 """ctypes access to the TEST-ONLY host build of csrc/trainset_device.hpp (tests/hostsim/sim_trainset.cpp): the per-element
-rules of the device-resident training set.  A library of its own, built with g++ on first use."""
+rules of the device-resident training set.  A library of its own, built by hostbuild.py on first use."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-from . import simlib
-
-SO = os.path.join(simlib.BUILD, "libvpk_hostsim_trainset.so")
-SRC = [os.path.join(simlib.HERE, "sim_trainset.cpp"), os.path.join(simlib.CSRC, "trainset_device.hpp"),
-       os.path.join(simlib.CSRC, "train_device.hpp")]
-
-_lib = None
+from . import hostbuild, simlib
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        os.makedirs(simlib.BUILD, exist_ok=True)
-        if (not os.path.exists(SO)) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", SRC[0], "-o", SO])
-        _lib = ctypes.CDLL(SO)
-    return _lib
+    return hostbuild.load("trainset")
 
 
 def _d(a):

@@ -1,29 +1,16 @@
 """ctypes access to the TEST-ONLY host build of vpset_run<MEASURE> (tests/hostsim/sim_vpset.cpp): the stand-alone counts
-and merge on one image under "angle", "dotprod" or "area".  A library of its own, built with g++ on first use."""
+and merge on one image under "angle", "dotprod" or "area".  A library of its own, built by hostbuild.py on first use."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-from . import simlib
+from . import hostbuild, simlib
 
-SO = os.path.join(simlib.BUILD, "libvpk_hostsim_vpset.so")
-SRC = [os.path.join(simlib.HERE, "sim_vpset.cpp")] + simlib.SRC[1:]
 MEASURES = {"angle": 0, "dotprod": 1, "area": 2}       # include/vpk.h: enum vpk_dist_measure
-
-_lib = None
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        os.makedirs(simlib.BUILD, exist_ok=True)
-        if (not os.path.exists(SO)) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                                   "-Wno-unknown-pragmas", SRC[0], "-o", SO])
-        _lib = ctypes.CDLL(SO)
-    return _lib
+    return hostbuild.load("vpset")
 
 
 def _c(a, dtype):

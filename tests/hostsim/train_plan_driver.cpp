@@ -3,8 +3,7 @@
 // refusals and limits, its buffers, the kept blobs' life cycle, the rates and the set_params rules -- walked in one process.
 // Made to be built with the host sanitizers and run on its own; it prints one line and returns 0 when every call answered as
 // expected:
-//     g++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=all
-//         tests/hostsim/train_plan_driver.cpp -o train_plan_driver && ./train_plan_driver
+//     python tests/hostsim/hostbuild.py drivers
 // No test runs it.
 #include <stdio.h>
 

@@ -1,17 +1,11 @@
 """csrc/batch_args.hpp -- the rules the batch drivers (vpk_vpset.hip, vpk_emstep.hip, vpk_estep.hip, vpk_lines.hip) hold their
 host offsets to -- compiled for the host by tests/hostsim/sim_batch_args.cpp, each rule at its edge.  CPU only."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-BUILD = os.path.join(HERE, "hostsim", "_build")
-SO = os.path.join(BUILD, "libvpk_hostsim_batch_args.so")
-SRC = [os.path.join(HERE, "hostsim", "sim_batch_args.cpp"), os.path.join(HERE, "..", "include", "vpk.h"),
-       os.path.join(HERE, "..", "vanishing_points_2017_amd", "csrc", "batch_args.hpp")]
+from hostsim import hostbuild
 
 OK, EMPTY, NEGATIVE, NULL, OFFSETS, VPS, LINES, SLOT = range(8)      # BatchRule
 VPK_OK, VPK_ERR_ARG, VPK_ERR_LIMIT = 0, -1, -5                       # include/vpk.h
@@ -21,10 +15,7 @@ LP = ctypes.POINTER(ctypes.c_int64)
 
 @pytest.fixture(scope="module")
 def sim():
-    os.makedirs(BUILD, exist_ok=True)
-    if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-fPIC", "-shared", SRC[0], "-o", SO])
-    lib = ctypes.CDLL(SO)
+    lib = hostbuild.load("batch_args")
     lib.sim_batch_offsets.argtypes = [ctypes.c_int, LP, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]
     lib.sim_batch_pair.argtypes = [ctypes.c_int, LP, LP, ctypes.c_longlong, ctypes.c_longlong]
     lib.sim_batch_slots.argtypes = [ctypes.c_int, LP, LP]

@@ -5,16 +5,10 @@ kernels take by value -- for every layer, field by field --, the work items of e
 im2col tap tables and the arena.  The expected values below are derived here from the net (channels, kernel, stride, padding, groups:
 deploy.prototxt) and from the tiles as the kernel headers' comments state them; they share no code with the header."""
 import ctypes
-import os
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIM = os.path.join(HERE, "hostsim")
-CSRC = os.path.join(HERE, "..", "vanishing_points_2017_amd", "csrc")
-SO = os.path.join(SIM, "_build", "libvpk_hostsim_cnn_model.so")
-SRC = [os.path.join(SIM, "sim_cnn_model.cpp"), os.path.join(CSRC, "cnn_model.hpp")]
+from hostsim import hostbuild
 
 BATCHES = [1, 4, 5, 102, 128, 129, 257, 4096]       # conv1's groups of 4, 128 / 256 columns, Winograd's 64 and 30 tiles; the largest chunk
 INT_MAX = 2 ** 31 - 1
@@ -50,10 +44,7 @@ def test_the_net_chains():
 
 @pytest.fixture(scope="module")
 def sim():
-    os.makedirs(os.path.dirname(SO), exist_ok=True)
-    if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-fPIC", "-shared", SRC[0], "-o", SO])
-    lib = ctypes.CDLL(SO)
+    lib = hostbuild.load("cnn_model")
     ll, i, f = ctypes.POINTER(ctypes.c_longlong), ctypes.c_int, ctypes.c_float
     dbl = ctypes.POINTER(ctypes.c_double)
     lib.sim_conv_dims.argtypes = [i, i, i, ll]

@@ -6,16 +6,11 @@ vpk_cnn_set_precision 0..3 x vpk_cnn_set_algorithm 0..4 x vpk_cnn_set_fusion 0..
 (and for vpk_cnn_forward_f32 / vpk_cnn_set_range_policy); it shares no code and no structure with the resolver."""
 import ctypes
 import itertools
-import os
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIM = os.path.join(HERE, "hostsim")
-CSRC = os.path.join(HERE, "..", "vanishing_points_2017_amd", "csrc")
-SO = os.path.join(SIM, "_build", "libvpk_hostsim_cnn_plan.so")
-SRC = [os.path.join(SIM, "sim_cnn_plan.cpp"), os.path.join(CSRC, "cnn_plan.hpp"), os.path.join(HERE, "..", "include", "vpk.h")]
+from hostsim import hostbuild
+
 
 # the enums of cnn_plan.hpp, in declaration order
 C1_GEMM, C1_DIRECT_F32, C1_GEMM_FUSED, C1_PIECES3, C1_PIECES2 = range(5)
@@ -28,10 +23,7 @@ MSG_FUSION4 = "vpk_cnn_forward_f32: vpk_cnn_set_fusion(4) takes uint8 rasters on
 
 @pytest.fixture(scope="module")
 def sim():
-    os.makedirs(os.path.dirname(SO), exist_ok=True)
-    if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-fPIC", "-shared", SRC[0], "-o", SO])
-    lib = ctypes.CDLL(SO)
+    lib = hostbuild.load("cnn_plan")
     lib.sim_cnn_plan.argtypes = [ctypes.c_int] * 8 + [ctypes.POINTER(ctypes.c_int), ctypes.c_char_p]
     lib.sim_cnn_plan.restype = None
     return lib

@@ -5,16 +5,13 @@ example.py's --detector flag, checked without a GPU.  The kernels themselves: te
 the tables below."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from hostsim import hostbuild
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-BUILD = os.path.join(HERE, "hostsim", "_build")
-SO = os.path.join(BUILD, "libvpk_hostsim_detect.so")
-SRC = [os.path.join(HERE, "hostsim", "sim_detect.cpp"),
-       os.path.join(HERE, "..", "vanishing_points_2017_amd", "csrc", "detect_device.hpp")]
 
 V, I = ctypes.c_void_p, ctypes.c_int
 ORDER_M = (0, 1, 2, 3, 15, 16, 17, 33, 63, 64)
@@ -24,10 +21,7 @@ PIXEL_DIMS = ((640, 480), (427, 640), (1, 1), (1048576, 3))
 
 
 def build_sim():
-    os.makedirs(BUILD, exist_ok=True)
-    if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", SRC[0], "-o", SO])
-    lib = ctypes.CDLL(SO)
+    lib = hostbuild.load("detect")
     lib.sim_vp_order.argtypes = [I, I, V, V, I, V]
     lib.sim_to_pixels.argtypes = [I, V, V, V, I] + [V] * 6
     return lib

@@ -5,9 +5,7 @@ takes every image of a ragged batch in turn, in one slot -- against the per-imag
 (tests/hostsim/simlib.py), and the reference's stored results (tests/golden/emstep/) against the extended references.
 The kernel itself: tests/test_gpu_emstep.py."""
 import ctypes
-import glob
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,14 +13,9 @@ import pytest
 import em_phase_reference as R
 import em_smoother_reference as S
 import emstep_cases as C
-from hostsim import simlib
+from hostsim import hostbuild, simlib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-BUILD = os.path.join(HERE, "hostsim", "_build")
-SO = os.path.join(BUILD, "libvpk_hostsim_emstep.so")
-CSRC = os.path.join(HERE, "..", "vanishing_points_2017_amd", "csrc")
-SRC = [os.path.join(HERE, "hostsim", "sim_emstep.cpp"), os.path.join(HERE, "hostsim", "hip_sim.hpp"),
-       os.path.join(HERE, "..", "include", "vpk.h")] + sorted(glob.glob(os.path.join(CSRC, "*.hpp")))
 
 D, L, I = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_longlong), ctypes.c_int
 IP, FP, BP = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_ubyte)
@@ -33,11 +26,7 @@ MSTEP_SHAPES = ((15, 5), (1, 1), (65, 33), (2, 4), (64, 64), (3, 32), (129, 4))
 
 @pytest.fixture(scope="module")
 def sim():
-    os.makedirs(BUILD, exist_ok=True)
-    if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wno-unknown-pragmas",
-                               SRC[0], "-o", SO])
-    lib = ctypes.CDLL(SO)
+    lib = hostbuild.load("emstep")
     lib.sim_weight_matrix_batch.argtypes = [I, L, L, D, D, L, D, ctypes.c_double, I, D]
     lib.sim_mstep_batch.argtypes = [I, L, L, D, D, D, D, L, D, ctypes.c_double, ctypes.c_double, D, D, D, IP, IP, D]
     lib.sim_init_vps_batch.argtypes = [I, FP, BP, I, I, D, IP, FP]

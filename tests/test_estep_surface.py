@@ -4,31 +4,20 @@ tests/hostsim/sim_estep.cpp and run serially against both, and the host side of 
 tests/test_gpu_estep_surface.py."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import em_phase_reference as E
 import estep_reference as R
+from hostsim import hostbuild
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-BUILD = os.path.join(HERE, "hostsim", "_build")
-SO = os.path.join(BUILD, "libvpk_hostsim_estep.so")
-CSRC = os.path.join(HERE, "..", "vanishing_points_2017_amd", "csrc")
-SRC = [os.path.join(HERE, "hostsim", "sim_estep.cpp"), os.path.join(HERE, "hostsim", "hip_sim.hpp"),
-       os.path.join(CSRC, "estep_device.hpp"), os.path.join(CSRC, "prior_device.hpp"), os.path.join(CSRC, "line_device.hpp"),
-       os.path.join(HERE, "..", "include", "vpk.h")]
 MEASURE_ID = {"angle": 0, "dotprod": 1, "area": 2}
 
 
 @pytest.fixture(scope="module")
 def sim():
-    os.makedirs(BUILD, exist_ok=True)
-    if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wno-unknown-pragmas",
-                               SRC[0], "-o", SO])
-    lib = ctypes.CDLL(SO)
+    lib = hostbuild.load("estep")
     D, L, I = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_longlong), ctypes.c_int
     lib.sim_estep_batch.argtypes = [I, L, L, D, D, D, D, D, I, I, D, D, D, D, D]
     return lib

@@ -48,8 +48,8 @@ def _hlw():
 
 
 @pytest.fixture(scope="module")
-def sim(tmp_path_factory):
-    return build_sim(tmp_path_factory.mktemp("sim_frontend_gpu"))
+def sim():
+    return build_sim()
 
 
 @pytest.fixture(scope="module")

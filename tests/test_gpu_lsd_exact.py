@@ -20,8 +20,8 @@ VPK_ERR_ARG = -1
 
 
 @pytest.fixture(scope="module")
-def port(tmp_path_factory):
-    run = build_sim(tmp_path_factory.mktemp("sim_lsd_exact"), "sim_lsd_portable")
+def port():
+    run = build_sim("sim_lsd_portable")
 
     def rows(images, scale):
         with ThreadPoolExecutor(8) as pool:                   # ctypes calls release the GIL

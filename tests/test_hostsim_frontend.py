@@ -3,26 +3,18 @@ the grey levels, rows -> lines) compiled for the host by tests/hostsim/sim_front
 Pillow's Image.resize(LANCZOS) (frontend.resize_to_fit), the grey formula of include/vpk.h (vpk_image_prepare_batch)
 and detect_lsd_lines + homogeneous_lines.  The kernels' orchestration is what tests/test_gpu_frontend_device.py covers."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 from PIL import Image
 
+from hostsim import hostbuild
 from vanishing_points_2017_amd import frontend
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIM_SRC = os.path.join(HERE, "hostsim", "sim_frontend.cpp")
 
-
-def build_sim(directory):
-    """Compile tests/hostsim/sim_frontend.cpp into `directory`; returns (prepare, rows_to_lines)."""
-    so = os.path.join(str(directory), "libvpk_hostsim_frontend.so")
-    if not os.path.exists(so):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-builtin", "-fPIC", "-shared",
-                               SIM_SRC, "-o", so])
-    lib = ctypes.CDLL(so)
+def build_sim():
+    """The host build of tests/hostsim/sim_frontend.cpp; returns (prepare, rows_to_lines)."""
+    lib = hostbuild.load("frontend")
     lib.sim_prepare.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 2
     lib.sim_rows_to_lines.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                       ctypes.c_void_p]
@@ -48,8 +40,8 @@ def build_sim(directory):
 
 
 @pytest.fixture(scope="module")
-def sim(tmp_path_factory):
-    return build_sim(tmp_path_factory.mktemp("sim_frontend"))
+def sim():
+    return build_sim()
 
 
 def grey_formula(image):

@@ -9,31 +9,24 @@ stay a faithful LSD: the detector contract of test_frontend.py, and the host det
 is held to.  Also: the argument checks of lsd.detect_line_segments_batch that need no GPU."""
 import ctypes
 import os
-import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
+from hostsim import hostbuild
 from test_frontend import _render
 from vanishing_points_2017_amd import _lib, lsd
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SIM_SRC = os.path.join(HERE, "hostsim", "sim_lsd.cpp")
 
 pytestmark = pytest.mark.skipif(not os.path.exists(_lib.SO_PATH), reason="libvpk.so not built")
 
 
-def build_sim(directory, export="sim_lsd"):
-    """Compile tests/hostsim/sim_lsd.cpp into `directory`; returns run(image, scale) -> the rows of `export` (sim_lsd:
-    libm, sim_lsd_portable: the portable math policy), all of them however many."""
-    so = os.path.join(str(directory), "libvpk_hostsim_lsd.so")
-    if not os.path.exists(so):
-        # -fno-builtin: g++ merges sin(a) and cos(a) into glibc's sincos, which differs from sin / cos in the last bit of
-        # some arguments; the product's host detector (clang) calls sin and cos
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-builtin", "-fPIC", "-shared",
-                               SIM_SRC, "-o", so])
-    fn = getattr(ctypes.CDLL(so), export)
+def build_sim(export="sim_lsd"):
+    """The host build of tests/hostsim/sim_lsd.cpp; returns run(image, scale) -> the rows of `export` (sim_lsd: libm,
+    sim_lsd_portable: the portable math policy), all of them however many."""
+    fn = getattr(hostbuild.load("lsd"), export)
     fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_int,
                    ctypes.POINTER(ctypes.c_int)]
 
@@ -53,18 +46,13 @@ def build_sim(directory, export="sim_lsd"):
 
 
 @pytest.fixture(scope="module")
-def sim_dir(tmp_path_factory):
-    return tmp_path_factory.mktemp("sim_lsd")
+def sim():
+    return build_sim()
 
 
 @pytest.fixture(scope="module")
-def sim(sim_dir):
-    return build_sim(sim_dir)
-
-
-@pytest.fixture(scope="module")
-def sim_portable(sim_dir):
-    return build_sim(sim_dir, "sim_lsd_portable")
+def sim_portable():
+    return build_sim("sim_lsd_portable")
 
 
 def _strokes(seed, n, h, w, noise):

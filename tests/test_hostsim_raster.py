@@ -10,16 +10,13 @@ atomics, simplify_kernel's wave machine, blend_kernel's fetch pipeline, tables a
 rasters (tests/golden) and the restatement oracle/agg_raster.py."""
 import functools
 import os
-import sys
 
 import numpy as np
 import pytest
 
 from golden_util import load
+from hostsim import simlib
 from oracle import agg_raster
-
-sys.path.insert(0, os.path.join(os.path.dirname(__file__), "hostsim"))
-import simlib  # noqa: E402
 
 
 GOLDENS = ["tiny_n12", "clean3_n60", "noweights_n100", "yud_n330", "stress_n300"]

@@ -2,20 +2,12 @@
 serially, and the argument rules of vp_localisation's Python layer, against the references and bars of
 tests/line_geometry_reference.py.  The kernels themselves: tests/test_gpu_line_geometry.py."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import line_geometry_reference as R
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-BUILD = os.path.join(HERE, "hostsim", "_build")
-SO = os.path.join(BUILD, "libvpk_hostsim_lines.so")
-CSRC = os.path.join(HERE, "..", "vanishing_points_2017_amd", "csrc")
-SRC = [os.path.join(HERE, "hostsim", "sim_lines.cpp"), os.path.join(HERE, "hostsim", "hip_sim.hpp"),
-       os.path.join(CSRC, "line_device.hpp"), os.path.join(CSRC, "prior_device.hpp")]
+from hostsim import hostbuild
 
 D, Q, I = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_longlong), ctypes.c_int
 SENTINEL = -7.25
@@ -23,10 +15,7 @@ SENTINEL = -7.25
 
 @pytest.fixture(scope="module")
 def sim():
-    os.makedirs(BUILD, exist_ok=True)
-    if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", SRC[0], "-o", SO])
-    lib = ctypes.CDLL(SO)
+    lib = hostbuild.load("lines")
     lib.sim_line_similarity.argtypes = [I, Q, D, ctypes.c_double, Q, D]
     lib.sim_line_rating.argtypes = [I, Q, D, I, I, ctypes.c_double, D, D, D, I]
     return lib

@@ -3,18 +3,11 @@ batch's images are held to, every image's slice of the workspace and the chunks 
 the host by tests/hostsim/sim_lsd_plan.cpp, each rule and the limit at their edges.  CPU only: no GPU, no libvpk.so."""
 import ctypes
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-BUILD = os.path.join(HERE, "hostsim", "_build")
-SO = os.path.join(BUILD, "libvpk_hostsim_lsd_plan.so")
-CSRC = os.path.join(HERE, "..", "vanishing_points_2017_amd", "csrc")
-SRC = [os.path.join(HERE, "hostsim", "sim_lsd_plan.cpp"), os.path.join(HERE, "..", "include", "vpk.h")] + \
-      [os.path.join(CSRC, f) for f in ("lsd_plan.hpp", "lsd_device.hpp", "lsd_portable_math.hpp")]
+from hostsim import hostbuild
 
 OK, SIDE, OFFSETS, DIM, PIXELS = range(5)                            # PlanRule, in the order the driver checks an image
 VPK_OK, VPK_ERR_ARG, VPK_ERR_LIMIT = 0, -1, -5                       # include/vpk.h
@@ -24,10 +17,7 @@ ARRAYS = ("aux", "scaled", "ang", "grad", "order", "reg", "used")
 
 @pytest.fixture(scope="module")
 def sim():
-    os.makedirs(BUILD, exist_ok=True)
-    if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-fPIC", "-shared", SRC[0], "-o", SO])
-    lib = ctypes.CDLL(SO)
+    lib = hostbuild.load("lsd_plan")
     lib.sim_lsd_plan.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_ulonglong] + \
         [ctypes.c_void_p] * 4 + [ctypes.c_int] + [ctypes.c_void_p] * 3
     assert lib.sim_lsd_plan_meta_bytes() == META

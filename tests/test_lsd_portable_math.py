@@ -5,16 +5,14 @@ are the header's: 2 ulp for atan2, sin, cos, exp, log; 4 ulp for log10, pow, sin
 finite, deterministic results outside those domains."""
 import ctypes
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from hostsim import hostbuild
+
 mpmath = pytest.importorskip("mpmath")
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-DRIVER = os.path.join(HERE, "hostsim", "pm_driver.cpp")
 N = 100000
 FN = {"atan2": 0, "sin": 1, "cos": 2, "exp": 3, "log": 4, "log10": 5, "pow": 6, "sinh": 7}
 BOUND = {"atan2": 2, "sin": 2, "cos": 2, "exp": 2, "log": 2, "log10": 4, "pow": 4, "sinh": 4}
@@ -23,10 +21,8 @@ TINY = 5e-324
 
 
 @pytest.fixture(scope="module")
-def pm(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("pm") / "libvpk_pm.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", DRIVER, "-o", so])
-    lib = ctypes.CDLL(so)
+def pm():
+    lib = hostbuild.load("pm")
     lib.pm_eval.argtypes = [ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
 
     def run(name, a, b=None):

@@ -3,30 +3,18 @@ serially, against the NumPy restatement of DESIGN section 7d (tests/overlay_refe
 and result_plotting's Python layer -- draw lists, best-VP order, panels -- without a GPU (where it needs pixels, the host
 build stands in for the kernels).  The kernels themselves: tests/test_gpu_overlay.py."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import overlay_reference as R
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-BUILD = os.path.join(HERE, "hostsim", "_build")
-SO = os.path.join(BUILD, "libvpk_hostsim_overlay.so")
-CSRC = os.path.join(HERE, "..", "vanishing_points_2017_amd", "csrc")
-SRC = [os.path.join(HERE, "hostsim", "sim_overlay.cpp"), os.path.join(HERE, "hostsim", "hip_sim.hpp"),
-       os.path.join(CSRC, "overlay_device.hpp"), os.path.join(CSRC, "line_device.hpp"), os.path.join(CSRC, "prior_device.hpp")]
+from hostsim import hostbuild
 
 GUARD, FILL = 64, 0xA5
 
 
 def _sim():
-    os.makedirs(BUILD, exist_ok=True)
-    if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wno-unknown-pragmas", SRC[0],
-                               "-o", SO])
-    lib = ctypes.CDLL(SO)
+    lib = hostbuild.load("overlay")
     lib.sim_overlay.argtypes = [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 7
     return lib
 

@@ -2,27 +2,17 @@
 and the host side of probability_functions, against the reference's stored output (tests/golden/prior/prior_pdf.npz).  The
 kernels themselves: tests/test_gpu_prior_pdf.py."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import prior_reference as R
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-BUILD = os.path.join(HERE, "hostsim", "_build")
-SO = os.path.join(BUILD, "libvpk_hostsim_prior.so")
-SRC = [os.path.join(HERE, "hostsim", "sim_prior.cpp"), os.path.join(HERE, "hostsim", "hip_sim.hpp"),
-       os.path.join(HERE, "..", "vanishing_points_2017_amd", "csrc", "prior_device.hpp")]
+from hostsim import hostbuild
 
 
 @pytest.fixture(scope="module")
 def sim():
-    os.makedirs(BUILD, exist_ok=True)
-    if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", SRC[0], "-o", SO])
-    lib = ctypes.CDLL(SO)
+    lib = hostbuild.load("prior")
     D, F, I = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.c_int
     lib.sim_prior_params.argtypes = [I, F, ctypes.c_double, F]
     lib.sim_mixture_pdf.argtypes = [I, I, D, I, D, ctypes.c_double, I, D, I, I, D, D]

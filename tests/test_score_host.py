@@ -17,16 +17,13 @@ auc.calc_auc at every n.  One error alone is held to the restatement too: calc_a
 no vector left to sort."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from hostsim import hostbuild
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-BUILD = os.path.join(HERE, "hostsim", "_build")
-SO = os.path.join(BUILD, "libvpk_hostsim_score.so")
-SRC = [os.path.join(HERE, "hostsim", "sim_score.cpp"),
-       os.path.join(HERE, "..", "vanishing_points_2017_amd", "csrc", "score_device.hpp")]
 
 V, I, D = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
 ERROR_DIMS = ((640, 480), (427, 640), (1, 1))
@@ -36,10 +33,7 @@ CUTOFF = 0.25
 
 
 def build_sim():
-    os.makedirs(BUILD, exist_ok=True)
-    if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", SRC[0], "-o", SO])
-    lib = ctypes.CDLL(SO)
+    lib = hostbuild.load("score")
     lib.sim_horizon_error.argtypes = [I, V, V, V, V]
     lib.sim_auc.argtypes = [I, V, D, V, V]
     return lib
