@@ -6,6 +6,8 @@
 
 #include <type_traits>
 
+#include "cnn_prims.hpp"   // f32x2, f32x4, lds_barrier, TileQueue
+
 namespace {
 
 // --------------------------------------------------------------------------------------------
@@ -23,8 +25,6 @@ namespace {
 //     (windows clipped like Caffe) -> 3 x 8 pooled outputs per channel, written with conv2's border.
 // Neighbouring patches share one conv row / column (1.24x the MFMA work); conv1's 0.59 GB blob (B = 102) never exists.
 // --------------------------------------------------------------------------------------------
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) const f32x2 lds_cf32x2;
 typedef __attribute__((address_space(3))) const float lds_cfloat;
 constexpr int C1D_THREADS = 512;
@@ -36,12 +36,8 @@ constexpr int C1D_KS = 31;                            // K steps of 4 taps: 121 
 constexpr int C1D_LD = 132;                           // row stride of the output patch [channel][column]: the four row groups
                                                       // a wave writes at once (rows 4 apart) hit disjoint bank quarters
 
-// workgroup barrier that orders LDS traffic only: the pooled outputs' global stores stay in flight across it
-// (__syncthreads also waits for vmcnt(0), i.e. one HBM write round trip per tile)
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-}
+// (the barriers are lds_barrier(), cnn_prims.hpp: the pooled outputs' global stores stay in flight across them, where
+//  __syncthreads would wait for one HBM write round trip per tile)
 
 #ifdef C1D_TIME
 __device__ long long c1d_dbg[256 * 8 * 8];
@@ -60,6 +56,7 @@ __global__ __launch_bounds__(C1D_THREADS, 2) void conv1_direct_kernel(const Px* 
     __shared__ __attribute__((aligned(16))) float Xs[C1D_XS];
     __shared__ __attribute__((aligned(16))) float Cs[96 + 4][C1D_LD];  // channel c in row c + 2; rows 0, 1, 98, 99 stay 0 (LRN halo)
     __shared__ int s_next[2];
+    TileQueue queue{s_next};
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, c16 = lane & 15;
     if (tid < C1D_LD) Cs[0][tid] = Cs[1][tid] = Cs[98][tid] = Cs[99][tid] = 0.f;
@@ -149,15 +146,16 @@ __global__ __launch_bounds__(C1D_THREADS, 2) void conv1_direct_kernel(const Px* 
                 }
             }
     };
-    // dynamic tile queue (CUs held by other streams' kernels make static shares uneven); the index of the tile after
-    // next is fetched one tile ahead, so the atomic's round trip is never waited for
+    // The tile queue (cnn_prims.hpp) TWO tiles ahead: `next`'s patch is loaded under `tile`'s MFMAs, so the index of the tile after
+    // next is what a tile fetches -- the compiler's atomicAdd at its top, consumed (stored, read back) only at its end, so that the
+    // atomic's round trip is never waited for.  The slots alternate with the iteration, not with a parity of the queue's.
     int tile = blockIdx.x;
     f32x4 pre[PRE];
     Raw pre8[PRE];
     if (tile < total_tiles) { patch_load(tile, pre, pre8); patch_store(pre, pre8); }
-    if (tid == 0) s_next[0] = atomicAdd(tile_counter, 1) + (int)gridDim.x;
+    queue.take(tile_counter, 0);
     __syncthreads();
-    int next = __builtin_amdgcn_readfirstlane(s_next[0]);
+    int next = queue.peek(0);
     // Software pipeline across tiles: the LRN and the pooling of tile i-1 are issued between the MFMA steps of tile i, so
     // that per tile only "accumulators -> Cs" and "Cs -> LRN inputs" stand alone between barriers.  f32 MFMAs run at the
     // packed-f32 vector rate and do NOT overlap with VALU work of either wave of the SIMD (measured: a phase costs the
@@ -289,7 +287,7 @@ __global__ __launch_bounds__(C1D_THREADS, 2) void conv1_direct_kernel(const Px* 
         C1D_T(7)
         ptile = tile;
         tile = next;
-        next = __builtin_amdgcn_readfirstlane(s_next[(it + 1) & 1]);
+        next = queue.peek((it + 1) & 1);
     }
     if (ptile >= 0) {                                               // drain: the last tile's epilogue
         lrn_squares();

@@ -1,5 +1,5 @@
 // cnn_conv1_pieces.hpp -- conv1 + relu1 + norm1 + pool1 (cnn/deploy.prototxt:9-55) on the bf16 matrix cores with EXACT
-// operands.  Included by vpk_cnn.hip (after cnn_split_gemm.hpp: bf16x8; cnn_conv1_direct.hpp: lds_barrier, C1D_LD; cnn_gemm_f32.hpp: C1_* constants).
+// operands.  Included by vpk_cnn.hip (after cnn_split_gemm.hpp: split3; cnn_pairs.hpp: split2h_guard).
 //
 // conv1's input is an 8-bit raster (evaluation.py:34-38: float(image) - mean, no scaling).  An integer 0..255 IS a bf16
 // number (8 significant bits), every f32 weight is exactly the sum of three bf16 pieces (cnn_split_gemm.hpp), a product of
@@ -33,6 +33,8 @@
 #ifndef VPK_CNN_CONV1_PIECES_HPP_
 #define VPK_CNN_CONV1_PIECES_HPP_
 
+#include "cnn_prims.hpp"   // the vector types, lds_barrier, TileQueue
+
 namespace {
 
 constexpr int C1B_THREADS = 768;
@@ -42,8 +44,6 @@ constexpr int C1B_LDW = C1B_PCOLS;                     // row stride of the raw 
 constexpr int C1B_XS = C1B_PROWS * C1B_LDW;            // bf16 per patch buffer
 constexpr int C1B_STEPS = 6;                           // K steps of 32
 
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) const u32x2 lds_cu32x2;
 
 // max |w| -> the power of two that puts it in [2^13, 2^14): the scale of a layer's fp16-pair weights (1 for all-zero weights)
@@ -162,6 +162,7 @@ __global__ __launch_bounds__(C1B_THREADS, 3) void conv1_pieces_kernel(const Px* 
     // floats = 27 x 16 bytes keeps the 16 lanes of a quarter wave (consecutive columns) on different banks.
     __shared__ __attribute__((aligned(16))) float Ct[128][C1T_LD];
     __shared__ int s_next[2];
+    TileQueue queue{s_next};                                             // (cnn_prims.hpp; the immediate form, one item ahead)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int mtile = wave % 6, chalf = wave / 6;
@@ -237,7 +238,7 @@ __global__ __launch_bounds__(C1B_THREADS, 3) void conv1_pieces_kernel(const Px* 
     int pr = (item % C1B_PATCHES) / C1_TC, pc = item % C1_TC;
     int b = (item / C1B_PATCHES) * group;
     int b1 = b + group < batch ? b + group : batch;
-    if (tid == 0) s_next[0] = atomicAdd(item_counter, 1) + (int)gridDim.x;
+    queue.take(item_counter, 0);
     int poff = patch_offset(pr, pc);
     patch_store(*reinterpret_cast<const Raw*>(sphere + (size_t)b * 250000 + poff), 0);
     bool fresh = true;                                                   // first tile of a work item: fetch its constants
@@ -334,7 +335,7 @@ __global__ __launch_bounds__(C1B_THREADS, 3) void conv1_pieces_kernel(const Px* 
         int n_item = item, n_pr = pr, n_pc = pc, n_b = b + 1, n_b1 = b1;
         bool n_fresh = false;
         if (n_b >= b1) {
-            n_item = __builtin_amdgcn_readfirstlane(s_next[parity]);
+            n_item = queue.peek(parity);
             n_pr = (n_item % C1B_PATCHES) / C1_TC; n_pc = n_item % C1_TC;
             n_b = (n_item / C1B_PATCHES) * group;
             n_b1 = n_b + group < batch ? n_b + group : batch;
@@ -365,7 +366,7 @@ __global__ __launch_bounds__(C1B_THREADS, 3) void conv1_pieces_kernel(const Px* 
         float raw[20];
         {
             const float* rp = &Ct[lp][16 * lcg + 2];                     // channels 16 lcg - 2 ..: 8 bytes, 4 x 16 bytes, 8 bytes
-            const f32x2v a = *reinterpret_cast<const f32x2v*>(rp), z = *reinterpret_cast<const f32x2v*>(rp + 18);
+            const f32x2 a = *reinterpret_cast<const f32x2*>(rp), z = *reinterpret_cast<const f32x2*>(rp + 18);
             raw[0] = a[0]; raw[1] = a[1]; raw[18] = z[0]; raw[19] = z[1];
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {
@@ -397,6 +398,8 @@ __global__ __launch_bounds__(C1B_THREADS, 3) void conv1_pieces_kernel(const Px* 
             }
         }
         if (n_on) patch_store(pre, buf ^ 1);                             // (that buffer was last read in the previous tile's K loop)
+        // (queue.take(item_counter, parity ^ 1) under this kernel's own condition, in this order of its terms: as a call the kernel's
+        //  code comes out differently)
         if (n_fresh && tid == 0 && n_on) s_next[parity ^ 1] = atomicAdd(item_counter, 1) + (int)gridDim.x;
         lds_barrier();
         // ---- 3 x 3 / stride 2 max pool: (channel, pooled row, half) = 4 outputs from 3 x 9 values ----

@@ -1,5 +1,5 @@
 // cnn_conv_pieces.hpp -- conv2..conv5 of cnn/deploy.prototxt (:56-174) as DIRECT convolutions on the matrix cores with the f32
-// operands cut into 16-bit pieces whose products are exact.  Included by vpk_cnn.hip (after cnn_split_gemm.hpp: bf16x8, split3, dma16).
+// operands cut into 16-bit pieces whose products are exact.  Included by vpk_cnn.hip (after cnn_split_gemm.hpp: split3; cnn_pairs.hpp: split2h).
 //
 // Arithmetic.  Two ways to cut an f32 number (template parameter NP):
 //   NP = 3  three bf16 pieces, EXACT (8 + 8 + 8 significand bits); of the nine partial products the six with i + j <= 2 carry
@@ -38,6 +38,8 @@
 // (timing ablations in DESIGN.md section 8: the patch DMA's completion is tied to the weight waits by the in-order vmcnt).
 #ifndef VPK_CNN_CONV_PIECES_HPP_
 #define VPK_CNN_CONV_PIECES_HPP_
+
+#include "cnn_prims.hpp"   // the vector types, LDS-DMA, waits, TileQueue
 
 namespace {
 
@@ -95,15 +97,14 @@ __global__ __launch_bounds__(256) void to_planes_kernel(const float* __restrict_
 
 template <int N>
 __device__ __forceinline__ void cp_wait() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+    wait_vmcnt<N>();
     __builtin_amdgcn_sched_barrier(0);           // (nothing that reads a loaded register moves above the wait)
 }
 
-// A 16-byte global load the COMPILER DOES NOT KNOW TO BE A LOAD (round 5).  hipcc keeps a scoreboard of the vector-memory operations it
-// has emitted and puts its own s_waitcnt in front of the first use of a loaded register; with LDS-DMA issued from inline asm in between
-// (which it cannot count) it falls back to `s_waitcnt vmcnt(0)` -- in front of every K16 step's first matrix instruction in the first
-// version, which turned "weights two steps ahead" into "everything in flight must land now".  Issued from asm, completion is counted
-// by hand (cp_wait: a bare s_waitcnt and a scheduling barrier; a wait that names the registers as "+v" operands makes hipcc COPY them
+// A 16-byte global load the COMPILER DOES NOT KNOW TO BE A LOAD (round 5; the general reason: cnn_prims.hpp).  With LDS-DMA issued from
+// inline asm between its own loads hipcc fell back to `s_waitcnt vmcnt(0)` in front of every K16 step's first matrix instruction in the
+// first version, which turned "weights two steps ahead" into "everything in flight must land now".  Issued from asm, completion is counted
+// by hand (cp_wait: the counted wait and a scheduling barrier; a wait that names the registers as "+v" operands makes hipcc COPY them
 // into the asm's operand registers BEFORE the wait -- stale data).  The destination is a "+v" operand -- the load overwrites the
 // register the variable already lives in -- so that the compiler has no fresh value to copy into place either.
 template <int OFF>
@@ -171,7 +172,7 @@ __global__ __launch_bounds__(CP_THREADS, 2) void conv_pieces_kernel(PieceDims d,
     const int wmq = RH == 1 ? wave : (wave & 1);             // this wave: block wmq of the tile's output channels,
     const int rh = RH == 1 ? 0 : (wave >> 1);                //            rows rh * NB .. + NB - 1 of the tile
     const int n31 = lane & 31, kh_ = lane >> 5;
-    const unsigned lds0 = lds_addr(cp_lds);
+    const unsigned lds0 = lds_addr_of(cp_lds);
     typedef __attribute__((address_space(3))) const bf16x8 lds_cbf8;
     // a lane's B operand for pixel column n31 + kw: word ((column / 8) * 64 + row * 8 + column % 8) of plane (piece, k half = lane / 32)
     unsigned vb[KH];
@@ -181,6 +182,9 @@ __global__ __launch_bounds__(CP_THREADS, 2) void conv_pieces_kernel(PieceDims d,
         vb[kw] = lds0 + (unsigned)(kh_ * PLANE + rh * NB * 128) + (c >> 3) * (unsigned)GST + (c & 7u) * 16u;
     }
     const unsigned voff_a = (unsigned)lane * 16u;
+    // The tile queue's protocol (TileQueue, cnn_prims.hpp: request, publish, next) WRITTEN OUT, the one kernel that does: through the
+    // queue's members s_next[parity] is reached through a pointer, the optimiser's address arithmetic loses a no-wrap flag, and two
+    // variants of this kernel (3 x 3 on pairs, RH = 1 and 2) -- no register to spare -- come out with other scalar spills.
     int parity = 0;
     for (int tile = blockIdx.x; tile < total_tiles;) {
         int nx = 0;
@@ -210,8 +214,8 @@ __global__ __launch_bounds__(CP_THREADS, 2) void conv_pieces_kernel(PieceDims d,
             const int pl = q1 / KPP, kk = q1 - pl * KPP;     // wave-uniform
             const unsigned char* src = in_g + ((size_t)cg * NPL + pl) * plane_bytes + (size_t)kk * 128;
             const unsigned dst = lds0 + (unsigned)((cg & 1) * PBUF + pl * PLANE + kk * GST);
-            if (PARTS == 1 || part == 0) dma16(voff_p, src, __builtin_amdgcn_readfirstlane(dst));
-            else if (lane < 8 * (PR - 8)) dma16(voff_p2, src, __builtin_amdgcn_readfirstlane(dst + 1024u));   // (masked lanes write nothing)
+            if (PARTS == 1 || part == 0) lds_dma16(voff_p, src, __builtin_amdgcn_readfirstlane(dst));
+            else if (lane < 8 * (PR - 8)) lds_dma16(voff_p2, src, __builtin_amdgcn_readfirstlane(dst + 1024u));   // (masked lanes write nothing)
         };
         // ---- weights: this wave's three fragments (pieces) of a K16 step, 16 bytes per lane each, straight from L2 into registers ----
         const unsigned char* wgrp = reinterpret_cast<const unsigned char*>(wfrag) +
@@ -245,12 +249,12 @@ __global__ __launch_bounds__(CP_THREADS, 2) void conv_pieces_kernel(PieceDims d,
         // The accumulators are register PAIRS that only inline asm adds to (cp_fold): left to the compiler, the sum of accumulator and
         // block sum lands in the block sum's registers, the accumulators wander between two homes over the unrolled blocks and
         // ~30 of them are spilled (and every scratch reload is a `s_waitcnt vmcnt(0)` on the weights in flight).
-        f32x2v acc[NB][8];
+        f32x2 acc[NB][8];
         f32x16 tq[NB];
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) acc[j][e] = f32x2v{0.f, 0.f};
+            for (int e = 0; e < 8; ++e) acc[j][e] = f32x2{0.f, 0.f};
 #pragma unroll
             for (int e = 0; e < 16; ++e) tq[j][e] = 0.f;
         }
@@ -267,8 +271,7 @@ __global__ __launch_bounds__(CP_THREADS, 2) void conv_pieces_kernel(PieceDims d,
         const unsigned char* anext = wgrp + (size_t)D * wstep;   // the next weights to request (step s + D behind step s; none behind the last D)
         cp_wait<0>();
         if (tid == 0) s_next[parity] = nx + (int)gridDim.x;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();                        // patch 0 is complete for every wave
+        lds_barrier();                                       // patch 0 is complete for every wave
         fetch_all(std::integral_constant<int, 0>(), 0u);
         // The matrix instructions of one tile row (the products of a K16 step, the small ones first) into its block sum.  FIRST: the step
         // opens a block -- the first product starts from zero (C = 0: no register clearing).  (A row's instructions form a dependent
@@ -295,8 +298,8 @@ __global__ __launch_bounds__(CP_THREADS, 2) void conv_pieces_kernel(PieceDims d,
             asm volatile("s_nop 7" ::: "memory");
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const f32x2v t2 = {tq[j][2 * e], tq[j][2 * e + 1]};
-                f32x2v& a2 = acc[j][e];                      // (a plain use: an asm operand alone does not make the lambda capture `acc`)
+                const f32x2 t2 = {tq[j][2 * e], tq[j][2 * e + 1]};
+                f32x2& a2 = acc[j][e];                      // (a plain use: an asm operand alone does not make the lambda capture `acc`)
                 asm volatile("v_pk_add_f32 %0, %0, %1" : "+v"(a2) : "v"(t2));
             }
         };
@@ -406,11 +409,11 @@ __global__ __launch_bounds__(CP_THREADS, 2) void conv_pieces_kernel(PieceDims d,
             const unsigned char* obase = reinterpret_cast<const unsigned char*>(out + ((size_t)e_b * d.groups + e_g) * d.OC * plane);
             const int oh0 = e_rt * TR + rh * NB;             // this wave's first row of the blob
             const unsigned vo0 = ((unsigned)(4 * e_kh) * plane + (unsigned)((oh0 + d.opad) * d.OWp + ow + d.opad)) * 4u;
-            f32x4v bl[4];
+            f32x4 bl[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {                    // this lane's 4 rows of each 8-row slice (the packed weights' padding rows: clamped)
                 const int m0 = m_blk + 8 * q < d.OC ? m_blk + 8 * q : d.OC - 8;
-                bl[q] = *reinterpret_cast<const f32x4v*>(bias + e_g * d.OC + m0 + 4 * e_kh);
+                bl[q] = *reinterpret_cast<const f32x4*>(bias + e_g * d.OC + m0 + 4 * e_kh);
             }
             if (NP == 2 && out_planes) {
                 // the NEXT layer's input: fp16 pairs of o_ascale x (ReLU(result)) in its piece planes (interior only: the border is the

@@ -1,5 +1,5 @@
 // cnn_dense_pieces.hpp -- fc6 of cnn/deploy.prototxt (:192-210: InnerProduct 57 600 -> 4 096, weights (out, in)) on the bf16 matrix
-// cores with exact operands.  Included by vpk_cnn.hip (after cnn_split_gemm.hpp: bf16x8, split3, dma16, lds_addr).
+// cores with exact operands.  Included by vpk_cnn.hip (after cnn_split_gemm.hpp: split3; cnn_pairs.hpp: split2h).
 //
 // Why: at B = 102 the layer is 48 GFLOP over a 0.94 GB weight matrix.  On the f32-input matrix instructions (157 TF) the products
 // take 0.31 ms at peak -- longer than streaming the weights from HBM (0.17 ms at 5.5 TB/s) -- so the layer was matrix-pipe-bound
@@ -18,6 +18,8 @@
 //     addition; split-K partials are reduced by splitk_reduce_kernel in a fixed order (deterministic).
 #ifndef VPK_CNN_DENSE_PIECES_HPP_
 #define VPK_CNN_DENSE_PIECES_HPP_
+
+#include "cnn_prims.hpp"   // the vector types, LDS-DMA, waits, TileQueue
 
 namespace {
 
@@ -41,10 +43,10 @@ __global__ __launch_bounds__(256) void dense_split_kernel(const float* __restric
     const int n = nt * DP_BN + 32 * j + (lane & 31), h = lane >> 5;
     float v[16];
     if (n < N) {
-        const f32x4v* src = reinterpret_cast<const f32x4v*>(x + (size_t)n * K + (size_t)c * DP_CHUNK + 16 * h);
+        const f32x4* src = reinterpret_cast<const f32x4*>(x + (size_t)n * K + (size_t)c * DP_CHUNK + 16 * h);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const f32x4v t = src[q];
+            const f32x4 t = src[q];
             v[4 * q] = t[0]; v[4 * q + 1] = t[1]; v[4 * q + 2] = t[2]; v[4 * q + 3] = t[3];
         }
     } else {
@@ -91,9 +93,9 @@ __global__ void dense_tile_weights_kernel(const float* __restrict__ w, float* __
     const int c = (int)(tc % chunks);
     const int mt = (int)(tc / chunks);
     const int row = mt * DP_BM + r;
-    f32x4v v = {0.f, 0.f, 0.f, 0.f};
-    if (row < OC) v = *reinterpret_cast<const f32x4v*>(w + (size_t)row * K + (size_t)c * DP_CHUNK + 4 * kk4);
-    reinterpret_cast<f32x4v*>(out)[o4] = v;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (row < OC) v = *reinterpret_cast<const f32x4*>(w + (size_t)row * K + (size_t)c * DP_CHUNK + 4 * kk4);
+    reinterpret_cast<f32x4*>(out)[o4] = v;
 }
 
 // fp16 pairs, PRE-SPLIT (round 6): a scaled pair is 2 + 2 bytes -- exactly an f32 weight's four -- so the weights can be stored as the
@@ -123,6 +125,65 @@ __global__ void dense_pair_weights_kernel(const float* __restrict__ w, unsigned 
     reinterpret_cast<u32x4*>(out)[o] = w4;
 }
 
+// ---- what dense_pairs_kernel and dense_pieces_kernel share: the work item, the B fragments' DMA and wait, the fold, the partials.
+//      (Theirs alone: the weight loads, the register sets, the split in registers, the product order.)  How a helper takes its
+//      arguments -- the item through a reference, the partials' dimensions as scalars -- is what leaves the kernels' code as it was. ----
+typedef __attribute__((address_space(3))) const bf16x8 lds_cbf8;
+// work item -> (row tile mt, column tile nt, k part ks = chunks c0 .. c1 - 1)
+struct DenseItem { int mt, nt, ks, c0, c1; };
+__device__ __forceinline__ void dense_item(const DenseDims& d, int item, DenseItem& it) {
+    int t = item;
+    it.mt = t % d.mtiles; t /= d.mtiles;
+    it.nt = t % d.ntiles;
+    it.ks = t / d.ntiles;
+    it.c0 = it.ks * d.cpp;
+    it.c1 = it.c0 + d.cpp < d.chunks ? it.c0 + d.cpp : d.chunks;
+}
+// chunk c's B fragments -> stage c % DP_NST: 8 NP fragments of 1 KB, wave w brings NP w .. NP w + NP - 1
+template <int NP>
+__device__ __forceinline__ void dense_issue_b(const unsigned char* xsrc, unsigned lds0, int c, int wave, int lane) {
+    const unsigned char* src = xsrc + (size_t)c * DP_STAGE<NP>;
+    const unsigned dst = lds0 + (unsigned)((c % DP_NST) * DP_STAGE<NP>);
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+        const int f = NP * wave + k;
+        lds_dma16((unsigned)(f * 1024 + lane * 16), src, __builtin_amdgcn_readfirstlane(dst + (unsigned)f * 1024u));
+    }
+}
+// chunk c's weights and B fragments (own pieces) have landed; younger: chunk c + 1's 4 + NP requests (`more`: there is one)
+template <int NP>
+__device__ __forceinline__ void dense_wait_chunk(bool more) {
+    if (more) wait_vmcnt<4 + NP>(); else wait_vmcnt<0>();
+}
+// the block sum joins the accumulators after DP_FOLD chunks and behind the item's last chunk
+__device__ __forceinline__ void dense_fold(f32x16 (&acc)[4], f32x16 (&tq)[4], int& fold, int c, int c1) {
+    if (++fold == DP_FOLD || c + 1 == c1) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            acc[j] += tq[j];
+#pragma unroll
+            for (int e = 0; e < 16; ++e) tq[j][e] = 0.f;
+        }
+        fold = 0;
+    }
+}
+// partials [k part][image][output]: accumulator register 4 q + e = row 8 q + 4 h + e of this wave's 32-row block
+__device__ __forceinline__ void dense_store_partials(int N, int OC, float oscale, int mt, int nt, int ks, const f32x16 (&acc)[4], float* part,
+                                                     int wave, int r31, int h) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int n = nt * DP_BN + 32 * j + r31;
+        if (n >= N) continue;
+        float* prow = part + ((size_t)ks * N + n) * OC + mt * DP_BM + 32 * wave + 4 * h;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (mt * DP_BM + 32 * wave + 8 * q >= OC) continue;
+            f32x4 v4 = {acc[j][4 * q] * oscale, acc[j][4 * q + 1] * oscale, acc[j][4 * q + 2] * oscale, acc[j][4 * q + 3] * oscale};
+            *reinterpret_cast<f32x4*>(prow + 8 * q) = v4;
+        }
+    }
+}
+
 // the loop on pre-split pairs: per chunk and wave four 16-byte loads (2 steps x 2 pieces) three chunks deep (three register sets:
 // the set of chunk c is still the matrix instructions' operand when chunk c + 2 is requested), the B fragments as before
 __global__ __launch_bounds__(DP_THREADS, 2) void dense_pairs_kernel(DenseDims d, const unsigned short* __restrict__ wpair,
@@ -134,18 +195,13 @@ __global__ __launch_bounds__(DP_THREADS, 2) void dense_pairs_kernel(DenseDims d,
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r31 = lane & 31, h = lane >> 5;
-    const unsigned lds0 = lds_addr(dp_lds);
-    typedef __attribute__((address_space(3))) const bf16x8 lds_cbf8;
-    int parity = 0;
+    const unsigned lds0 = lds_addr_of(dp_lds);
+    TileQueue queue{s_next};
     for (int item = blockIdx.x; item < total_items;) {
-        int nx = 0;
-        if (tid == 0)
-            asm volatile("s_nop 4\n\tglobal_atomic_add %0, %1, %2, %3 sc0" : "=v"(nx) : "v"(0), "v"(1), "s"(item_counter) : "memory");
-        int t = item;
-        const int mt = t % d.mtiles; t /= d.mtiles;
-        const int nt = t % d.ntiles;
-        const int ks = t / d.ntiles;
-        const int c0 = ks * d.cpp, c1 = c0 + d.cpp < d.chunks ? c0 + d.cpp : d.chunks;
+        int nx = queue.request(item_counter);
+        DenseItem it;
+        dense_item(d, item, it);
+        const int mt = it.mt, nt = it.nt, ks = it.ks, c0 = it.c0, c1 = it.c1;
         // this wave's fragments of chunk c: 4 KB at ((mt * chunks + c) * 8 + wave) * 4 KB; (step s, piece q) at ((2 s + q) * 64 + lane) * 16
         const bf16x8* wbase = reinterpret_cast<const bf16x8*>(wpair) + ((size_t)mt * d.chunks * 8 + wave) * 256 + lane;
         const unsigned char* xsrc = reinterpret_cast<const unsigned char*>(xfrag) + (size_t)nt * d.chunks * DP_STAGE<NP>;
@@ -158,15 +214,7 @@ __global__ __launch_bounds__(DP_THREADS, 2) void dense_pairs_kernel(DenseDims d,
 #pragma unroll
                 for (int q = 0; q < NP; ++q) af[o][s][q] = src[(2 * s + q) * 64];
         };
-        auto issue_b = [&](int c) {                           // 8 NP fragments of 1 KB: wave w brings NP w .. NP w + NP - 1
-            const unsigned char* src = xsrc + (size_t)c * DP_STAGE<NP>;
-            const unsigned dst = lds0 + (unsigned)((c % DP_NST) * DP_STAGE<NP>);
-#pragma unroll
-            for (int k = 0; k < NP; ++k) {
-                const int f = NP * wave + k;
-                dma16((unsigned)(f * 1024 + lane * 16), src, __builtin_amdgcn_readfirstlane(dst + (unsigned)f * 1024u));
-            }
-        };
+        auto issue_b = [&](int c) { dense_issue_b<NP>(xsrc, lds0, c, wave, lane); };
         f32x16 acc[4], tq[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -179,9 +227,8 @@ __global__ __launch_bounds__(DP_THREADS, 2) void dense_pairs_kernel(DenseDims d,
         int fold = 0;
         auto chunk = [&](auto o_tag, auto o2_tag, int c) {   // o: this chunk's register set, o2: the set of chunk c + 2
             constexpr int o = decltype(o_tag)::value;
-            // chunk c's weights and B fragments (own pieces) have landed; younger: chunk c + 1's 4 + NP requests
-            if (c + 1 < c1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 + NP) : "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (c == c0 && tid == 0) { asm volatile("" : "+v"(nx)); s_next[parity] = nx + (int)gridDim.x; }
+            dense_wait_chunk<NP>(c + 1 < c1);
+            if (c == c0 && tid == 0) { asm volatile("" : "+v"(nx)); queue.publish(nx); }   // (the atomic is older than chunk c0's requests)
             __builtin_amdgcn_s_barrier();                    // ... for every wave; and every wave is done with chunk c - 1's stage
             if (c + 2 < c1) { load_a(c + 2, o2_tag); issue_b(c + 2); }   // (stage (c + 2) % 3 and set (c + 2) % 3 held chunk c - 1)
             const unsigned stage = lds0 + (unsigned)((c % DP_NST) * DP_STAGE<NP> + lane * 16);
@@ -200,15 +247,7 @@ __global__ __launch_bounds__(DP_THREADS, 2) void dense_pairs_kernel(DenseDims d,
                         tq[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, af[o][s][PA[pr]]),
                                                                        __builtin_bit_cast(f16x8, bfr[j][PB[pr]]), tq[j], 0, 0, 0);
             }
-            if (++fold == DP_FOLD || c + 1 == c1) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    acc[j] += tq[j];
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) tq[j][e] = 0.f;
-                }
-                fold = 0;
-            }
+            dense_fold(acc, tq, fold, c, c1);
         };
         int c = c0;
         for (; c + 2 < c1; c += 3) {
@@ -218,21 +257,8 @@ __global__ __launch_bounds__(DP_THREADS, 2) void dense_pairs_kernel(DenseDims d,
         }
         if (c < c1) chunk(std::integral_constant<int, 0>(), std::integral_constant<int, 2>(), c);
         if (c + 1 < c1) chunk(std::integral_constant<int, 1>(), std::integral_constant<int, 0>(), c + 1);
-        // ---- partials [k part][image][output]: accumulator register 4 q + e = row 8 q + 4 h + e of this wave's 32-row block ----
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int n = nt * DP_BN + 32 * j + r31;
-            if (n >= d.N) continue;
-            float* prow = part + ((size_t)ks * d.N + n) * d.OC + mt * DP_BM + 32 * wave + 4 * h;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                if (mt * DP_BM + 32 * wave + 8 * q >= d.OC) continue;
-                f32x4v v4 = {acc[j][4 * q] * d.oscale, acc[j][4 * q + 1] * d.oscale, acc[j][4 * q + 2] * d.oscale, acc[j][4 * q + 3] * d.oscale};
-                *reinterpret_cast<f32x4v*>(prow + 8 * q) = v4;
-            }
-        }
-        item = __builtin_amdgcn_readfirstlane(s_next[parity]);
-        parity ^= 1;
+        dense_store_partials(d.N, d.OC, d.oscale, mt, nt, ks, acc, part, wave, r31, h);
+        item = queue.next();
     }
 }
 
@@ -245,43 +271,30 @@ __global__ __launch_bounds__(DP_THREADS, 2) void dense_pieces_kernel(DenseDims d
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r31 = lane & 31, h = lane >> 5;
-    const unsigned lds0 = lds_addr(dp_lds);
-    typedef __attribute__((address_space(3))) const bf16x8 lds_cbf8;
-    int parity = 0;
+    const unsigned lds0 = lds_addr_of(dp_lds);
+    TileQueue queue{s_next};
     if (d.live) {                                        // recompute pass: the column tiles of the device count's images
         d.N = __builtin_amdgcn_readfirstlane(*d.live);
         d.ntiles = (d.N + DP_BN - 1) / DP_BN;
         total_items = d.mtiles * d.ntiles * d.kparts;
     }
     for (int item = blockIdx.x; item < total_items;) {
-        int nx = 0;
-        if (tid == 0)
-            asm volatile("s_nop 4\n\tglobal_atomic_add %0, %1, %2, %3 sc0" : "=v"(nx) : "v"(0), "v"(1), "s"(item_counter) : "memory");
-        int t = item;
-        const int mt = t % d.mtiles; t /= d.mtiles;
-        const int nt = t % d.ntiles;
-        const int ks = t / d.ntiles;
-        const int c0 = ks * d.cpp, c1 = c0 + d.cpp < d.chunks ? c0 + d.cpp : d.chunks;
+        int nx = queue.request(item_counter);
+        DenseItem it;
+        dense_item(d, item, it);
+        const int mt = it.mt, nt = it.nt, ks = it.ks, c0 = it.c0, c1 = it.c1;
         const int row = mt * DP_BM + 32 * wave + r31;
         const bool row_ok = row < d.OC;
         // (weights in TILE order, dense_tile_weights_kernel: a chunk of a tile is 32 KB contiguous, a wave's 32 rows 4 KB of it)
-        const f32x4v* wrow = reinterpret_cast<const f32x4v*>(w + ((size_t)mt * d.chunks * DP_BM + 32 * wave + r31) * DP_CHUNK + 16 * h);
+        const f32x4* wrow = reinterpret_cast<const f32x4*>(w + ((size_t)mt * d.chunks * DP_BM + 32 * wave + r31) * DP_CHUNK + 16 * h);
         const unsigned char* xsrc = reinterpret_cast<const unsigned char*>(xfrag) + (size_t)nt * d.chunks * DP_STAGE<NP>;
-        f32x4v araw[2][4];                                   // the 16 weights of this lane for chunks c and c + 1 (two register sets)
+        f32x4 araw[2][4];                                   // the 16 weights of this lane for chunks c and c + 1 (two register sets)
         auto load_a = [&](int c, auto o_tag) {
             constexpr int o = decltype(o_tag)::value;
 #pragma unroll
             for (int q = 0; q < 4; ++q) araw[o][q] = wrow[(size_t)c * (DP_BM * DP_CHUNK / 4) + q];
         };
-        auto issue_b = [&](int c) {                           // 8 NP fragments of 1 KB: wave w brings NP w .. NP w + NP - 1
-            const unsigned char* src = xsrc + (size_t)c * DP_STAGE<NP>;
-            const unsigned dst = lds0 + (unsigned)((c % DP_NST) * DP_STAGE<NP>);
-#pragma unroll
-            for (int k = 0; k < NP; ++k) {
-                const int f = NP * wave + k;
-                dma16((unsigned)(f * 1024 + lane * 16), src, __builtin_amdgcn_readfirstlane(dst + (unsigned)f * 1024u));
-            }
-        };
+        auto issue_b = [&](int c) { dense_issue_b<NP>(xsrc, lds0, c, wave, lane); };
         f32x16 acc[4], tq[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -297,9 +310,8 @@ __global__ __launch_bounds__(DP_THREADS, 2) void dense_pieces_kernel(DenseDims d
         // for its own LDS reads.)
         auto chunk = [&](auto o_tag, int c) {
             constexpr int o = decltype(o_tag)::value;
-            // chunk c's weights and B fragments (own pieces) have landed; younger: chunk c + 1's 4 + NP requests
-            if (c + 1 < c1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 + NP) : "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (c == c0 && tid == 0) { asm volatile("" : "+v"(nx)); s_next[parity] = nx + (int)gridDim.x; }
+            dense_wait_chunk<NP>(c + 1 < c1);
+            if (c == c0 && tid == 0) { asm volatile("" : "+v"(nx)); queue.publish(nx); }   // (the atomic is older than chunk c0's requests)
             __builtin_amdgcn_s_barrier();                    // ... for every wave; and every wave is done with chunk c - 1's stage
             // split this lane's 16 weights: step A = values 0..7, step B = values 8..15
             bf16x8 af[2][NP];
@@ -339,15 +351,7 @@ __global__ __launch_bounds__(DP_THREADS, 2) void dense_pieces_kernel(DenseDims d
                                                                             __builtin_bit_cast(f16x8, bfr[j][PB[pr]]), tq[j], 0, 0, 0);
                     }
             }
-            if (++fold == DP_FOLD || c + 1 == c1) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    acc[j] += tq[j];
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) tq[j][e] = 0.f;
-                }
-                fold = 0;
-            }
+            dense_fold(acc, tq, fold, c, c1);
         };
         int c = c0;
         for (; c + 1 < c1; c += 2) {
@@ -355,21 +359,8 @@ __global__ __launch_bounds__(DP_THREADS, 2) void dense_pieces_kernel(DenseDims d
             chunk(std::integral_constant<int, 1>(), c + 1);
         }
         if (c < c1) chunk(std::integral_constant<int, 0>(), c);
-        // ---- partials [k part][image][output]: accumulator register 4 q + e = row 8 q + 4 h + e of this wave's 32-row block ----
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int n = nt * DP_BN + 32 * j + r31;
-            if (n >= d.N) continue;
-            float* prow = part + ((size_t)ks * d.N + n) * d.OC + mt * DP_BM + 32 * wave + 4 * h;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                if (mt * DP_BM + 32 * wave + 8 * q >= d.OC) continue;
-                f32x4v v4 = {acc[j][4 * q] * d.oscale, acc[j][4 * q + 1] * d.oscale, acc[j][4 * q + 2] * d.oscale, acc[j][4 * q + 3] * d.oscale};
-                *reinterpret_cast<f32x4v*>(prow + 8 * q) = v4;
-            }
-        }
-        item = __builtin_amdgcn_readfirstlane(s_next[parity]);
-        parity ^= 1;
+        dense_store_partials(d.N, d.OC, d.oscale, mt, nt, ks, acc, part, wave, r31, h);
+        item = queue.next();
     }
 }
 

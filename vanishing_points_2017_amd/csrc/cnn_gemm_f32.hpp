@@ -1,15 +1,13 @@
 // cnn_gemm_f32.hpp -- the f32 implicit-GEMM path of every conv / dense layer on the exact-f32 matrix cores
-// (v_mfma_f32_32x32x2_f32): conv_gemm_dma_kernel with its LDS-DMA helpers and the conv1 patch constants its fused
-// epilogue shares with the other conv1 kernels, the split-K reduction of the dense layers and the load-time weight
-// re-pack into k-major panels.  Included by vpk_cnn.hip first: the later headers use its typedefs and constants.
+// (v_mfma_f32_32x32x2_f32): conv_gemm_dma_kernel, the split-K reduction of the dense layers and the load-time weight
+// re-pack into k-major panels.  Included by vpk_cnn.hip.
 #ifndef VPK_CNN_GEMM_F32_HPP_
 #define VPK_CNN_GEMM_F32_HPP_
 
 #include "cnn_model.hpp"   // ConvDims, BK, C1_*
+#include "cnn_prims.hpp"   // f32x16, LDS-DMA, waits, TileQueue
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int CONV_THREADS = 256;
 
@@ -33,29 +31,8 @@ constexpr int CONV_THREADS = 256;
 // DMA uses the saddr form (64-bit SGPR base + 32-bit VGPR offset); the lane offsets are computed once
 // per workgroup.  Columns beyond N (last tile) re-read column N-1 and are not stored.
 // --------------------------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-// LDS-DMA issued from inline asm: hipcc knows that the global_load_lds builtin writes LDS and puts an
-// s_waitcnt vmcnt(0) in front of the next ds_read, which drains the stage that was just issued and
-// defeats the pipeline.  An asm statement is outside its bookkeeping; completion is counted by hand
-// (wait_stage below).  M0 = wave-uniform LDS byte address of the destination (the hardware adds
-// lane * size); M0 is compiler-reserved, so it is saved and restored inside the statement.  The three
-// scalar instructions in front of the load give 5 wait states: hipcc may have written the SGPR operands
-// with v_readlane / v_readfirstlane just before (VALU-writes-SGPR -> VMEM hazard it cannot see in asm).
-__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)(lds_ptr_t)p; }
-__device__ __forceinline__ void dma16(unsigned voff, const void* sbase, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 2\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void dma4(unsigned voff, const void* sbase, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 2\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
+// (lds_dma16 / lds_dma4, wait_vmcnt, lds_barrier and the tile queue: cnn_prims.hpp, which also says why they are inline asm;
+//  completion of a stage's DMA is counted by wait_stage below)
 
 // conv1 + norm1 + pool1 as ONE kernel (C1FUSE): a tile's 128 columns are a 2-D patch of 7 x 17 conv1 outputs
 // (all 96 channels: one M tile, so the LRN across channels is local to the tile); after the K loop the patch
@@ -87,23 +64,15 @@ __global__ __launch_bounds__(CONV_THREADS, WPC) void conv_gemm_dma_kernel(ConvDi
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-    // Persistent workgroups over a dynamic tile queue: the first gridDim.x tiles are taken statically, the
-    // rest from an atomic counter.  (With a static grid the workgroups are dealt round-robin to the XCDs, and
-    // CUs that another stream's kernel holds -- the EM runs beside the CNN -- make their XCD the straggler.)
-    // The next index is fetched at the start of a tile and published through LDS, so its latency is hidden.
     __shared__ int s_next[2];
-    int parity = 0;
+    TileQueue queue{s_next};                            // persistent workgroups over the layer's tiles (cnn_prims.hpp)
     if (!C1FUSE && live) {                              // recompute pass (vpk_cnn_set_range_policy): the device count's images only
         d.B = __builtin_amdgcn_readfirstlane(*live);
         d.N = d.B * d.OH * d.OW;
         total_tiles = d.groups * d.ksplit * ((d.N + BN - 1) / BN) * (d.Mp / BM);
     }
     for (int tile = blockIdx.x; tile < total_tiles;) {
-    int nx = 0;
-    if (tid == 0)    // ONE lane; the oldest outstanding vector-memory op of wave 0: complete at the first wait_stage
-        // (s_nop 4: hipcc may have produced the SGPR pair with v_readlane right before this statement and
-        //  cannot see that the instruction inside reads it -- VALU-writes-SGPR -> VMEM needs 5 wait states)
-        asm volatile("s_nop 4\n\tglobal_atomic_add %0, %1, %2, %3 sc0" : "=v"(nx) : "v"(0), "v"(1), "s"(tile_counter) : "memory");
+    int nx = queue.request(tile_counter);               // the oldest vector-memory op of wave 0: complete at the first wait_stage
     const int mtiles = d.Mp / BM;
     int bid = tile;
     const int mt = bid % mtiles; bid /= mtiles;
@@ -162,7 +131,7 @@ __global__ __launch_bounds__(CONV_THREADS, WPC) void conv_gemm_dma_kernel(ConvDi
         const int kk = (idx * 4) / BM, m = (idx * 4) % BM;
         aoff[r] = (unsigned)(kk * d.Mp + m) * 4u;
     }
-    const unsigned as_base = lds_addr(&As[0][0][0]), bs_base = lds_addr(&Bs[0][0][0]);
+    const unsigned as_base = lds_addr_of(&As[0][0][0]), bs_base = lds_addr_of(&Bs[0][0][0]);
     auto issue = [&](int kt, int buf) {
         const int k0 = kt * BK;
         const float* abase = wpan + (size_t)k0 * d.Mp;
@@ -170,13 +139,13 @@ __global__ __launch_bounds__(CONV_THREADS, WPC) void conv_gemm_dma_kernel(ConvDi
         for (int r = 0; r < A_IT; ++r) {
             const int idx0 = r * CONV_THREADS + wave * 64;         // wave-uniform first float4 of this piece
             if (idx0 < A_F4)
-                dma16(aoff[r], abase, __builtin_amdgcn_readfirstlane(as_base + (unsigned)((buf * BK * BM + idx0 * 4) * 4)));
+                lds_dma16(aoff[r], abase, __builtin_amdgcn_readfirstlane(as_base + (unsigned)((buf * BK * BM + idx0 * 4) * 4)));
         }
         if (DENSE) {
 #pragma unroll
             for (int q = 0; q < 2; ++q) {                            // this wave's two k quads (of four), its half of the columns
                 const int kq = (wave >> 1) * 2 + q;
-                dma16(boff, bbase + k0 + 4 * kq, __builtin_amdgcn_readfirstlane(
+                lds_dma16(boff, bbase + k0 + 4 * kq, __builtin_amdgcn_readfirstlane(
                           bs_base + (unsigned)((buf * BK * BN + (kq * BN + (wave & 1) * 64) * 4) * 4)));
             }
             return;
@@ -187,7 +156,7 @@ __global__ __launch_bounds__(CONV_THREADS, WPC) void conv_gemm_dma_kernel(ConvDi
         for (int q = 0; q < 8; ++q) e[q] = ktab[kb + q];            // wave-uniform byte offsets: scalar loads
 #pragma unroll
         for (int q = 0; q < 8; ++q)
-            dma4(boff, (const char*)bbase + e[q], __builtin_amdgcn_readfirstlane(
+            lds_dma4(boff, (const char*)bbase + e[q], __builtin_amdgcn_readfirstlane(
                                 bs_base + (unsigned)(((buf * BK + kset * 8 + q) * BN + (wave & 1) * 64) * 4)));
     };
     // DMA instructions one thread issues per stage (waves whose A piece falls outside issue one less)
@@ -219,9 +188,8 @@ __global__ __launch_bounds__(CONV_THREADS, WPC) void conv_gemm_dma_kernel(ConvDi
     if (AHEAD > 1 && nk > 1) issue(kt0 + 1, 1);
     wait_stage(AHEAD > 1 && nk > 1);
     asm volatile("" : "+v"(nx));                        // the atomic's result has landed (it is older than stage 0)
-    if (tid == 0) s_next[parity] = nx + (int)gridDim.x;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    queue.publish(nx);
+    lds_barrier();
     for (int t = 0; t < nk; ++t) {
         const int buf = t % NST;
         if (t + AHEAD < nk) issue(kt0 + t + AHEAD, (t + AHEAD) % NST);
@@ -251,8 +219,7 @@ __global__ __launch_bounds__(CONV_THREADS, WPC) void conv_gemm_dma_kernel(ConvDi
             __builtin_amdgcn_sched_barrier(0);
         }
         wait_stage(AHEAD > 1 && t + 2 < nk);            // stage t+1 has landed (own pieces) ...
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();                   // ... for every wave; stage t's buffer is free again
+        lds_barrier();                                  // ... for every wave; stage t's buffer is free again
     }
 
     // Epilogue.  The 32 x 32 accumulator tile holds rows 8q + 4 khalf + (0..3) in registers 4q .. 4q + 3: a
@@ -362,8 +329,7 @@ __global__ __launch_bounds__(CONV_THREADS, WPC) void conv_gemm_dma_kernel(ConvDi
         }
     }
     }
-    tile = __builtin_amdgcn_readfirstlane(s_next[parity]);
-    parity ^= 1;
+    tile = queue.next();
     }   // tile loop
 }
 

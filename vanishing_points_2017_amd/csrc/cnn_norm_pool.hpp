@@ -1,8 +1,10 @@
 // cnn_norm_pool.hpp -- the f32 element-wise stages between the GEMMs: conv1's input pre-pass (prep_input_kernel), LRN + max
 // pool fused (norm1 / pool1 tiled, norm2 / pool2 as a stream over the channels), pool5, and the tap-only unpad of bordered
-// planes.  Included by vpk_cnn.hip after cnn_conv1_direct.hpp (C1_* constants, f32x4).
+// planes.  Included by vpk_cnn.hip (the C1_* constants: cnn_model.hpp).
 #ifndef VPK_CNN_NORM_POOL_HPP_
 #define VPK_CNN_NORM_POOL_HPP_
+
+#include "cnn_prims.hpp"   // f32x4
 
 namespace {
 

@@ -16,6 +16,8 @@
 #ifndef VPK_CNN_NORM_POOL_PLANES_HPP_
 #define VPK_CNN_NORM_POOL_PLANES_HPP_
 
+#include "cnn_prims.hpp"   // f32x2, u32x4
+
 namespace {
 
 template <int TPH>
@@ -98,7 +100,7 @@ __global__ __launch_bounds__(256) void lrn5_pool3s2_planes_kernel(const float* _
                 float mm = 0.f;                          // (every value is >= 0: ReLU, then a positive factor)
 #pragma unroll
                 for (int dy = 0; dy < 3; ++dy) {
-                    const f32x2v a = *reinterpret_cast<const f32x2v*>(w0 + k * PMAX + dy * LW);
+                    const f32x2 a = *reinterpret_cast<const f32x2*>(w0 + k * PMAX + dy * LW);
                     const float c = w0[k * PMAX + dy * LW + 2];
                     mm = __builtin_fmaxf(mm, __builtin_fmaxf(__builtin_fmaxf(a[0], a[1]), c));
                 }

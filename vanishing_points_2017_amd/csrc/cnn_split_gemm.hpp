@@ -27,10 +27,7 @@
 #ifndef VPK_CNN_SPLIT_GEMM_HPP_
 #define VPK_CNN_SPLIT_GEMM_HPP_
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+#include "cnn_prims.hpp"   // bf16x8, f32x4, f32x16, LDS-DMA, waits, TileQueue
 
 // (SplitDims and the tile's 256 columns, SG_BN: cnn_model.hpp)
 // f32 -> three bf16 pieces, each the round-to-nearest-even bf16 of what is left: x - p0 and (x - p0) - p1 are exact in
@@ -105,7 +102,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, WPE) void conv_gemm_split_k
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-    const unsigned lds0 = lds_addr(sg_lds);
+    const unsigned lds0 = lds_addr_of(sg_lds);
     const int mtiles = d.mblocks / MB;
     const int ntiles = (d.N + SG_BN - 1) / SG_BN;
     const int ohw = d.OH * d.OW;
@@ -113,14 +110,12 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, WPE) void conv_gemm_split_k
     // every wave brings NB / NWAVES column blocks
     constexpr int CB = NB / NWAVES;                      // column blocks per wave
     const int na_mine = (NA - wave + NWAVES - 1) / NWAVES;   // wave-uniform
-    int parity = 0;
+    TileQueue queue{s_next};
 #ifdef SG_TIME
     long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = (long long)__builtin_amdgcn_s_memtime();
 #endif
     for (int tile = blockIdx.x; tile < total_tiles;) {
-        int nx = 0;
-        if (tid == 0)
-            asm volatile("s_nop 4\n\tglobal_atomic_add %0, %1, %2, %3 sc0" : "=v"(nx) : "v"(0), "v"(1), "s"(tile_counter) : "memory");
+        int nx = queue.request(tile_counter);
         int bid = tile;
         const int mt = bid % mtiles; bid /= mtiles;
         const int nt = bid % ntiles;
@@ -163,12 +158,12 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, WPE) void conv_gemm_split_k
 #pragma unroll
             for (int q = 0; q < (NA + NWAVES - 1) / NWAVES; ++q) {
                 const int f = wave + NWAVES * q;          // wave-uniform
-                if (f < NA) dma16(aoff[q], i_w, __builtin_amdgcn_readfirstlane(stage + (unsigned)f * 1024u));
+                if (f < NA) lds_dma16(aoff[q], i_w, __builtin_amdgcn_readfirstlane(stage + (unsigned)f * 1024u));
             }
             const unsigned char* bst = bgrp + ((size_t)(i_kh * d.Wp + i_kw) * d.Ctot + i_c0) * 6;
 #pragma unroll
             for (int q = 0; q < 3 * CB; ++q)
-                dma16(boff[q], bst, __builtin_amdgcn_readfirstlane(stage + (unsigned)((NA + wave * 3 * CB + q) * 1024)));
+                lds_dma16(boff[q], bst, __builtin_amdgcn_readfirstlane(stage + (unsigned)((NA + wave * 3 * CB + q) * 1024)));
             i_w += wstep;
             i_buf = i_buf + 1 == NST ? 0 : i_buf + 1;
             if (++i_kw == d.KW) {
@@ -196,9 +191,8 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, WPE) void conv_gemm_split_k
         if (AHEAD > 1 && nk > 1) issue();
         wait_stage(AHEAD > 1 && nk > 1);
         asm volatile("" : "+v"(nx));                     // the atomic's result has landed (it is older than stage 0)
-        if (tid == 0) s_next[parity] = nx + (int)gridDim.x;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
+        queue.publish(nx);
+        lds_barrier();
         SG_T(0)
         int buf = NST - 1;
         for (int t = 0; t < nk; ++t) {
@@ -260,8 +254,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, WPE) void conv_gemm_split_k
             SG_T(2)
             wait_stage(AHEAD > 1 && t + 2 < nk);         // stage t + 1 has landed (own pieces) ...
             SG_T(3)
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();                // ... for every wave; stage t's buffer is free again
+            lds_barrier();                               // ... for every wave; stage t's buffer is free again
             SG_T(4)
         }
         // ---- epilogue: bias + ReLU, f32 NCHW planes (accumulator register 4 q + e = row 8 q + 4 (lane / 32) + e) ----
@@ -283,7 +276,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, WPE) void conv_gemm_split_k
                 for (int q = 0; q < 4; ++q) {
                     const int m0 = __builtin_amdgcn_readfirstlane((mt * MB + wm * TM + i) * 32 + 8 * q);
                     if (m0 >= d.OC) continue;
-                    const f32x4v bl = *reinterpret_cast<const f32x4v*>(bias + g * d.OC + m0 + 4 * khalf);   // this lane's 4 rows
+                    const f32x4 bl = *reinterpret_cast<const f32x4*>(bias + g * d.OC + m0 + 4 * khalf);   // this lane's 4 rows
                     float v[4];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
@@ -310,8 +303,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, WPE) void conv_gemm_split_k
                 }
         }
         SG_T(5)
-        tile = __builtin_amdgcn_readfirstlane(s_next[parity]);
-        parity ^= 1;
+        tile = queue.next();
     }
 #ifdef SG_TIME
     if (lane == 0 && blockIdx.x < 256)

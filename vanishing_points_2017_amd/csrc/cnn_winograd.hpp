@@ -1,5 +1,5 @@
 // cnn_winograd.hpp -- conv3 / conv4 / conv5 of cnn/deploy.prototxt (:104-174: 3 x 3, stride 1, pad 1, 30 x 30 planes) by
-// Winograd's minimal filtering F(2 x 2, 3 x 3) on the f32 matrix cores.  Included by vpk_cnn.hip (uses cnn_gemm_f32.hpp's DMA helpers).
+// Winograd's minimal filtering F(2 x 2, 3 x 3) on the f32 matrix cores.  Included by vpk_cnn.hip.
 //
 // A 2 x 2 block of outputs of one channel is  Y = A^T [ (G g G^T) (.) (B^T d B) ] A  with d the 4 x 4 input patch, g the 3 x 3
 // filter and (.) the element-wise product summed over the input channels: 16 multiplications per input channel instead
@@ -24,6 +24,8 @@
 //     applies A^T . A, bias and ReLU and stores the 2 x 2 outputs into the consumer's bordered planes.
 #ifndef VPK_CNN_WINOGRAD_HPP_
 #define VPK_CNN_WINOGRAD_HPP_
+
+#include "cnn_prims.hpp"   // f32x16, LDS-DMA, waits, TileQueue
 
 namespace {
 
@@ -71,24 +73,20 @@ __global__ __launch_bounds__(WG_THREADS, 1) void conv3x3_winograd_kernel(WinoDim
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int khalf = lane >> 5, l31 = lane & 31;
-    const unsigned us_base = lds_addr(&Us[0][0][0][0]);
+    const unsigned us_base = lds_addr_of(&Us[0][0][0][0]);
     if (live) {                                         // recompute pass (vpk_cnn_set_range_policy): the device count's images only
         d.tiles = __builtin_amdgcn_readfirstlane(*live) * WG_TILES_PER_IMAGE;
         total_tiles = d.groups * d.ocblocks * ((d.tiles + WG_TB - 1) / WG_TB);
     }
     const int nblocks = (d.tiles + WG_TB - 1) / WG_TB;
-    // persistent workgroups over a dynamic tile queue (the first gridDim.x tiles are static): beside another stream's kernel
-    // that holds CUs (the EM), a static deal leaves the workgroups of the busy XCDs behind
-    // (two slots used in turn, like the other persistent kernels: with one, thread 0 of a wave that has gone round could
-    //  overwrite the index before a slower wave has read it -- no barrier separates that read from the next write)
     __shared__ int s_next[2];
-    int parity = 0;
+    TileQueue queue{s_next};                            // (cnn_prims.hpp; the immediate form)
 #ifdef W5_TIME
     long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     long long tlast = __builtin_readcyclecounter();
 #endif
     for (int tile = blockIdx.x; tile < total_tiles;) {
-        if (tid == 0) s_next[parity] = atomicAdd(tile_counter, 1) + (int)gridDim.x;   // read after the K loop's barriers
+        queue.take(tile_counter);                       // read after the K loop's barriers
         int t = tile;
         const int ob = t % d.ocblocks; t /= d.ocblocks;     // output-channel blocks of the same tiles next to each other (L2)
         const int tb = t % nblocks;
@@ -137,7 +135,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void conv3x3_winograd_kernel(WinoDim
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int piece = wave + 8 * q;
-                dma16((unsigned)lane * 16u, src + piece * 256,
+                lds_dma16((unsigned)lane * 16u, src + piece * 256,
                       __builtin_amdgcn_readfirstlane(us_base + (unsigned)((buf * 16 * WG_KC * WG_OCB + piece * 256) * 4)));
             }
         };
@@ -157,8 +155,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void conv3x3_winograd_kernel(WinoDim
         fetch(0);
         transform(0);
         wait_vmcnt<0>();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
+        lds_barrier();
         W5_LAP(3);
         for (int c = 0; c < d.chunks; ++c) {
             const int buf = c & 1;
@@ -197,8 +194,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void conv3x3_winograd_kernel(WinoDim
             if (more) transform(buf ^ 1);
             W5_LAP(0);
             wait_vmcnt<0>();                            // the next chunk's U has landed (own pieces) ...
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();               // ... for every wave; this chunk's buffers are free
+            lds_barrier();                              // ... for every wave; this chunk's buffers are free
             W5_LAP(2);
         }
 
@@ -257,8 +253,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void conv3x3_winograd_kernel(WinoDim
             __syncthreads();
             W5_LAP(5);
         }
-        tile = __builtin_amdgcn_readfirstlane(s_next[parity]);
-        parity ^= 1;
+        tile = queue.next();
     }
 #ifdef W5_TIME
     if (lane == 0 && blockIdx.x < 256)
@@ -345,8 +340,8 @@ __global__ __launch_bounds__(W5_THREADS, 1) void conv5x5_winograd_kernel(Wino5Di
     __shared__ __attribute__((aligned(16))) float Vs[2][W5_P][W5_KC][W5_NB];     // 36 KB
     __shared__ __attribute__((aligned(16))) float Sw[12][10][6][7];              // 20 KB: per wave, B^T d of its ten pairs [pair][i][column] (row stride 7)
     float (*Ms)[16][W5_NB] = reinterpret_cast<float (*)[16][W5_NB]>(&Us[0][0][0][0]);   // epilogue: [p][row][tile] = 72 KB over Us
-    __shared__ int s_next[2];                          // two slots used in turn (see the 3 x 3 kernel)
-    int parity = 0;
+    __shared__ int s_next[2];
+    TileQueue queue{s_next};
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int khalf = lane >> 5, l31 = lane & 31;
@@ -355,7 +350,7 @@ __global__ __launch_bounds__(W5_THREADS, 1) void conv5x5_winograd_kernel(Wino5Di
     const int tq = t_on ? lane / 6 : 9, tc = t_on ? lane - 6 * (lane / 6) : 5;
     const int tpair = 10 * wave + tq;                   // 0..119 = channel * 30 + tile
     const int tch = tpair / W5_TB, ttile = tpair - tch * W5_TB;
-    const unsigned us_base = lds_addr(&Us[0][0][0][0]);
+    const unsigned us_base = lds_addr_of(&Us[0][0][0][0]);
     const int nblocks = (d.tiles + W5_TB - 1) / W5_TB;
     for (int q = tid; q < 2 * W5_P * W5_KC * W5_NB; q += W5_THREADS) (&Vs[0][0][0][0])[q] = 0.f;   // (columns 30, 31 stay zero)
     __syncthreads();
@@ -364,7 +359,7 @@ __global__ __launch_bounds__(W5_THREADS, 1) void conv5x5_winograd_kernel(Wino5Di
     long long tlast = __builtin_readcyclecounter();
 #endif
     for (int tile = blockIdx.x; tile < total_tiles;) {
-        if (tid == 0) s_next[parity] = atomicAdd(tile_counter, 1) + (int)gridDim.x;     // read after the K loop's barriers
+        queue.take(tile_counter);                       // read after the K loop's barriers
         int t = tile;
         const int ob = t % d.ocblocks; t /= d.ocblocks;
         const int tb = t % nblocks;
@@ -414,7 +409,7 @@ __global__ __launch_bounds__(W5_THREADS, 1) void conv5x5_winograd_kernel(Wino5Di
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
                 const int piece = wave + 12 * q;
-                dma16((unsigned)lane * 16u, src + piece * 256,
+                lds_dma16((unsigned)lane * 16u, src + piece * 256,
                       __builtin_amdgcn_readfirstlane(us_base + (unsigned)((buf * W5_P * W5_KC * W5_OCB + piece * 256) * 4)));
             }
         };
@@ -432,7 +427,7 @@ __global__ __launch_bounds__(W5_THREADS, 1) void conv5x5_winograd_kernel(Wino5Di
         transform(0);
         if (d.chunks > 1) fetch(1);
         wait_vmcnt<0>();
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        raw_barrier();
         W5_LAP(3);
         for (int c = 0; c < d.chunks; ++c) {
             const int buf = c & 1;
@@ -475,7 +470,7 @@ __global__ __launch_bounds__(W5_THREADS, 1) void conv5x5_winograd_kernel(Wino5Di
             next_v();
             W5_LAP(1);
             wait_vmcnt<0>();                            // the next chunk's U has landed (own pieces) ...
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // ... for every wave; this chunk's buffers are free
+            raw_barrier();                              // ... for every wave; this chunk's buffers are free
             W5_LAP(2);
         }
 
@@ -534,8 +529,7 @@ __global__ __launch_bounds__(W5_THREADS, 1) void conv5x5_winograd_kernel(Wino5Di
             __syncthreads();
             W5_LAP(5);
         }
-        tile = __builtin_amdgcn_readfirstlane(s_next[parity]);
-        parity ^= 1;
+        tile = queue.next();
     }
 #ifdef W5_TIME
     if (lane == 0 && blockIdx.x < 256)

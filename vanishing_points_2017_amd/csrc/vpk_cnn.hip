@@ -9,6 +9,8 @@
 // This file is the driver: the loaded model (Layer, vpk_cnn_state), weight loading, run_forward -- one launch per stage of the plan
 // that cnn_plan.hpp resolves from the arithmetic settings -- and the C entry points.  It is the CNN's one translation unit; the
 // kernels are included:
+//   cnn_prims.hpp           what the matrix-core kernels share below their schedules: vector types, counted wait and LDS-only barrier,
+//                           LDS-DMA (with wave_prims.hpp), the persistent tile queue -- and why those are inline asm
 //   cnn_gemm_f32.hpp        implicit GEMM on the f32-input matrix cores (every layer's f32 form), split-K reduction, weight panels
 //   cnn_conv1_direct.hpp    conv1 + LRN + pool as one f32 kernel
 //   cnn_norm_pool.hpp       LRN + pool fused, pool5, conv1's input pre-pass, unpad (taps)
@@ -30,13 +32,15 @@
 
 #include "cnn_plan.hpp"
 #include "cnn_model.hpp"
+#include "cnn_prims.hpp"     // first of the device headers, and here at file scope: it brings wave_prims.hpp and the HIP runtime
 #include "cnn_gemm_f32.hpp"
 #include "cnn_conv1_direct.hpp"
 #include "cnn_norm_pool.hpp"
 
 namespace {
 
-// (these headers open an anonymous namespace of their own; they stay nested in this one so that their kernels keep their symbol names)
+// (these headers open an anonymous namespace of their own; they stay nested in this one so that their kernels keep their symbol names.
+//  Each names cnn_prims.hpp, which is already in -- at file scope, above: opened here it would put the HIP runtime's declarations in this namespace)
 #include "cnn_split_gemm.hpp"
 #include "cnn_pairs.hpp"
 #include "cnn_conv1_pieces.hpp"

@@ -1,8 +1,10 @@
-// wave_prims.hpp -- gfx950 wavefront / workgroup primitives used by the EM device code.
+// wave_prims.hpp -- gfx950 wavefront / workgroup primitives of the library's device code.
 //
 // Everything that touches a hardware intrinsic lives here: 64-lane butterfly reductions
 // (ds_swizzle/DPP via __shfl_xor), workgroup barriers and LDS-visible wave fences.  The EM
-// device code (em_device.hpp) is written against this small vocabulary only.
+// device code (em_device.hpp) is written against this small vocabulary only; the CNN's kernels
+// take the hand-counted part from it -- LDS-DMA, the counted wait, the raw barrier -- through
+// cnn_prims.hpp, which adds what only they use.
 #ifndef VPK_WAVE_PRIMS_HPP_
 #define VPK_WAVE_PRIMS_HPP_
 
@@ -246,11 +248,10 @@ VPK_DEV void wave_lds_order() {
 }
 
 // LDS-DMA (global_load_lds_dwordx4): the 64 lanes of a wave move 16 bytes each from (sbase + voff), sbase wave-uniform, to
-// LDS at lds_dst + 16 * lane -- no staging registers, no ds_write.  Issued from inline asm: the compiler does not know that
-// the instruction writes LDS and is not asked to; completion is counted by hand (wait_vm<N>: at most N vector-memory
-// operations of this wave still outstanding; they retire in order) and published to the other waves by a barrier.  M0
-// (compiler-reserved) carries the LDS address and is saved / restored inside the statement; the s_nop covers the wait
-// states after a VALU write of the SGPR operands, which the hazard recogniser cannot see inside an asm statement.
+// LDS at lds_dst + 16 * lane -- no staging registers, no ds_write.  Issued from inline asm, completion counted by hand
+// (wait_vm<N>: at most N vector-memory operations of this wave still outstanding; they retire in order) and published to
+// the other waves by a barrier.  Why asm, what the s_nop is for and why M0 is saved and restored: cnn_prims.hpp, "WHY
+// THESE OPERATIONS ARE INLINE ASM" -- the one copy of that explanation.
 VPK_DEV unsigned lds_addr_of(const void* p) { return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p; }
 VPK_DEV void lds_dma16(unsigned voff, const void* sbase, unsigned lds_dst) {
     unsigned keep;
